@@ -8,7 +8,14 @@ n_hidden=200, seq_len=10, batch=1024 per GPU, dropout 0.5, fp32, random-init wei
 Inputs are device-resident when the timed region starts: the batch graphs / packed layouts of the
 W+K steps are prepared (host builder + one upload each) before it; the per-step host build time is
 reported separately (`host_build_ms`) and an end-to-end rate with the builder in the loop as
-`e2e_value`.  Launch: python bench.py [--gpus N --steps K --warmup W].  For N > 1 either under
+`e2e_value`.  Launch: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR].
+
+A plain run (no --full) sets up, runs the W + K steps, optionally writes the outputs of its last timed step (the loss and
+the updated parameters, see dump_outputs) and prints the line: `value` and `ms_per_step` of the K timed steps.  --full
+adds everything else this script measures or checks: per-step event medians, the per-kernel table and rooflines, the
+host build and enqueue times, the encoder-only, list-API and end-to-end rates, the CPU baseline with the HIP-vs-oracle
+parity, the companion GEMM modes and the other BASELINE configs, the scaling companions (N > 1) and bench_detail.json.
+For N > 1 either under
 torch.distributed.run (one rank per GPU, RCCL: RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment) or
 plainly -- without WORLD_SIZE in the environment the script re-executes itself under torch.distributed.run with N
 ranks on 127.0.0.1.  Rank 0 prints ONE JSON line.
@@ -160,6 +167,39 @@ def write_detail(out):
     return name
 
 
+def prep_threads(world):
+    """Threads per rank that build the host halves of a plain run's batches: the CPUs this process may use
+    (OMP_NUM_THREADS when set, else its affinity) shared by the node's ranks, at most 8."""
+    cpus = int(os.environ.get('OMP_NUM_THREADS') or 0)
+    if cpus <= 0:
+        cpus = len(os.sched_getaffinity(0)) if hasattr(os, 'sched_getaffinity') else (os.cpu_count() or 1)
+    return max(1, min(8, cpus // max(1, world)))
+
+
+DUMP_LIMIT = 1 << 22    # elements per dumped array; a larger parameter is written as a fixed sample of this many
+
+
+def dump_outputs(path, net, last_loss):
+    """--dump-outputs: what a caller of the timed path holds after its last step -- the step's loss (`loss.npy`) and
+    every parameter as that step's clip + Adam update left it (`<parameter name>.npy`), float32.  A parameter of more
+    than DUMP_LIMIT elements is written as DUMP_LIMIT of its flat elements at indices drawn by
+    np.random.RandomState(zlib.crc32(name)) without replacement, in ascending order (39 MB in all at the default
+    sizes; never more than 64 MB).  Same arguments, same inputs: two builds can be compared file by file."""
+    import zlib
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, 'loss.npy'), np.asarray([last_loss], dtype=np.float32))
+    params = list(net.named_parameters())
+    limit = DUMP_LIMIT
+    while sum(min(p_.numel(), limit) for _, p_ in params) * 4 > (64 << 20) - 4096:
+        limit //= 2
+    for name, p_ in params:
+        flat = p_.detach().reshape(-1)
+        if flat.numel() > limit:
+            idx = np.sort(np.random.RandomState(zlib.crc32(name.encode())).choice(flat.numel(), limit, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        np.save(os.path.join(path, name + '.npy'), flat.float().cpu().numpy())
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -207,10 +247,18 @@ def parse():
     ap.add_argument('--other-steps', type=int, default=20,
                     help='steps of the other BASELINE.json configs (WIKI-shaped, GDELT-shaped, YAGO-shaped n_hidden 400 '
                          'seq_len 15 bf16 storage), each a child process reported under `other_configs` (0 = skip)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check everything beyond `value` (event medians, kernel table and rooflines, '
+                         'host build / enqueue times, encoder-only, list-API and end-to-end rates, CPU baseline and '
+                         'parity, companion modes, other configs, scaling companions) and write bench_detail.json; the '
+                         'option arguments above that size those extras only act with it')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='after the timed steps, write what the last timed step computed (its loss and the parameters '
+                         'it updated) as DIR/<name>.npy in float32; see dump_outputs()')
     ap.add_argument('--plain', action='store_true',
-                    help='only the W + K steps of `value` (no event-timed second pass, no companions, no CPU baseline): '
-                         'the command to put under rocprofv3 --kernel-trace --stats, so that the trace holds the product '
-                         'configuration alone')
+                    help='only the W + K steps of `value`, even with --full: the command to put under rocprofv3 '
+                         '--kernel-trace --stats, so that the trace holds the product configuration alone (a run without '
+                         '--full is this too)')
     ap.add_argument('--child', default='', help='(internal) this run is a companion of another: print the reduced record')
     return ap.parse_args()
 
@@ -232,7 +280,8 @@ def self_launch(args):
 
 def main():
     args = parse()
-    if args.plain:
+    if args.plain or not args.full:          # the headline alone: set up, W + K steps, outputs, the line
+        args.plain = True
         args.cpu_steps = args.enc_steps = args.e2e_steps = args.f32_steps = args.other_steps = args.companions = 0
         args.list_steps = 0
     rank = int(os.environ.get('RANK', '0'))
@@ -332,6 +381,27 @@ def main():
             return (net.prepare(b, hist_s.take(idx), graph_dict, subject=True),
                     net.prepare(b, hist_o.take(idx), graph_dict, subject=False))
 
+        def host_half(self, step):
+            """The host half of prepare(step) for a merged batch (model.host_batch_both: pure host work, no device
+            access); None where prepare() falls back to two passes."""
+            idx = self.indices(perm, step, rank)
+            return net.host_batch_both(quads[idx], hist_s.take(idx), hist_o.take(idx), graph_dict,
+                                       shard=self.shard(rank))
+
+        def prepare_all(self, n):
+            """prepare() of steps 0 .. n-1.  With --full one after the other (`host_build_ms` is that time per step);
+            a plain run has prep_threads() threads build the host halves of merged batches (pipeline.BatchPrefetcher)
+            and uploads them here in step order: the same batches in the same order, in a fraction of the setup time
+            (which would otherwise grow to minutes with --steps)."""
+            if not args.plain or self.passes != 'merged' or n < 2:
+                return [self.prepare(k) for k in range(n)]
+            import pipeline
+            out = [self.prepare(0)]          # (fills the builder's caches before the threads share them)
+            pf = pipeline.BatchPrefetcher(self.host_half, range(1, n), prep_threads(world), threads=True)
+            for k, hb in zip(range(1, n), pf):
+                out.append((net.prepare_both_from_host(hb),) if hb is not None else self.prepare(k))
+            return out
+
         def step_loss(self, *preps):
             if len(preps) == 1:              # same arithmetic per row; every kernel sees the rows of both passes
                 return net.loss_prepared_both(preps[0])
@@ -354,9 +424,9 @@ def main():
             host_ms = None
             if prepared is None:
                 t0 = time.time()
-                prepared = [self.prepare(k) for k in range(n_total)]
+                prepared = self.prepare_all(n_total)
                 torch.cuda.synchronize()
-                host_ms = (time.time() - t0) * 1e3 / max(n_total, 1)
+                host_ms = None if args.plain else (time.time() - t0) * 1e3 / max(n_total, 1)
             for k in range(args.warmup):
                 self.train_step(*prepared[k])
             assert flat.check_views(), 'param.grad views were replaced'
@@ -409,6 +479,8 @@ def main():
     # the timed region of `value`: the product configuration (side streams on, no per-kernel events) ...
     elapsed, last_loss, host_build_ms, prepared = mode.run()
     value = mode.global_batch * args.steps / elapsed
+    if args.dump_outputs and rank == 0:      # before anything below trains the parameters further
+        dump_outputs(args.dump_outputs, net, last_loss)
     # the same step measured two more ways (product configuration, same prepared batches): per-step HIP events over >= 100
     # steps whatever --steps says (median and spread), and the host's enqueue time over a 16-step window
     median_block = host_enqueue_ms = None
@@ -633,7 +705,7 @@ def main():
     pmc, pmc_file = {}, None
     legacy_mode = {'r02_pmc_traffic.json': 'bf16x6', 'r03_pmc_traffic.json': 'f16x3'}
     for name in sorted(os.listdir(os.path.join(ROOT, 'profiles')), reverse=True) \
-            if os.path.isdir(os.path.join(ROOT, 'profiles')) else []:
+            if (not args.plain and os.path.isdir(os.path.join(ROOT, 'profiles'))) else []:
         if '_pmc_traffic' in name and name.endswith('.json'):
             try:
                 with open(os.path.join(ROOT, 'profiles', name)) as f:
@@ -769,7 +841,7 @@ def main():
         cmd = [sys.executable, os.path.abspath(__file__), '--steps', str(steps), '--warmup', str(args.warmup),
                '--batch', str(args.batch), '--dropout', str(args.dropout), '--cpu-steps', str(cpu_steps),
                '--cpu-warmup', '0', '--e2e-steps', '0', '--list-steps', '0', '--f32-steps', '0', '--enc-steps', '0', '--other-steps', '0',
-               '--passes', args.passes, '--child', '1'] + extra_args
+               '--passes', args.passes, '--child', '1', '--full'] + extra_args
         r = subprocess.run(cmd, env=dict(os.environ, **env_extra), capture_output=True, text=True)
         try:
             j = json.loads(r.stdout.strip().splitlines()[-1])
@@ -827,7 +899,8 @@ def main():
                                    'nonempty': int(g0.nnz)}},
         'roofline': roofline, 'roofline_rgcn_gather': gather, 'roofline_gru': gru, 'parity': parity,
         'encoder_only': encoder_only,
-        'kernel_only': {'ms_per_step': ko, 'value': rank_batch / max(ko * 1e-3, 1e-12), 'glue_ms_per_step': glue_ms,
+        'kernel_only': None if args.plain else {
+                        'ms_per_step': ko, 'value': rank_batch / max(ko * 1e-3, 1e-12), 'glue_ms_per_step': glue_ms,
                         'timed_pass_ms_per_step': elapsed_timed * 1e3 / args.steps if elapsed_timed else None,
                         'what': 'sum of the HIP-event durations of EVERY C-ABI launch of a step (named classes + the '
                                 "small kernels as 'glue:*'), from a second pass over the same steps with events on "
@@ -849,11 +922,11 @@ def main():
     }
     out.update(companions)
     if world > 1 and not companions:
-        out['multi_gpu_note'] = 'companion scaling modes skipped (--companions 0)'
+        out['multi_gpu_note'] = 'companion scaling modes skipped (--companions 0, or a run without --full)'
     if args.child:
         print(json.dumps(out))            # a companion's full record, read by the parent process only
     else:
-        print(compact_line(out, write_detail(out)))
+        print(compact_line(out, None if args.plain else write_detail(out)))
     if dist_on:
         dist.destroy_process_group()
 

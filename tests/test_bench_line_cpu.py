@@ -99,3 +99,29 @@ def test_oversized_mandatory_fields_are_shortened_and_a_plain_record_still_gives
     assert line['plan_entries_per_step'] == 61
     for k in CONTRACT:
         assert k in line
+
+
+def test_dump_outputs_writes_the_loss_and_every_parameter_reproducibly(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: loss.npy + one float32 file per parameter; a parameter above DUMP_LIMIT elements as a
+    seeded sample of DUMP_LIMIT of its elements in flat order; the same state gives the same files."""
+    import numpy as np
+    import torch
+    import bench
+    monkeypatch.setattr(bench, 'DUMP_LIMIT', 1000)
+    torch.manual_seed(0)
+    net = torch.nn.Sequential(torch.nn.Linear(40, 50), torch.nn.Linear(50, 3))
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), net, 16.5)
+    names = [n for n, _ in net.named_parameters()]
+    assert sorted(f.name for f in (tmp_path / 'a').iterdir()) == sorted(['loss.npy'] + [n + '.npy' for n in names])
+    assert np.load(str(tmp_path / 'a' / 'loss.npy')).tolist() == [16.5]
+    for n, p in net.named_parameters():
+        a, b = (np.load(str(tmp_path / d / (n + '.npy'))) for d in ('a', 'b'))
+        assert a.dtype == np.float32 and np.array_equal(a, b), n
+        flat = p.detach().reshape(-1).numpy()
+        if flat.size <= 1000:
+            assert np.array_equal(a, flat), n
+        else:
+            pos = {v: i for i, v in enumerate(flat.tolist())}
+            idx = [pos[v] for v in a.tolist()]
+            assert a.size == 1000 and idx == sorted(set(idx)), n
