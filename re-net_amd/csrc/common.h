@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
 #include "../../include/renet_hip.h"
 
 // hipGetLastError() reports the last error of ANY earlier runtime call on this thread -- including calls made
@@ -19,6 +21,31 @@
         hipError_t e__ = hipGetLastError();       \
         if (e__ != hipSuccess) return (int)e__;   \
     } while (0)
+
+// ---- run-time switches ----------------------------------------------------------------------
+// Every switch is an environment variable read ONCE per process: the caller keeps the result in a function-local
+// `static const`.  An unset variable, or a value the reader does not accept, gives the default.
+static inline bool renet_env_flag(const char* name, bool dflt) {          // "0" | "1"
+    const char* e = getenv(name);
+    return (e && e[0] == '0') ? false : (e && e[0] == '1') ? true : dflt;
+}
+static inline int renet_env_int(const char* name, int dflt, int lo, int hi) {
+    const char* e = getenv(name);
+    const int v = e ? atoi(e) : dflt;
+    return (v < lo || v > hi) ? dflt : v;
+}
+static inline bool renet_env_is(const char* name, const char* value) {
+    const char* e = getenv(name);
+    return e && strcmp(e, value) == 0;
+}
+
+// RENET_GEMM_TILE_ORDER = 0 | 1: plain order | XCD-aware virtual tile order (default) of every tiled GEMM (tile_of_block in
+// gemm.hip and gemm_tiles.h).  Returns 0 for the plain order, else the panel width of the XCD-aware order:
+// RENET_GEMM_PANEL_W = 1..64 (default 8; setting it also pins the width, see panel_width() in gemm_tiles.h).
+static inline int renet_gemm_tile_order() {
+    static const int v = renet_env_flag("RENET_GEMM_TILE_ORDER", true) ? renet_env_int("RENET_GEMM_PANEL_W", 8, 1, 64) : 0;
+    return v;
+}
 
 static inline bool renet_dim_ok(int D) { return D == 100 || D == 200 || D == 400; }
 
@@ -76,7 +103,7 @@ __device__ __forceinline__ int renet_xcd_block(int b, int nb) {
     return (nb & 7) == 0 ? (b & 7) * (nb >> 3) + (b >> 3) : b;
 }
 
-// ---- T16: the tiled storage format of bf16 operand PLANES (csrc/gemm_p6.h; tools/p6_layout_sim.py is the executable
+// ---- T16: the tiled storage format of bf16 operand PLANES (csrc/gemm_planes.hip; tools/p6_layout_sim.py is the executable
 // specification).  Element offset of (row, col) inside one plane of a padded matrix with `tc_count` = Cp / 16 tiles per
 // tile row: 16 x 16 tiles of 512 bytes, row i of a tile at i ^ 4 when the tile column is odd, the two 16-byte halves of a
 // tile row swapped when (i >> 3) & 1.  Four consecutive columns starting at a multiple of 4 are consecutive elements.

@@ -646,23 +646,10 @@ int colsum_impl(const T* X, int M, int N, int ldx, float* out, float beta, float
 }
 
 
-int tile_order_f32() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("RENET_GEMM_TILE_ORDER");
-        v = (e && e[0] == '0') ? 0 : 1;
-    }
-    return v;
-}
-
 // RENET_GEMM_F32_GENERIC=1: the round-1 kernel for every shape (A/B runs, tests of the fallback)
 bool generic_forced() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("RENET_GEMM_F32_GENERIC");
-        v = (e && e[0] == '1') ? 1 : 0;
-    }
-    return v != 0;
+    static const bool v = renet_env_flag("RENET_GEMM_F32_GENERIC", false);
+    return v;
 }
 
 }  // namespace
@@ -689,7 +676,7 @@ int renet_gemm_f32(int ta, int tb, int M, int N, int K, float alpha, const float
     g.k_tiles_per_split = (kt_total + split_k - 1) / split_k;
     if (g.k_tiles_per_split < 1) g.k_tiles_per_split = 1;
     g.partial = workspace;
-    g.xcd_order = tile_order_f32();
+    g.xcd_order = renet_gemm_tile_order() != 0;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((N + BN - 1) / BN, (M + BM - 1) / BM, split_k);
     // the buffer-addressed kernel reaches every element (and up to two k-tiles past the end) with a 32-bit byte offset

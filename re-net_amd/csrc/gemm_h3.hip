@@ -1,5 +1,3 @@
-// Fragment of gemm_split.hip's translation unit (included inside its anonymous namespace; uses its tile helpers).
-//
 // fp32-accurate GEMM on the f16 matrix cores of gfx950 ("f16x3 split", renet_gemm_f32_h3):
 //
 //   every fp32 operand value, multiplied by a power-of-two scale s of its TENSOR (so that max |x| s lies in
@@ -23,6 +21,11 @@
 //
 // Structure: the two-phase k-loop of gemm_split_kernel / gemm_split_tall_kernel (128 x 128 x 32 or 256 x 128 x 32
 // tile, split in registers on the way into LDS, the next tile's global loads spread over the MFMAs).
+#include <type_traits>
+#include "gemm_tiles.h"
+#include "gemm_skinny.h"
+
+namespace {
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
@@ -50,9 +53,6 @@ __device__ __forceinline__ float h3_wave_max(const float* __restrict__ part, int
     for (int off = 32; off >= 1; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
     return m;
 }
-
-// (TileLoaderH and fix_item_h -- the raw-buffer loader these kernels were first written for -- now live in gemm_split.hip:
-// the bf16x6 two-phase kernels use them too.)
 
 // registers -> two f16 planes in LDS (same [row][k] image and item order as store_items)
 template <bool CONTIG_K, bool EDGE, int NT, int ROWS, int NI>
@@ -264,3 +264,106 @@ __global__ __launch_bounds__(256) void maxabs_multi_kernel(const MaxabsJob* __re
     __syncthreads();
     if (threadIdx.x == 0) j.part[blockIdx.x] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
 }
+
+// f16x3 kernels: the 256-row tile from RENET_H3_TALL tiles on (default 1000, as for the bf16x6 kernels; 0 disables).
+// Measured on the step's shapes (tools/sessions/r03_s20.sh): the tall tile wins for K-contiguous A from 200 tiles on
+// when the k range is split (dfeat 2048 x 600 x 23033 / 6: 286 -> 259 us) and loses for K-strided A (dW 23033 x 600 x
+// 2048: 293 -> 319 us; the split-K weight gradients 100 -> 178 us).
+bool use_tall_h3(int ta, int M, int nbx, int split_k) {
+    static const int forced = renet_env_int("RENET_H3_TALL", -1, 0, 0x7fffffff);        // -1: not set
+    const long tiles = (long)nbx * ((M + 255) / 256) * split_k;
+    if (forced >= 0) return forced > 0 && tiles >= forced;
+    return !ta && (tiles >= 1000 || (split_k >= 4 && tiles >= 200));
+}
+
+}  // namespace
+
+extern "C" {
+
+#ifdef RENET_GEMM_TRACE
+int renet_gemm_h3_trace_set(unsigned long long* buf) {
+    return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_trace), &buf, sizeof(buf));
+}
+#endif
+
+int renet_maxabs_blocks(int rows, int cols, int ld) {
+    if (rows <= 0 || cols <= 0) return 1;
+    const size_t total = (size_t)rows * cols;
+    if (ld == cols && (total & 3) == 0) return (int)max((size_t)1, min((size_t)256, total / 4096));
+    return min(rows, 256);
+}
+
+int renet_maxabs_partials(const float* x, int rows, int cols, int ld, float* part, void* stream) {
+    if (rows < 0 || cols < 0 || ld < cols || !part) return RENET_ERR_BADARG;
+    if (rows == 0 || cols == 0) {
+        hipError_t e = hipMemsetAsync(part, 0, sizeof(float), (hipStream_t)stream);
+        return e == hipSuccess ? RENET_OK : (int)e;
+    }
+    const int blocks = renet_maxabs_blocks(rows, cols, ld);
+    const bool flat = ld == cols && (((size_t)rows * cols) & 3) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
+    if (flat) RENET_LAUNCH(maxabs_partials_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, rows, cols,
+                           (size_t)ld, part);
+    else RENET_LAUNCH(maxabs_partials_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, rows, cols,
+                      (size_t)ld, part);
+    RENET_LAUNCH_CHECK();
+    return RENET_OK;
+}
+
+int renet_maxabs_partials_multi(const void* jobs, int n_jobs, void* stream) {
+    if (n_jobs < 0 || (n_jobs > 0 && !jobs)) return RENET_ERR_BADARG;
+    if (n_jobs == 0) return RENET_OK;
+    RENET_LAUNCH(maxabs_multi_kernel, dim3(256, n_jobs), dim3(256), 0, (hipStream_t)stream, (const MaxabsJob*)jobs);
+    RENET_LAUNCH_CHECK();
+    return RENET_OK;
+}
+
+int renet_gemm_f32_h3(int ta, int tb, int M, int N, int K, float alpha, const float* A, int lda, const float* B,
+                      int ldb, float beta, float* C, int ldc, const float* bias, int split_k, float* workspace,
+                      size_t workspace_bytes, const float* maxA, int nA, const float* maxB, int nB, void* stream) {
+    if (M < 0 || N < 0 || K < 1 || lda <= 0 || ldb <= 0 || ldc < N) return RENET_ERR_BADARG;
+    if (!maxA || !maxB || nA < 1 || nB < 1 || nA > 1024 || nB > 1024) return RENET_ERR_BADARG;
+    if (M == 0 || N == 0) return RENET_OK;
+    // the f16x3 loaders address with 32-bit byte offsets; operands of 4 GiB and more and the weight-resident shapes run
+    // the bf16x6 kernels (same accuracy class, no bounds needed)
+    const bool small_ok = (size_t)(ta ? K : M) * lda < ((size_t)1 << 30) && (size_t)(tb ? N : K) * ldb < ((size_t)1 << 30);
+    if (!small_ok || ((split_k <= 1) && renet_gemm_skinny_enabled() && renet_gemm_skinny_eligible(ta, M, N, K, A, lda, B, ldb, tb)))
+        return renet_gemm_f32_split(ta, tb, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, bias, split_k, workspace,
+                                    workspace_bytes, stream);
+    if (split_k < 1) split_k = 1;
+    const int kt_total = (K + BK - 1) / BK;
+    if (split_k > kt_total) split_k = max(kt_total, 1);
+    if (split_k > 1 && workspace_bytes < renet_gemm_workspace(M, N, split_k)) return RENET_ERR_WORKSPACE;
+    H3Args h;
+    SplitArgs& g = h.g;
+    g.A = A; g.B = B; g.C = C; g.bias = bias; g.M = M; g.N = N; g.K = K;
+    g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.alpha = alpha; g.beta = beta;
+    g.split_k = split_k;
+    g.k_tiles_per_split = max(1, (kt_total + split_k - 1) / split_k);
+    g.partial = workspace;
+    g.xcd_order = renet_gemm_tile_order();
+    h.maxA = maxA; h.maxB = maxB; h.nA = nA; h.nB = nB;
+    hipStream_t st = (hipStream_t)stream;
+    const int nbx = (N + BN - 1) / BN;
+#define RENET_H3_LAUNCH(TALLV, THR)                                                                    \
+    do {                                                                                               \
+        if (!ta && !tb) RENET_LAUNCH((gemm_h3_kernel<false, false, TALLV>), grid, dim3(THR), 0, st, h); \
+        else if (!ta && tb) RENET_LAUNCH((gemm_h3_kernel<false, true, TALLV>), grid, dim3(THR), 0, st, h); \
+        else if (ta && !tb) RENET_LAUNCH((gemm_h3_kernel<true, false, TALLV>), grid, dim3(THR), 0, st, h); \
+        else RENET_LAUNCH((gemm_h3_kernel<true, true, TALLV>), grid, dim3(THR), 0, st, h);              \
+    } while (0)
+    if (use_tall_h3(ta, M, nbx, split_k)) {
+        dim3 grid(nbx, (M + 255) / 256, split_k);
+        g.xcd_order = panel_width(g.xcd_order, nbx, (int)grid.y, 256, K, split_k, 32);
+        RENET_H3_LAUNCH(true, 512);
+    } else {
+        dim3 grid(nbx, (M + BM - 1) / BM, split_k);
+        g.xcd_order = panel_width(g.xcd_order, nbx, (int)grid.y, BM, K, split_k, 64);
+        RENET_H3_LAUNCH(false, 256);
+    }
+#undef RENET_H3_LAUNCH
+    RENET_LAUNCH_CHECK();
+    if (split_k > 1) return renet_split_reduce(workspace, split_k, M, N, alpha, beta, bias, C, ldc, st);
+    return RENET_OK;
+}
+
+}  // extern "C"

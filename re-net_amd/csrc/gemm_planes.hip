@@ -1,4 +1,4 @@
-// "Planes" GEMM (round 6; included by gemm_split.hip inside its anonymous namespace): the bf16x6 arithmetic of
+// "Planes" GEMM (round 6; renet_gemm_planes, renet_pack_planes): the bf16x6 arithmetic of
 // gemm_split_kernel -- every fp32 operand value as three bf16 terms, the six leading term products on
 // v_mfma_f32_32x32x16_bf16, fp32 accumulation -- on operands that ARRIVE split: three bf16 planes per matrix in HBM,
 // written by the kernel that produces the tensor (softmax-CE: the CE gradient) or by renet_pack_planes (a weight: once per
@@ -28,6 +28,11 @@
 // Epilogue extras: `alpha_dev` (a device scalar folded into alpha: the upstream autograd gradient, no pass over the CE
 // gradient), and `col_out`: the LAST logical column of the product goes to a vector instead of C -- with a ones column
 // appended to B this is the bias gradient (column sums of A^T) for free, inside the padding of the last column tile.
+
+#include <type_traits>
+#include "gemm_tiles.h"
+
+namespace {
 
 struct P6Args {
     const __bf16* A;
@@ -61,7 +66,7 @@ struct P6Cfg {
 };
 
 // Work item L (the order in which a plain grid would have dispatched its workgroups: x fastest, then y, then z) -> tile.
-// The arithmetic of tile_of_block (gemm_split.hip) with the grid passed explicitly: the persistent kernel below walks
+// The arithmetic of tile_of_block (gemm_tiles.h) with the grid passed explicitly: the persistent kernel below walks
 // L = blockIdx.x, blockIdx.x + gridDim.x, ... (gridDim.x a multiple of 8 whenever it is smaller than the item count, so a
 // workgroup stays on "its" XCD's eighth of the virtual tile sequence).
 __device__ __forceinline__ void p6_tile_of_index(int L, int nbx, int nby, int nbz, int xcd_order, int& bx, int& by, int& bz) {
@@ -246,7 +251,7 @@ __global__ __launch_bounds__(P6Cfg<WM>::THREADS, 2) void gemm_p6_kernel(P6Args p
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-    // the six term pairs, smallest first (the order of mfma_tile: both kernels sum a k-slab's products alike); group q =
+    // the six term pairs, smallest first (the order of mfma_tile in gemm_split.hip: both kernels sum a k-slab's products alike); group q =
     // the four MFMAs of one term pair
     auto mfma_group = [&](const P6Frags& F, auto qc) {
         constexpr int q = decltype(qc)::value;
@@ -423,3 +428,92 @@ int launch_p6(const P6Args& pa, dim3 grid, hipStream_t st) {
     RENET_LAUNCH_CHECK();
     return RENET_OK;
 }
+
+}  // namespace
+
+extern "C" {
+
+size_t renet_planes_elems(int R, int C) {
+    const size_t rp = ((size_t)R + 255) & ~(size_t)255, cp = ((size_t)C + 255) & ~(size_t)255;
+    return rp * cp;
+}
+
+int renet_pack_planes(const float* X, int R, int C, int ldx, int ones_col, void* out, void* stream) {
+    if (R < 0 || C < 0 || ldx < C || !out) return RENET_ERR_BADARG;
+    const int cols = ones_col ? C + 1 : C;
+    const int Rp = (R + 255) & ~255, Cp = (cols + 255) & ~255;
+    if (Rp == 0 || Cp == 0) return RENET_OK;
+    const size_t blocks = (size_t)(Rp >> 4) * (size_t)(Cp >> 6);       // one workgroup per tile row x 4 tiles
+    if (blocks > 0x7fffffffu) return RENET_ERR_UNSUPPORTED;
+    RENET_LAUNCH(pack_planes_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, X, R, C, ldx, Rp, Cp,
+                 ones_col ? C : -1, (__bf16*)out, (size_t)Rp * Cp);
+    RENET_LAUNCH_CHECK();
+    return RENET_OK;
+}
+
+int renet_gemm_planes(int a_tr, int b_tr, int M, int N, int K, float alpha, const float* alpha_dev, const void* Ap,
+                      int lda, size_t a_plane, const void* Bp, int ldb, size_t b_plane, float beta, float* C, int ldc,
+                      const float* bias, float* col_out, int split_k, float* workspace, size_t workspace_bytes,
+                      void* stream) {
+    // N counts the logical columns of the product INCLUDING the col_out one
+    const int n_main = col_out ? N - 1 : N;
+    if (M < 0 || N < 0 || n_main < 0 || K < 1 || ldc < n_main || !Ap || !Bp) return RENET_ERR_BADARG;
+    if (M == 0 || N == 0) return RENET_OK;
+    // lda / ldb: Cp (columns of the padded stored matrix, a multiple of 16: T16 tiles)
+    const int Mp = (M + 255) & ~255, Np = (N + 127) & ~127, Kp = (K + 15) & ~15;
+    if (lda < (a_tr ? Mp : Kp) || ldb < (b_tr ? Np : Kp) || (lda & 15) || (ldb & 15)) return RENET_ERR_BADARG;
+    // the plane strides must cover the stored (padded) matrix
+    if (a_plane < (size_t)(a_tr ? Kp : Mp) * lda || b_plane < (size_t)(b_tr ? Kp : Np) * ldb) return RENET_ERR_BADARG;
+    if (split_k < 1) split_k = 1;
+    const int st_total = (K + 15) / 16;                       // half-stages of 16 k
+    if (split_k > st_total) split_k = max(st_total, 1);
+    if (split_k > 1 && workspace_bytes < renet_gemm_workspace(M, N, split_k)) return RENET_ERR_WORKSPACE;
+    P6Args pa;
+    pa.A = (const __bf16*)Ap; pa.B = (const __bf16*)Bp;
+    pa.a_plane = a_plane; pa.b_plane = b_plane;
+    pa.tca = lda >> 4; pa.tcb = ldb >> 4;
+    pa.alpha_dev = alpha_dev; pa.col_out = col_out;
+    SplitArgs& g = pa.out;
+    g.A = nullptr; g.B = nullptr; g.C = C; g.bias = bias; g.M = M; g.N = N; g.K = K;
+    g.lda = 0; g.ldb = 0; g.ldc = ldc; g.alpha = alpha; g.beta = beta;
+    g.split_k = split_k;
+    g.k_tiles_per_split = (max(1, (st_total + split_k - 1) / split_k) + 1) & ~1;     // even: see gemm_p6_kernel
+    g.partial = workspace;
+    hipStream_t st = (hipStream_t)stream;
+    // tile height: 128 rows (two workgroups per CU) unless RENET_P6_TILE=256 (one 8-wave workgroup per CU)
+    static const int tile_h = renet_env_int("RENET_P6_TILE", 128, 256, 256);         // any other value: 128
+    const int nbx = (N + BN - 1) / BN, nby = (M + tile_h - 1) / tile_h;
+    g.xcd_order = panel_width(renet_gemm_tile_order(), nbx, nby, tile_h, K, split_k, tile_h == 256 ? 32 : 64);
+    // persistent grid: at most `slots` workgroups (two per CU for the 128-row tile, one for the 256-row tile), a multiple of 8
+    // when the items outnumber it (a workgroup then stays on one XCD's share of the tile sequence); RENET_P6_PERSISTENT=1
+    // selects it (default: one workgroup per item)
+    pa.nbx = nbx; pa.nby = nby; pa.nbz = split_k;
+    // measured: no gain (profiles/r06_a_planes_ablation.md, v6): off by default
+    static const bool persistent = renet_env_flag("RENET_P6_PERSISTENT", false);
+    const long items = (long)nbx * nby * split_k;
+    const long slots = tile_h == 256 ? 256 : 512;
+    if (items > 0x7fffffffL) return RENET_ERR_UNSUPPORTED;
+    dim3 grid((unsigned)((persistent && items > slots) ? slots : items), 1, 1);
+    int e;
+#define RENET_P6_LAUNCH(WMV)                                                   \
+    do {                                                                       \
+        if (!a_tr && !b_tr) e = launch_p6<false, false, WMV>(pa, grid, st);    \
+        else if (!a_tr && b_tr) e = launch_p6<false, true, WMV>(pa, grid, st); \
+        else if (a_tr && !b_tr) e = launch_p6<true, false, WMV>(pa, grid, st); \
+        else e = launch_p6<true, true, WMV>(pa, grid, st);                     \
+    } while (0)
+    if (tile_h == 256) RENET_P6_LAUNCH(4);
+    else RENET_P6_LAUNCH(2);
+#undef RENET_P6_LAUNCH
+    if (e != RENET_OK) return e;
+    if (split_k > 1) {
+        const size_t total = (size_t)M * N;
+        const int blocks = (int)min((size_t)2048, (total + 255) / 256);
+        RENET_LAUNCH(p6_reduce_kernel, dim3(blocks), dim3(256), 0, st, workspace, split_k, M, N, alpha, alpha_dev, beta,
+                     bias, C, ldc, col_out);
+        RENET_LAUNCH_CHECK();
+    }
+    return RENET_OK;
+}
+
+}  // extern "C"

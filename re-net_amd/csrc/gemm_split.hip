@@ -21,99 +21,13 @@
 // load, see gemm.hip).
 #include <cstdlib>
 #include <type_traits>
-#include "common.h"
+#include "gemm_tiles.h"
 #include "gemm_skinny.h"
 
 namespace {
 
-constexpr int BM = 128, BN = 128, BK = 32;
-constexpr int LDS_ROW = 40;                     // bf16 per LDS row (80 B)
 constexpr int PLANE = BM * LDS_ROW;             // bf16 per plane
 constexpr int THREADS = 256;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
-struct SplitArgs {
-    const float* A;
-    const float* B;
-    float* C;
-    const float* bias;
-    int M, N, K, lda, ldb, ldc;
-    float alpha, beta;
-    int k_tiles_per_split;
-    int split_k;
-    float* partial;
-    int xcd_order;          // 0: plain order; w >= 1: XCD-aware virtual tile order with panels of <= w tiles (tile_of_block)
-};
-
-
-// Optional phase tracing (tools/gemm_trace.py builds a separate library with -DRENET_GEMM_TRACE; the shipped
-// library contains none of this): s_memtime stamps per wave and k-step for the first TRACE_BLOCKS workgroups.
-#ifdef RENET_GEMM_TRACE
-constexpr int TRACE_BLOCKS = 64, TRACE_STEPS = 320;
-__device__ unsigned long long* g_trace = nullptr;          // [TRACE_BLOCKS][8 waves][TRACE_STEPS][4]
-__device__ __forceinline__ void trace_put(int wave8, int step, int slot, unsigned long long v) {
-    const int flat = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-    // workgroups 0-31 and 256-287: the second set usually lands on the same CUs as the first
-    if (g_trace && flat < 512 && (flat & 255) < 32 && step < TRACE_STEPS && (threadIdx.x & 63) == 0)
-        g_trace[(((size_t)((flat >> 8) * 32 + (flat & 255)) * 8 + wave8) * TRACE_STEPS + step) * 4 + slot] = v;
-}
-#define TRACE_T(wave8, step, slot) trace_put(wave8, step, slot, __builtin_amdgcn_s_memtime())
-#define TRACE_V(wave8, step, slot, v) trace_put(wave8, step, slot, (unsigned long long)(v))
-#else
-#define TRACE_T(wave8, step, slot)
-#define TRACE_V(wave8, step, slot, v)
-#endif
-
-// Tile of this workgroup.  The dispatcher deals workgroups to the 8 XCDs round-robin (block b -> XCD b % 8, each
-// XCD with its own 4 MB L2), so the plain (blockIdx.x, blockIdx.y) order makes every XCD sweep the WHOLE of the
-// long operand once per tile row of the short one (PMC: 215 MB of fabric traffic per GEMM launch of the step
-// against ~60 MB of operands + output; 127 MB with this order).  Virtual order instead: XCD x owns one contiguous
-// 1/8 of the tile sequence, and in that sequence the SHORT grid dimension runs fastest, so the tiles that share
-// a slab of the long operand are consecutive on one XCD and the slab is fetched once.  RENET_GEMM_TILE_ORDER=0
-// in the environment restores the plain order (tools/gemm_bench.py).
-__device__ __forceinline__ void tile_of_block(int nbx, int nby, int xcd_order, int& bx, int& by, int& bz) {
-    bz = blockIdx.z;
-    if (!xcd_order) { bx = blockIdx.x; by = blockIdx.y; return; }
-    const int nb = nbx * nby;
-    int t;                                                   // position in the tile sequence of one k-slice
-    if (gridDim.z == 1) {
-        const int per = nb >> 3;
-        const int L = blockIdx.x + nbx * blockIdx.y;
-        t = L < 8 * per ? (L & 7) * per + (L >> 3) : L;
-    } else {
-        // split-K grids (round 4): the dispatcher deals the FLATTENED index (x fastest, then y, then z) to the XCDs, so the
-        // 2-D rule above spreads every k-slice over all eight L2s whenever nbx * nby is not a multiple of 8 -- and even
-        // when it is, each slice's operand slabs are fetched by all XCDs (PMC, tools/pmc_by_shape.py: 600 x 800 x 16000 / 14
-        // read 421 MB for 90 MB of operands, dfeat 2048 x 600 x 23033 / 6 689 MB for 244).  Here XCD x owns one contiguous
-        // eighth of the (k-slice, tile) sequence: whole k-slices, read by one L2 (two where a slice straddles).
-        const int total = nb * (int)gridDim.z, per3 = total >> 3;
-        const int L3 = blockIdx.x + nbx * (blockIdx.y + nby * blockIdx.z);
-        const int v = L3 < 8 * per3 ? (L3 & 7) * per3 + (L3 >> 3) : L3;
-        bz = v / nb;
-        t = v - bz * nb;
-    }
-    // sequence: panels of <= 8 tiles across the SHORT dimension, the long dimension sweeping each panel
-    // (a square problem becomes 8 x 8 blocks of concurrently resident tiles per XCD instead of 2 x 32)
-    const int ns = min(nbx, nby), nl = max(nbx, nby);
-    const int w = min(ns, xcd_order);
-    const int p = t / (w * nl), r = t - p * (w * nl);
-    const int wp = min(w, ns - p * w);                       // width of this (possibly last, narrower) panel
-    const int l = r / wp, sh = p * w + (r - l * wp);
-    if (nby <= nbx) { bx = l; by = sh; }
-    else { by = l; bx = sh; }
-}
-
-// item i of this thread (f = tid + threads * i) of a ROWS x 32 operand tile:
-//   CONTIG_K: row = f>>3, k = 4*(f&7);  else: row = f % ROWS, k = 4*(f / ROWS)
-template <bool CONTIG_K, int ROWS = 128>
-__device__ __forceinline__ void item_pos(int f, int& row, int& k) {
-    if constexpr (CONTIG_K) { row = f >> 3; k = (f & 7) << 2; }
-    else { row = f & (ROWS - 1); k = (f / ROWS) << 2; }
-}
 
 // Per-thread load state: the row part of every item's address is computed ONCE (the per-tile work is an
 // add); integer multiplies inside the k loop cost more issue slots than the MFMAs they feed.
@@ -167,13 +81,6 @@ struct ItemLoader {
     }
 };
 
-__device__ __forceinline__ uint2 pack4(bf16x2 lo, bf16x2 hi) {
-    uint2 u;
-    u.x = __builtin_bit_cast(unsigned, lo);
-    u.y = __builtin_bit_cast(unsigned, hi);
-    return u;
-}
-
 // Out-of-range fix-up of one clamped item (see ItemLoader::load_item): (row, k) are the item's coordinates
 // inside the tile.
 template <bool CONTIG_K>
@@ -186,71 +93,6 @@ __device__ __forceinline__ float4 fix_item(float4 v, int rows, int K, int row0, 
                                                                  : make_float4(v.w, 0.f, 0.f, 0.f);
         }
     }
-    const bool rok = row0 + row < rows;
-    if (!rok || kg >= K) v.x = 0.f;
-    if (!rok || kg + 1 >= K) v.y = 0.f;
-    if (!rok || kg + 2 >= K) v.z = 0.f;
-    if (!rok || kg + 3 >= K) v.w = 0.f;
-    return v;
-}
-
-// Raw-buffer loader (f16x3 kernels since round 3, bf16x6 two-phase kernels since round 4): raw buffer loads -- a descriptor of the operand (SGPRs) plus a per-lane 32-bit byte
-// offset computed once and advanced by the tile's uniform k offset (one v_add per load): no 64-bit address arithmetic and
-// NO BRANCH inside the MFMA phase.  (tools/gemm_trace.py: with the generic ItemLoader -- clamped addresses, a
-// uniform branch per item -- every load piece cost the issuing wave ~180 cycles between two MFMAs, 2.4x the
-// matrix-pipe time of the 24-MFMA phase.)  Nothing is clamped along k: the descriptor's num_records is the operand's
-// exact extent, every dword beyond it reads as 0 without touching memory (raw buffers are range-checked per dword:
-// tests/test_gpu_parity.py runs K % 4 != 0 with odd row strides, where the last row's last 16-byte load straddles the
-// end), reads beyond K inside it (the next row) are zeroed by store_items_h's EDGE path like the clamped rows.
-// Requires rows * ld * 4 < 2^32 (checked on the host; larger operands run the bf16x6 kernels).
-typedef uint32_t h3_u32x4 __attribute__((ext_vector_type(4)));
-
-template <bool CONTIG_K, int NT, int ROWS, int NI>
-struct TileLoaderH {
-    __amdgpu_buffer_rsrc_t rs;
-    uint32_t off[NI];          // bytes: CONTIG_K: (row * ld + kk) * 4      else: (row + kk * ld) * 4
-    uint32_t ldb;              // row stride in bytes
-
-    __device__ __forceinline__ void init(const float* P, int ld, int rows, int K, int row0, int tid) {
-        const uint32_t extent = CONTIG_K ? (uint32_t)(rows - 1) * (uint32_t)ld + (uint32_t)K
-                                         : (uint32_t)(K - 1) * (uint32_t)ld + (uint32_t)rows;
-        rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(P), (short)0, (int)(extent * 4u),
-                                               0x00020000);
-        ldb = (uint32_t)ld * 4u;
-#pragma unroll
-        for (int i = 0; i < NI; ++i) {
-            int row, k;
-            item_pos<CONTIG_K, ROWS>(tid + NT * i, row, k);
-            row = min(row0 + row, rows - 1);
-            off[i] = (CONTIG_K ? (uint32_t)row * (uint32_t)ld + (uint32_t)k : (uint32_t)row + (uint32_t)k * (uint32_t)ld) * 4u;
-        }
-    }
-
-    __device__ __forceinline__ void load_item(int i, int k0, float4& r) const {
-#ifdef RENET_PROBE_NOLOAD           // probe builds only (tools/gemm_split_probe.py): the k-loop without its global loads
-        if (k0 > 0) return;
-#endif
-        if constexpr (CONTIG_K) {
-            const h3_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(off[i] + (uint32_t)k0 * 4u), 0, 0);
-            r = make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-        } else {
-            const uint32_t b0 = off[i] + (uint32_t)k0 * ldb;
-            r.x = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, (int)b0, 0, 0));
-            r.y = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, (int)(b0 + ldb), 0, 0));
-            r.z = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, (int)(b0 + 2u * ldb), 0, 0));
-            r.w = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, (int)(b0 + 3u * ldb), 0, 0));
-        }
-    }
-
-    __device__ __forceinline__ void load(int k0, float4 (&r)[NI]) const {
-#pragma unroll
-        for (int i = 0; i < NI; ++i) load_item(i, k0, r[i]);
-    }
-};
-
-// out-of-range fix-up of one UNCLAMPED item: rows past the operand and k past K become zeros
-__device__ __forceinline__ float4 fix_item_h(float4 v, int rows, int K, int row0, int k0, int row, int k) {
-    const int kg = k0 + k;
     const bool rok = row0 + row < rows;
     if (!rok || kg >= K) v.x = 0.f;
     if (!rok || kg + 1 >= K) v.y = 0.f;
@@ -327,14 +169,6 @@ __device__ __forceinline__ void mfma_tile(const __bf16* __restrict__ sA, const _
     }
 }
 
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
-
 // The MFMA phase of the two-phase kernels with the NEXT tile's global loads spread over it: issued in one
 // burst right after the barrier (8 x 1 KB per wave, every wave of the CU at once) they fill the vector-memory
 // queue -- the texture-address unit takes 64 B/clk, 16 cycles per dwordx4 wave-instruction -- and the waves
@@ -367,51 +201,6 @@ __device__ __forceinline__ void mfma_tile_ld(const __bf16* __restrict__ sA, cons
         if constexpr (g % 5 == 2 && g / 5 < NPIECES) load_piece(std::integral_constant<int, g / 5>{});
         __builtin_amdgcn_sched_barrier(0);
     });
-}
-
-// accumulators -> C (or the split-K partial plane).  C/D layout of the 32x32 MFMA: col = lane & 31,
-// row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
-__device__ __forceinline__ void store_tile(const SplitArgs& g, int m0, int n0, int z, int wm, int wn, int lane,
-                                           const f32x16 (&acc)[2][2]) {
-#ifdef RENET_PROBE_NOSTORE          // probe builds only (tools/gemm_split_probe.py): what the C-store epilogue costs
-    if (acc[0][0][0] != 12345.678f) return;
-#endif
-    const bool split = g.split_k > 1;
-    float* Cout = split ? g.partial + (size_t)z * g.M * g.N : g.C;
-    const int ldo = split ? g.N : g.ldc;
-    const int half = lane >> 5;
-    const bool accumulate = !split && g.beta != 0.f;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int col = n0 + wn * 64 + j * 32 + (lane & 31);
-            if (col >= g.N) continue;
-            const float bv = (!split && g.bias) ? g.bias[col] : 0.f;
-            const int row_base = m0 + wm * 64 + i * 32 + 4 * half;
-            // beta != 0 (in-place gradient accumulation): ALL 16 reads of C first, then the 16 stores.  Written as
-            // load / fma / store per element the compiler must assume that a store aliases the next load and chains
-            // 64 memory round trips per lane at the end of every tile.
-            float old[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) old[r] = 0.f;
-            if (accumulate) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = min(row_base + (r & 3) + 8 * (r >> 2), g.M - 1);
-                    old[r] = Cout[(size_t)row * ldo + col];
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = row_base + (r & 3) + 8 * (r >> 2);
-                if (row < g.M) {
-                    float* p = Cout + (size_t)row * ldo + col;
-                    if (split) *p = acc[i][j][r];
-                    else *p = g.alpha * acc[i][j][r] + bv + (accumulate ? g.beta * old[r] : 0.f);
-                }
-            }
-        }
 }
 
 // RAW: operands addressed through raw buffer descriptors (TileLoaderH; both operands below 2^30 elements of reach, checked
@@ -909,287 +698,6 @@ __global__ __launch_bounds__(THREADS) void gemm_bf16_kernel(SplitArgs g) {
     store_tile(g, m0, n0, z, wm, wn, lane, acc);
 }
 
-// ------------------------------------------------------------------------------------------------------
-// LDS-DMA ring shared by the bf16-storage GEMM below (the three-plane "planes" GEMM that introduced it in round 2 was
-// measured against the in-loop split, not adopted -- DESIGN 4b -- and removed in round 5): operands are bf16 matrices
-// [rows][cols] in HBM, both dims padded with zeros to multiples of 128 (no edge handling in the loop); a k-tile is
-// global_load_lds_dwordx4 pieces (no VGPRs, no VALU, no ds_write) into a 3-deep LDS ring with ONE raw s_barrier per
-// k-tile.  An operand is consumed in one of two roles:
-//   K-CONTIGUOUS (tr = 0): rows = the operand's M (N) index, cols = K.  Tile image in LDS: [128 rows][32 k], 64-byte
-//       rows, the four 16-byte chunks of a row XOR-swizzled by (row >> 2) & 3 -- applied on the SOURCE address of
-//       the DMA (the LDS side of global_load_lds is lane-linear) -- which makes every ds_read_b128 fragment read
-//       conflict free.
-//   K-STRIDED (tr = 1): rows = K, cols = the operand's M (N) index (the tensor as stored when the contraction runs
-//       over its rows: dW = dlogits^T feat, dfeat = dlogits W).  Tile image [32 k][128 cols], 256-byte rows, the
-//       sixteen 16-byte chunks XOR-swizzled by 4 * (k & 3); fragments come from two ds_read_b64_tr_b16 each (gfx950's
-//       transposing LDS read: in a 16-lane group, lane i receives element i & 3 of the 8-byte chunks addressed by
-//       lanes (i >> 2) + 4 j, j = 0..3 -- measured with tools/probes/tr_probe.hip).
-// ------------------------------------------------------------------------------------------------------
-
-constexpr int P3_SLOTS = 3;
-constexpr int P3_LOADERS = 4;                           // loader waves per workgroup (48 DMA pieces per k-tile)
-constexpr int P3_THREADS = 64 * (4 + P3_LOADERS);
-
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-
-// Fragment of MFMA tile t of a wave whose 64 rows (K-contiguous image) / 64 columns (K-strided image) start at `w0`
-// inside the operand's 128-wide tile; `tile` = start of the plane's 8 KB image.
-template <bool TR>
-__device__ __forceinline__ bf16x8 p3_fragment(const char* tile, int lane, int w0, int t, int slab) {
-    if constexpr (!TR) {
-        const int row = w0 + 32 * t + (lane & 31);
-        const int chunk = (2 * slab + (lane >> 5)) ^ ((row >> 2) & 3);
-        return *reinterpret_cast<const bf16x8*>(tile + row * 64 + chunk * 16);
-    } else {
-        const int s = lane & 15;
-        const int col = w0 + 32 * t + 16 * ((lane >> 4) & 1) + 4 * (s & 3);  // first of the 4 columns of the chunk
-        bf16x8 r;
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const int kk = slab * 16 + 8 * (lane >> 5) + 4 * q + (s >> 2);
-            const int phys16 = (col >> 3) ^ (4 * (kk & 3));
-            const char* p = tile + kk * 256 + phys16 * 16 + ((col >> 2) & 1) * 8;
-            const s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) r[4 * q + j] = __builtin_bit_cast(__bf16, (short)v[j]);
-        }
-        return r;
-    }
-}
-
-// Wave specialisation: a workgroup is 8 waves -- waves 0..3 (one per SIMD) only read fragments and issue MFMAs, waves
-// 4..7 (their SIMD partners) only issue the LDS-DMA.  A global_load_lds costs the issuing wave ~60-100 cycles of issue
-// time (12 per k-tile and wave: as much as half the tile's MFMA time when the MFMA wave has to issue them itself,
-// measured: 3200 cycles per k-tile against 1536 of matrix-pipe time); from a partner wave it overlaps the MFMAs.
-//   ring of 3 slots, ONE s_barrier per round, all 8 waves:
-//     loader, round k : issue tile k + 2 into slot (k + 2) % 3   [held tile k - 1: every MFMA wave finished reading it
-//                                                                 before barrier k - 1]
-//                       s_waitcnt vmcnt(12)                       [tile k + 1 landed; tile k + 2 stays in flight]
-//                       barrier k
-//     MFMA wave, round k : fragments of tile k (slot k % 3), 48 MFMAs with the slab-1 reads behind the first 12,
-//                          s_waitcnt lgkmcnt(0), barrier k
-// ------------------------------------------------------------------------------------------------------
-// bf16-STORAGE GEMM (renet_gemm_bf16s, BASELINE config 5 "n_hidden=400 bf16"): both operands are bf16 matrices in
-// HBM ([Rp][Cp], padded with zeros to multiples of 128), ONE product per fragment
-// pair, fp32 accumulation.  The LDS-DMA ring, wave specialisation, images and swizzles described above; a
-// ring slot holds TWO 32-wide k sub-tiles per operand (4 x 8 KB = 32 KB per slot, 3 slots), so a stage is 128 x 128 x 64: 16 MFMAs per MFMA wave and barrier.  With one product per
-// element pair the k-loop moves 16 KB of operands per 1 MFLOP: the kernel is bound by the L2 -> LDS stream, not by
-// the matrix pipe.  Either operand may be consumed K-contiguous or K-strided (ds_read_b64_tr_b16).
-// ------------------------------------------------------------------------------------------------------
-struct Bf16sArgs {
-    const __bf16* A;
-    const __bf16* B;
-    int lda, ldb;               // row stride (elements)
-    SplitArgs out;              // M, N, K, C, ldc, alpha, beta, bias, split-K fields; k_tiles_per_split in 64-wide STAGES
-};
-
-constexpr int B1_SUB = 2;                                 // k sub-tiles per operand and ring slot
-constexpr int B1_BK = 32 * B1_SUB;                        // k per stage
-constexpr int B1_STAGE = 2 * B1_SUB * 8192;
-constexpr int B1_SLOTS = 3;
-constexpr size_t B1_LDS = (size_t)B1_STAGE * B1_SLOTS;
-constexpr size_t B1_LDS_TALL = (size_t)B1_SUB * (256 * 64 + 8192) * B1_SLOTS;
-
-// TALL: 256 x 128 tile, 8 MFMA waves (4 x 2, two per SIMD: one wave's barrier wait is covered by its partner's
-// MFMAs) + 4 loader waves; A images are 16 KB (256 rows K-contiguous / 256 columns K-strided).  0.75x the operand
-// bytes per flop of the 128 x 128 tile.
-template <bool A_TR, bool B_TR, bool TALL>
-__global__ __launch_bounds__(TALL ? 768 : P3_THREADS) void gemm_bf16s_kernel(Bf16sArgs pa) {
-    constexpr int TBM = TALL ? 256 : 128;
-    constexpr int MW = TALL ? 8 : 4;                       // MFMA waves
-    constexpr int AIMG = TBM * 64;                         // bytes of one A sub-tile image
-    constexpr int APIECES = TBM / 16;                      // 1 KB DMA pieces per A image
-    constexpr int STAGE = B1_SUB * (AIMG + 8192);
-    constexpr int NPIECE = B1_SUB * (APIECES + 8);
-    constexpr int PER = NPIECE / P3_LOADERS;               // 8 (128-row tile) or 12 (256-row tile)
-    extern __shared__ __attribute__((aligned(16))) char ring1[];
-    const SplitArgs& g = pa.out;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int bx, by, z;
-    tile_of_block(gridDim.x, gridDim.y, g.xcd_order, bx, by, z);
-    const int m0 = by * TBM, n0 = bx * BN;
-    const int st_total = (g.K + B1_BK - 1) / B1_BK;
-    const int s0 = z * g.k_tiles_per_split;
-    const int s1 = min(st_total, s0 + g.k_tiles_per_split);
-    const int nk = max(s1 - s0, 0);
-
-    if (wave >= MW) {
-        if (nk == 0) return;
-        const int lw = wave - MW;
-        const __bf16* src[PER];
-        int dst[PER];
-        bool is_b[PER];
-#pragma unroll
-        for (int i = 0; i < PER; ++i) {
-            const int id = lw + P3_LOADERS * i;
-            // pieces 0 .. B1_SUB * APIECES - 1: A (sub-tile major), then B
-            const int opnd = id >= B1_SUB * APIECES ? 1 : 0;
-            const int idl = opnd ? id - B1_SUB * APIECES : id;
-            const int per_sub = opnd ? 8 : APIECES;
-            const int sub = idl / per_sub, piece = idl % per_sub;
-            is_b[i] = opnd != 0;
-            const bool tr = opnd ? B_TR : A_TR;
-            const __bf16* base = opnd ? pa.B : pa.A;
-            const int ld = opnd ? pa.ldb : pa.lda;
-            const int r0 = opnd ? n0 : m0;
-            const size_t k0 = (size_t)s0 * B1_BK + sub * 32;
-            size_t off;
-            int img_off;
-            if (!tr) {                                   // [rows][32 k]: piece = 16 rows x 64 B
-                const int row = 16 * piece + (lane >> 2);
-                const int chunk = (lane & 3) ^ ((row >> 2) & 3);
-                off = (size_t)(r0 + row) * ld + k0 + chunk * 8;
-                img_off = piece * 1024;
-            } else {                                     // [32 k][cols]: 128-column panels of 8 KB, piece = 4 k x 256 B
-                const int panel = piece >> 3, pc = piece & 7;
-                const int kk = 4 * pc + (lane >> 4);
-                const int log16 = (lane & 15) ^ (4 * (kk & 3));
-                off = (k0 + kk) * ld + r0 + panel * 128 + log16 * 8;
-                img_off = panel * 8192 + pc * 1024;
-            }
-            src[i] = base + off;
-            dst[i] = (opnd ? B1_SUB * AIMG + sub * 8192 : sub * AIMG) + img_off;
-        }
-        const size_t a_step = A_TR ? (size_t)B1_BK * pa.lda : (size_t)B1_BK;
-        const size_t b_step = B_TR ? (size_t)B1_BK * pa.ldb : (size_t)B1_BK;
-        auto issue_all = [&](int slot) {
-            char* base = ring1 + slot * STAGE;
-#pragma unroll
-            for (int i = 0; i < PER; ++i) {
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src[i],
-                                                 (__attribute__((address_space(3))) void*)(base + dst[i]), 16, 0, 0);
-                src[i] += is_b[i] ? b_step : a_step;
-            }
-        };
-        static_assert(PER == 8 || PER == 12, "counted waits below");
-        auto wait_one_stage = [&]() {
-            if constexpr (PER == 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        };
-        issue_all(0);
-        if (nk > 1) {
-            issue_all(1);
-            wait_one_stage();
-        } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        __builtin_amdgcn_s_barrier();                                     // barrier -1: stage 0 visible
-        for (int kt = 0; kt < nk; ++kt) {
-            if (kt + 2 < nk) {
-                issue_all((kt + 2) % B1_SLOTS);
-                wait_one_stage();
-            } else {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
-            __builtin_amdgcn_s_barrier();                                 // barrier kt: stage kt + 1 visible
-        }
-        return;
-    }
-
-    // ---------------- MFMA waves ----------------
-    const int wm = wave >> 1, wn = wave & 1;               // wm: 0..1 (128-row tile) or 0..3 (256-row tile)
-    int offA[2][2], offB[2][2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            if constexpr (!A_TR) {
-                const int row = wm * 64 + 32 * t + (lane & 31);
-                offA[t][u] = row * 64 + (((2 * u + (lane >> 5)) ^ ((row >> 2) & 3)) * 16);
-            } else {
-                const int sl = lane & 15;
-                const int colf = wm * 64 + 32 * t + 16 * ((lane >> 4) & 1) + 4 * (sl & 3);
-                const int col = colf & 127;                  // inside its 128-column panel
-                const int kk = 8 * (lane >> 5) + 4 * u + (sl >> 2);
-                offA[t][u] = (colf >> 7) * 8192 + kk * 256 + (((col >> 3) ^ (4 * (kk & 3))) * 16) + ((col >> 2) & 1) * 8;
-            }
-            if constexpr (!B_TR) {
-                const int row = wn * 64 + 32 * t + (lane & 31);
-                offB[t][u] = row * 64 + (((2 * u + (lane >> 5)) ^ ((row >> 2) & 3)) * 16);
-            } else {
-                const int sl = lane & 15;
-                const int col = wn * 64 + 32 * t + 16 * ((lane >> 4) & 1) + 4 * (sl & 3);
-                const int kk = 8 * (lane >> 5) + 4 * u + (sl >> 2);
-                offB[t][u] = kk * 256 + (((col >> 3) ^ (4 * (kk & 3))) * 16) + ((col >> 2) & 1) * 8;
-            }
-        }
-    auto frag_tr = [&](const char* img, const int (&off)[2], int slab) {
-        bf16x8 r;
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                (__attribute__((address_space(3))) s16x4*)(img + off[q] + slab * 4096));
-#pragma unroll
-            for (int j = 0; j < 4; ++j) r[4 * q + j] = __builtin_bit_cast(__bf16, (short)v[j]);
-        }
-        return r;
-    };
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    if (nk > 0) __builtin_amdgcn_s_barrier();                             // barrier -1
-    for (int kt = 0; kt < nk; ++kt) {
-        const char* st = ring1 + (kt % B1_SLOTS) * STAGE;
-        bf16x8 fa[B1_SUB][2][2], fb[B1_SUB][2][2];                        // [sub][slab][t]: all 16 reads issued up front
-#pragma unroll
-        for (int sb = 0; sb < B1_SUB; ++sb)
-#pragma unroll
-            for (int slab = 0; slab < 2; ++slab)
-#pragma unroll
-                for (int t = 0; t < 2; ++t) {
-                    const char* ia = st + sb * AIMG;
-                    const char* ib = st + B1_SUB * AIMG + sb * 8192;
-                    if constexpr (!A_TR) fa[sb][slab][t] = *reinterpret_cast<const bf16x8*>(ia + offA[t][slab]);
-                    else fa[sb][slab][t] = frag_tr(ia, offA[t], slab);
-                    if constexpr (!B_TR) fb[sb][slab][t] = *reinterpret_cast<const bf16x8*>(ib + offB[t][slab]);
-                    else fb[sb][slab][t] = frag_tr(ib, offB[t], slab);
-                }
-#pragma unroll
-        for (int sb = 0; sb < B1_SUB; ++sb)
-#pragma unroll
-            for (int slab = 0; slab < 2; ++slab)
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[sb][slab][i], fb[sb][slab][j], acc[i][j], 0, 0, 0);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();                                     // barrier kt
-    }
-    store_tile(g, m0, n0, z, wm, wn, lane, acc);
-}
-
-// fp32 [R, C] (row stride ldx) -> ONE bf16 matrix [Rp][Cp] (RNE), padding written as zeros
-__global__ __launch_bounds__(256) void pack_bf16_kernel(const float* __restrict__ X, int R, int C, int ldx, int Rp,
-                                                        int Cp, __bf16* __restrict__ P) {
-    const size_t total = (size_t)Rp * Cp / 4;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int row = (int)(i / (Cp / 4)), c = (int)(i % (Cp / 4)) * 4;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (row < R) {
-            const float* x = X + (size_t)row * ldx + c;
-            if (c + 3 < C && ((ldx & 3) == 0) && ((reinterpret_cast<uintptr_t>(X) & 15) == 0)) {
-                v = *reinterpret_cast<const float4*>(x);
-            } else {
-                if (c < C) v.x = x[0];
-                if (c + 1 < C) v.y = x[1];
-                if (c + 2 < C) v.z = x[2];
-                if (c + 3 < C) v.w = x[3];
-            }
-        }
-        const bf16x2 lo = __builtin_convertvector(f32x2{v.x, v.y}, bf16x2);
-        const bf16x2 hi = __builtin_convertvector(f32x2{v.z, v.w}, bf16x2);
-        *reinterpret_cast<uint2*>(P + (size_t)row * Cp + c) = pack4(lo, hi);
-    }
-}
-
 __global__ __launch_bounds__(256) void split_reduce_kernel(const float* __restrict__ partial, int split_k,
                                                            int M, int N, float alpha, float beta,
                                                            const float* __restrict__ bias,
@@ -1240,47 +748,6 @@ __global__ __launch_bounds__(256) void split_reduce4_kernel(const float* __restr
     }
 }
 
-// RENET_GEMM_TILE_ORDER = 0 | 1: plain order | XCD-aware order (default; the SAME boolean gemm.hip reads).  The panel width
-// of the XCD-aware order is a separate knob, RENET_GEMM_PANEL_W = 1..64 (default 8; setting it also pins the width, i.e.
-// panel_width() below leaves it alone).
-bool panel_w_pinned() { return getenv("RENET_GEMM_PANEL_W") != nullptr; }
-int tile_order() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("RENET_GEMM_TILE_ORDER");
-        if (e && e[0] == '0') v = 0;
-        else {
-            const char* w = getenv("RENET_GEMM_PANEL_W");
-            v = w ? atoi(w) : 8;
-            if (v < 1 || v > 64) v = 8;
-        }
-    }
-    return v;
-}
-
-// Panel width for an UN-SPLIT grid that takes several rounds of tiles per XCD.  The short operand is swept once per round
-// by every XCD; when all of it (ns tiles) does not fit the 4 MB L2 next to the streamed long operand, that cyclic sweep
-// misses (PMC, tools/pmc_by_shape.py: the 256-row logits GEMM fetched 313 MB for 60 MB of operands, 258 MB of it the
-// 4.9 MB `feat`).  Narrower panels keep one panel of the short operand resident (<= 2.5 MB) and re-read the long operand
-// once per extra panel: taken when that costs less than the sweep does (so NOT for dW = dlogits^T feat, whose long
-// operand is 189 MB).  An explicit RENET_GEMM_PANEL_W, the plain order, or a split k range leaves the width alone.
-int panel_width(int base, int nbx, int nby, int tile_m, int K, int split_k, int slots_per_xcd) {
-    if (base != 8 || split_k != 1 || panel_w_pinned()) return base;
-    const bool short_is_m = nby <= nbx;
-    const int ns = short_is_m ? nby : nbx, nl = short_is_m ? nbx : nby;
-    const double slab = (double)(short_is_m ? tile_m : BN) * K * 4.0;           // short-operand bytes of one tile row / column
-    const double long_total = (double)(short_is_m ? BN : tile_m) * K * 4.0 * nl;
-    const double short_total = slab * ns;
-    const double rounds = (double)nbx * nby / (8.0 * slots_per_xcd);
-    if (short_total <= 3.0e6 || rounds <= 1.0) return base;
-    const int w = max(1, min(8, (int)(2.5e6 / slab)));
-    const int w0 = min(ns, 8);
-    if (w >= w0) return base;
-    const int extra_panels = (ns + w - 1) / w - (ns + w0 - 1) / w0;
-    if (long_total * extra_panels >= short_total * rounds * 8.0) return base;
-    return w;
-}
-
 template <bool TA, bool TB>
 int launch_fused(const SplitArgs& g, dim3 grid, hipStream_t st) {
     static bool attr_set = false;      // benign race: the attribute is idempotent
@@ -1312,37 +779,12 @@ int launch_tall(const SplitArgs& g, dim3 grid, hipStream_t st) {
 // 256-row tiles when the output has enough of them to fill the chip a few times (RENET_GEMM_TALL=0 disables,
 // =<n> sets the minimum tile count)
 bool use_tall(int ta, int M, int nbx, int split_k) {
-    static int min_tiles = -1;
-    static bool forced = false;
-    if (min_tiles < 0) {
-        const char* e = getenv("RENET_GEMM_TALL");
-        forced = e != nullptr;
-        min_tiles = e ? atoi(e) : 1000;             // measured: logits 2048 x 23033 x 600 (1440 tiles) 395 -> 362 us;
-                                                    // dW 23033 x 600 x 2048 (450 tiles: 1.76 rounds) 447 -> 480 us
-        if (e && min_tiles == 0) min_tiles = 0x7fffffff;
-    }
+    static const int forced = renet_env_int("RENET_GEMM_TALL", -1, 0, 0x7fffffff);      // -1: not set
     const long tiles = (long)nbx * ((M + BMT - 1) / BMT) * split_k;
-    if (forced) return tiles >= min_tiles;
+    if (forced >= 0) return forced > 0 && tiles >= forced;
+    // measured: logits 2048 x 23033 x 600 (1440 tiles) 395 -> 362 us; dW 23033 x 600 x 2048 (450 tiles: 1.76 rounds) 447 -> 480 us
     // round 4: as for the f16x3 kernels (use_tall_h3), K-contiguous A with a split k range from 200 tiles on (dfeat)
-    return tiles >= min_tiles || (!ta && split_k >= 4 && tiles >= 200);
-}
-
-// f16x3 kernels: the 256-row tile from RENET_H3_TALL tiles on (default 1000, as for the bf16x6 kernels; 0 disables).
-// Measured on the step's shapes (tools/sessions/r03_s20.sh): the tall tile wins for K-contiguous A from 200 tiles on
-// when the k range is split (dfeat 2048 x 600 x 23033 / 6: 286 -> 259 us) and loses for K-strided A (dW 23033 x 600 x
-// 2048: 293 -> 319 us; the split-K weight gradients 100 -> 178 us).
-bool use_tall_h3(int ta, int M, int nbx, int split_k) {
-    static int min_tiles = -1;
-    static bool forced = false;
-    if (min_tiles < 0) {
-        const char* e = getenv("RENET_H3_TALL");
-        forced = e != nullptr;
-        min_tiles = e ? atoi(e) : 1000;
-        if (e && min_tiles == 0) min_tiles = 0x7fffffff;
-    }
-    const long tiles = (long)nbx * ((M + 255) / 256) * split_k;
-    if (forced) return tiles >= min_tiles;
-    return !ta && (tiles >= min_tiles || (split_k >= 4 && tiles >= 200));
+    return tiles >= 1000 || (!ta && split_k >= 4 && tiles >= 200);
 }
 
 // Which k-loop: the fused kernel (one workgroup per CU, 122.9 KB LDS) when the whole grid fits in ONE round of
@@ -1352,63 +794,36 @@ bool use_tall_h3(int ta, int M, int nbx, int split_k) {
 // C-store epilogue and the barrier waits of the first (short K loops: 133 vs 117 TFLOP/s on the 1440-tile
 // K=600 logits GEMM).  RENET_GEMM_KERNEL=fused|split forces one of them (tools/gemm_bench.py).
 int kernel_choice(int ntiles) {
-    static int forced = -2;
-    if (forced == -2) {
-        const char* e = getenv("RENET_GEMM_KERNEL");
-        forced = !e ? -1 : e[0] == 's' ? 1 : e[0] == 'f' ? 0 : -1;
-    }
+    static const int forced = renet_env_is("RENET_GEMM_KERNEL", "split") ? 1 : renet_env_is("RENET_GEMM_KERNEL", "fused") ? 0 : -1;
     if (forced >= 0) return forced;
     return ntiles <= 256 ? 0 : 1;
 }
 
-#include "gemm_h3.h"
-#include "gemm_p6.h"
-
 }  // namespace
 
-namespace {
-template <bool A_TR, bool B_TR, bool TALL>
-int launch_bf16s(const Bf16sArgs& pa, dim3 grid, hipStream_t st) {
-    constexpr size_t lds = TALL ? B1_LDS_TALL : B1_LDS;
-    static bool attr_set = false;      // benign race: the attribute is idempotent
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)gemm_bf16s_kernel<A_TR, B_TR, TALL>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
+int renet_split_reduce(const float* partial, int split_k, int M, int N, float alpha, float beta, const float* bias,
+                       float* C, int ldc, hipStream_t st) {
+    const size_t total = (size_t)M * N;
+    if (total <= (size_t)256 * 1024 && split_k >= 8) {
+        RENET_LAUNCH(split_reduce4_kernel, dim3((unsigned)((total + 63) / 64)), dim3(256), 0, st, partial, split_k, M, N,
+                     alpha, beta, bias, C, ldc);
+    } else {
+        int blocks = (int)min((size_t)2048, (total + 255) / 256);
+        RENET_LAUNCH(split_reduce_kernel, dim3(blocks), dim3(256), 0, st, partial, split_k, M, N, alpha, beta, bias, C, ldc);
     }
-    RENET_LAUNCH((gemm_bf16s_kernel<A_TR, B_TR, TALL>), grid, dim3(TALL ? 768 : P3_THREADS), lds, st, pa);
     RENET_LAUNCH_CHECK();
     return RENET_OK;
 }
 
-}  // namespace
-
 extern "C" {
 
 #ifdef RENET_GEMM_TRACE
+int renet_gemm_h3_trace_set(unsigned long long* buf);      // gemm_h3.hip: every translation unit has its own g_trace
 int renet_gemm_trace_set(unsigned long long* buf) {
-    return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_trace), &buf, sizeof(buf));
+    const int e = (int)hipMemcpyToSymbol(HIP_SYMBOL(g_trace), &buf, sizeof(buf));
+    return e ? e : renet_gemm_h3_trace_set(buf);
 }
 #endif
-
-static bool skinny_enabled() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("RENET_GEMM_SKINNY");
-        v = (e && e[0] == '0') ? 0 : 1;
-    }
-    return v != 0;
-}
-
-static bool split_raw_enabled() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("RENET_GEMM_SPLIT_RAW");
-        v = (e && e[0] == '0') ? 0 : 1;
-    }
-    return v != 0;
-}
 
 // What the bf16x6 / bf16 launcher does for a problem: ONE function decides, the launcher executes it and
 // renet_gemm_split_plan reports it (host logic only -- testable without a GPU).
@@ -1429,12 +844,12 @@ static SplitPlan plan_split(bool bf16_mode, int ta, int tb, int M, int N, int K,
     if (split_k > kt_total) split_k = max(kt_total, 1);
     p.split_k = split_k;
     p.raw = 0;
-    p.xcd_order = tile_order();
+    p.xcd_order = renet_gemm_tile_order();
     const int nbx = (N + BN - 1) / BN, nby = (M + BM - 1) / BM;
     p.gx = nbx; p.gy = nby; p.gz = split_k;
     // tall activation x small weight (K <= 208, N <= 256): the weight-resident kernel of gemm_skinny.hip
     // (RENET_GEMM_SKINNY=0 in the environment keeps the general kernels, for A/B runs)
-    if (!bf16_mode && split_k == 1 && skinny_enabled() && renet_gemm_skinny_eligible(ta, M, N, K, A, lda, B, ldb, tb)) {
+    if (!bf16_mode && split_k == 1 && renet_gemm_skinny_enabled() && renet_gemm_skinny_eligible(ta, M, N, K, A, lda, B, ldb, tb)) {
         p.kernel = 3;
         return p;
     }
@@ -1446,9 +861,8 @@ static SplitPlan plan_split(bool bf16_mode, int ta, int tb, int M, int N, int K,
     if (choice == 0) { p.kernel = 0; return p; }
     if (choice == 2) { p.kernel = 4; return p; }
     // two-phase kernels: raw buffer descriptors (32-bit byte offsets) while both operands reach less than 2^30 elements
-    // (RENET_GEMM_SPLIT_RAW=0: the generic 64-bit loader, for A/B runs)
-    p.raw = split_raw_enabled() && (size_t)(ta ? K : M) * lda < ((size_t)1 << 30) &&
-            (size_t)(tb ? N : K) * ldb < ((size_t)1 << 30);
+    // (the generic 64-bit loader beyond that)
+    p.raw = (size_t)(ta ? K : M) * lda < ((size_t)1 << 30) && (size_t)(tb ? N : K) * ldb < ((size_t)1 << 30);
     if (use_tall(ta, M, nbx, split_k)) {
         p.kernel = 2;
         p.gy = (M + BMT - 1) / BMT;
@@ -1516,18 +930,7 @@ static int gemm_split_launch(bool bf16_mode, int ta, int tb, int M, int N, int K
     }
     if (e != RENET_OK) return e;
     RENET_LAUNCH_CHECK();
-    if (split_k > 1) {
-        const size_t total = (size_t)M * N;
-        if (total <= (size_t)256 * 1024 && split_k >= 8) {
-            RENET_LAUNCH(split_reduce4_kernel, dim3((unsigned)((total + 63) / 64)), dim3(256), 0, st, workspace,
-                               split_k, M, N, alpha, beta, bias, C, ldc);
-        } else {
-            int blocks = (int)min((size_t)2048, (total + 255) / 256);
-            RENET_LAUNCH(split_reduce_kernel, dim3(blocks), dim3(256), 0, st, workspace, split_k, M, N, alpha,
-                               beta, bias, C, ldc);
-        }
-        RENET_LAUNCH_CHECK();
-    }
+    if (split_k > 1) return renet_split_reduce(workspace, split_k, M, N, alpha, beta, bias, C, ldc, st);
     return RENET_OK;
 }
 
@@ -1554,282 +957,6 @@ int renet_gemm_bf16(int ta, int tb, int M, int N, int K, float alpha, const floa
                     int split_k, float* workspace, size_t workspace_bytes, void* stream) {
     return gemm_split_launch(true, ta, tb, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, bias, split_k, workspace,
                               workspace_bytes, stream);
-}
-
-int renet_maxabs_blocks(int rows, int cols, int ld) {
-    if (rows <= 0 || cols <= 0) return 1;
-    const size_t total = (size_t)rows * cols;
-    if (ld == cols && (total & 3) == 0) return (int)max((size_t)1, min((size_t)256, total / 4096));
-    return min(rows, 256);
-}
-
-int renet_maxabs_partials(const float* x, int rows, int cols, int ld, float* part, void* stream) {
-    if (rows < 0 || cols < 0 || ld < cols || !part) return RENET_ERR_BADARG;
-    if (rows == 0 || cols == 0) {
-        hipError_t e = hipMemsetAsync(part, 0, sizeof(float), (hipStream_t)stream);
-        return e == hipSuccess ? RENET_OK : (int)e;
-    }
-    const int blocks = renet_maxabs_blocks(rows, cols, ld);
-    const bool flat = ld == cols && (((size_t)rows * cols) & 3) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
-    if (flat) RENET_LAUNCH(maxabs_partials_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, rows, cols,
-                           (size_t)ld, part);
-    else RENET_LAUNCH(maxabs_partials_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, rows, cols,
-                      (size_t)ld, part);
-    RENET_LAUNCH_CHECK();
-    return RENET_OK;
-}
-
-int renet_maxabs_partials_multi(const void* jobs, int n_jobs, void* stream) {
-    if (n_jobs < 0 || (n_jobs > 0 && !jobs)) return RENET_ERR_BADARG;
-    if (n_jobs == 0) return RENET_OK;
-    RENET_LAUNCH(maxabs_multi_kernel, dim3(256, n_jobs), dim3(256), 0, (hipStream_t)stream, (const MaxabsJob*)jobs);
-    RENET_LAUNCH_CHECK();
-    return RENET_OK;
-}
-
-int renet_gemm_f32_h3(int ta, int tb, int M, int N, int K, float alpha, const float* A, int lda, const float* B,
-                      int ldb, float beta, float* C, int ldc, const float* bias, int split_k, float* workspace,
-                      size_t workspace_bytes, const float* maxA, int nA, const float* maxB, int nB, void* stream) {
-    if (M < 0 || N < 0 || K < 1 || lda <= 0 || ldb <= 0 || ldc < N) return RENET_ERR_BADARG;
-    if (!maxA || !maxB || nA < 1 || nB < 1 || nA > 1024 || nB > 1024) return RENET_ERR_BADARG;
-    if (M == 0 || N == 0) return RENET_OK;
-    // the f16x3 loaders address with 32-bit byte offsets; operands of 4 GiB and more and the weight-resident shapes run
-    // the bf16x6 kernels (same accuracy class, no bounds needed)
-    const bool small_ok = (size_t)(ta ? K : M) * lda < ((size_t)1 << 30) && (size_t)(tb ? N : K) * ldb < ((size_t)1 << 30);
-    if (!small_ok || ((split_k <= 1) && skinny_enabled() && renet_gemm_skinny_eligible(ta, M, N, K, A, lda, B, ldb, tb)))
-        return gemm_split_launch(false, ta, tb, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, bias, split_k, workspace,
-                                  workspace_bytes, stream);
-    if (split_k < 1) split_k = 1;
-    const int kt_total = (K + BK - 1) / BK;
-    if (split_k > kt_total) split_k = max(kt_total, 1);
-    if (split_k > 1 && workspace_bytes < renet_gemm_workspace(M, N, split_k)) return RENET_ERR_WORKSPACE;
-    H3Args h;
-    SplitArgs& g = h.g;
-    g.A = A; g.B = B; g.C = C; g.bias = bias; g.M = M; g.N = N; g.K = K;
-    g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.alpha = alpha; g.beta = beta;
-    g.split_k = split_k;
-    g.k_tiles_per_split = max(1, (kt_total + split_k - 1) / split_k);
-    g.partial = workspace;
-    g.xcd_order = tile_order();
-    h.maxA = maxA; h.maxB = maxB; h.nA = nA; h.nB = nB;
-    hipStream_t st = (hipStream_t)stream;
-    const int nbx = (N + BN - 1) / BN;
-#define RENET_H3_LAUNCH(TALLV, THR)                                                                    \
-    do {                                                                                               \
-        if (!ta && !tb) RENET_LAUNCH((gemm_h3_kernel<false, false, TALLV>), grid, dim3(THR), 0, st, h); \
-        else if (!ta && tb) RENET_LAUNCH((gemm_h3_kernel<false, true, TALLV>), grid, dim3(THR), 0, st, h); \
-        else if (ta && !tb) RENET_LAUNCH((gemm_h3_kernel<true, false, TALLV>), grid, dim3(THR), 0, st, h); \
-        else RENET_LAUNCH((gemm_h3_kernel<true, true, TALLV>), grid, dim3(THR), 0, st, h);              \
-    } while (0)
-    if (use_tall_h3(ta, M, nbx, split_k)) {
-        dim3 grid(nbx, (M + 255) / 256, split_k);
-        g.xcd_order = panel_width(g.xcd_order, nbx, (int)grid.y, 256, K, split_k, 32);
-        RENET_H3_LAUNCH(true, 512);
-    } else {
-        dim3 grid(nbx, (M + BM - 1) / BM, split_k);
-        g.xcd_order = panel_width(g.xcd_order, nbx, (int)grid.y, BM, K, split_k, 64);
-        RENET_H3_LAUNCH(false, 256);
-    }
-#undef RENET_H3_LAUNCH
-    RENET_LAUNCH_CHECK();
-    if (split_k > 1) {
-        const size_t total = (size_t)M * N;
-        if (total <= (size_t)256 * 1024 && split_k >= 8) {
-            RENET_LAUNCH(split_reduce4_kernel, dim3((unsigned)((total + 63) / 64)), dim3(256), 0, st, workspace,
-                               split_k, M, N, alpha, beta, bias, C, ldc);
-        } else {
-            int blocks = (int)min((size_t)2048, (total + 255) / 256);
-            RENET_LAUNCH(split_reduce_kernel, dim3(blocks), dim3(256), 0, st, workspace, split_k, M, N, alpha,
-                               beta, bias, C, ldc);
-        }
-        RENET_LAUNCH_CHECK();
-    }
-    return RENET_OK;
-}
-
-size_t renet_bf16_bytes(int R, int C) {
-    const size_t rp = ((size_t)R + 255) & ~(size_t)255, cp = ((size_t)C + 255) & ~(size_t)255;
-    return rp * cp * sizeof(__bf16);
-}
-
-int renet_pack_bf16(const float* X, int R, int C, int ldx, void* out, void* stream) {
-    if (R < 0 || C < 0 || ldx < C || !out) return RENET_ERR_BADARG;
-    const int Rp = (R + 255) & ~255, Cp = (C + 255) & ~255;
-    if (Rp == 0 || Cp == 0) return RENET_OK;
-    const size_t total = (size_t)Rp * Cp / 4;
-    const int blocks = (int)min((size_t)4096, (total + 255) / 256);
-    RENET_LAUNCH(pack_bf16_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, X, R, C, ldx, Rp, Cp, (__bf16*)out);
-    RENET_LAUNCH_CHECK();
-    return RENET_OK;
-}
-
-int renet_bf16_zero_padding(void* P, int rows, int C, int ld, int rows_alloc, void* stream) {
-    if (!P || rows < 0 || C < 0 || ld < C || rows_alloc < rows) return RENET_ERR_BADARG;
-    __bf16* p = (__bf16*)P;
-    hipStream_t st = (hipStream_t)stream;
-    const int c16 = min((C + 63) & ~63, ld), r16 = min((rows + 63) & ~63, rows_alloc);
-    if (c16 > C && rows > 0) {
-        hipError_t e = hipMemset2DAsync(p + C, (size_t)ld * sizeof(__bf16), 0, (size_t)(c16 - C) * sizeof(__bf16),
-                                        (size_t)rows, st);
-        if (e != hipSuccess) return (int)e;
-    }
-    if (r16 > rows) {
-        hipError_t e = hipMemsetAsync(p + (size_t)rows * ld, 0, (size_t)(r16 - rows) * ld * sizeof(__bf16), st);
-        if (e != hipSuccess) return (int)e;
-    }
-    return RENET_OK;
-}
-
-int renet_gemm_bf16s(int a_tr, int b_tr, int M, int N, int K, float alpha, const void* Ap, int lda, const void* Bp,
-                     int ldb, float beta, float* C, int ldc, const float* bias, int split_k, float* workspace,
-                     size_t workspace_bytes, void* stream) {
-    if (M < 0 || N < 0 || K < 1 || ldc < N || !Ap || !Bp) return RENET_ERR_BADARG;
-    if (M == 0 || N == 0) return RENET_OK;
-    const int Mp = (M + 255) & ~255, Np = (N + 255) & ~255, Kp = (K + 255) & ~255;
-    if (lda < (a_tr ? Mp : Kp) || ldb < (b_tr ? Np : Kp) || (lda & 7) || (ldb & 7)) return RENET_ERR_BADARG;
-    if (split_k < 1) split_k = 1;
-    const int st_total = (K + B1_BK - 1) / B1_BK;
-    if (split_k > st_total) split_k = max(st_total, 1);
-    if (split_k > 1 && workspace_bytes < renet_gemm_workspace(M, N, split_k)) return RENET_ERR_WORKSPACE;
-    Bf16sArgs pa;
-    pa.A = (const __bf16*)Ap; pa.B = (const __bf16*)Bp;
-    pa.lda = lda; pa.ldb = ldb;
-    SplitArgs& g = pa.out;
-    g.A = nullptr; g.B = nullptr; g.C = C; g.bias = bias; g.M = M; g.N = N; g.K = K;
-    g.lda = 0; g.ldb = 0; g.ldc = ldc; g.alpha = alpha; g.beta = beta;
-    g.split_k = split_k;
-    g.k_tiles_per_split = max(1, (st_total + split_k - 1) / split_k);
-    g.partial = workspace;
-    g.xcd_order = tile_order();
-    hipStream_t st = (hipStream_t)stream;
-    // 256 x 128 tiles when they still fill the chip (>= 256 workgroups); the matrices are padded to multiples of
-    // 256 in both dimensions, so a 256-row (or, K-strided, 256-column) A image never leaves the buffer --
-    // RENET_BF16S_TALL=0 keeps the 128 x 128 tile
-    const int nbx = (N + BN - 1) / BN;
-    static int tall_ok = -1;
-    if (tall_ok < 0) {
-        const char* e_ = getenv("RENET_BF16S_TALL");
-        tall_ok = (e_ && e_[0] == '0') ? 0 : 1;
-    }
-    const bool tall = tall_ok && (size_t)nbx * (Mp / 256) * split_k >= 256;
-    dim3 grid(nbx, tall ? Mp / 256 : (M + BM - 1) / BM, split_k);
-    int e;
-    if (tall) {
-        if (!a_tr && !b_tr) e = launch_bf16s<false, false, true>(pa, grid, st);
-        else if (!a_tr && b_tr) e = launch_bf16s<false, true, true>(pa, grid, st);
-        else if (a_tr && !b_tr) e = launch_bf16s<true, false, true>(pa, grid, st);
-        else e = launch_bf16s<true, true, true>(pa, grid, st);
-    } else {
-        if (!a_tr && !b_tr) e = launch_bf16s<false, false, false>(pa, grid, st);
-        else if (!a_tr && b_tr) e = launch_bf16s<false, true, false>(pa, grid, st);
-        else if (a_tr && !b_tr) e = launch_bf16s<true, false, false>(pa, grid, st);
-        else e = launch_bf16s<true, true, false>(pa, grid, st);
-    }
-    if (e != RENET_OK) return e;
-    if (split_k > 1) {
-        const size_t total = (size_t)M * N;
-        if (total <= (size_t)256 * 1024 && split_k >= 8) {
-            RENET_LAUNCH(split_reduce4_kernel, dim3((unsigned)((total + 63) / 64)), dim3(256), 0, st, workspace,
-                               split_k, M, N, alpha, beta, bias, C, ldc);
-        } else {
-            int blocks = (int)min((size_t)2048, (total + 255) / 256);
-            RENET_LAUNCH(split_reduce_kernel, dim3(blocks), dim3(256), 0, st, workspace, split_k, M, N, alpha,
-                               beta, bias, C, ldc);
-        }
-        RENET_LAUNCH_CHECK();
-    }
-    return RENET_OK;
-}
-
-// ---- planes GEMM (gemm_p6.h) -----------------------------------------------------------------------------------
-size_t renet_planes_elems(int R, int C) {
-    const size_t rp = ((size_t)R + 255) & ~(size_t)255, cp = ((size_t)C + 255) & ~(size_t)255;
-    return rp * cp;
-}
-
-int renet_pack_planes(const float* X, int R, int C, int ldx, int ones_col, void* out, void* stream) {
-    if (R < 0 || C < 0 || ldx < C || !out) return RENET_ERR_BADARG;
-    const int cols = ones_col ? C + 1 : C;
-    const int Rp = (R + 255) & ~255, Cp = (cols + 255) & ~255;
-    if (Rp == 0 || Cp == 0) return RENET_OK;
-    const size_t blocks = (size_t)(Rp >> 4) * (size_t)(Cp >> 6);       // one workgroup per tile row x 4 tiles
-    if (blocks > 0x7fffffffu) return RENET_ERR_UNSUPPORTED;
-    RENET_LAUNCH(pack_planes_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, X, R, C, ldx, Rp, Cp,
-                 ones_col ? C : -1, (__bf16*)out, (size_t)Rp * Cp);
-    RENET_LAUNCH_CHECK();
-    return RENET_OK;
-}
-
-int renet_gemm_planes(int a_tr, int b_tr, int M, int N, int K, float alpha, const float* alpha_dev, const void* Ap,
-                      int lda, size_t a_plane, const void* Bp, int ldb, size_t b_plane, float beta, float* C, int ldc,
-                      const float* bias, float* col_out, int split_k, float* workspace, size_t workspace_bytes,
-                      void* stream) {
-    // N counts the logical columns of the product INCLUDING the col_out one
-    const int n_main = col_out ? N - 1 : N;
-    if (M < 0 || N < 0 || n_main < 0 || K < 1 || ldc < n_main || !Ap || !Bp) return RENET_ERR_BADARG;
-    if (M == 0 || N == 0) return RENET_OK;
-    // lda / ldb: Cp (columns of the padded stored matrix, a multiple of 16: T16 tiles, gemm_p6.h)
-    const int Mp = (M + 255) & ~255, Np = (N + 127) & ~127, Kp = (K + 15) & ~15;
-    if (lda < (a_tr ? Mp : Kp) || ldb < (b_tr ? Np : Kp) || (lda & 15) || (ldb & 15)) return RENET_ERR_BADARG;
-    // the plane strides must cover the stored (padded) matrix
-    if (a_plane < (size_t)(a_tr ? Kp : Mp) * lda || b_plane < (size_t)(b_tr ? Kp : Np) * ldb) return RENET_ERR_BADARG;
-    if (split_k < 1) split_k = 1;
-    const int st_total = (K + 15) / 16;                       // half-stages of 16 k (gemm_p6.h)
-    if (split_k > st_total) split_k = max(st_total, 1);
-    if (split_k > 1 && workspace_bytes < renet_gemm_workspace(M, N, split_k)) return RENET_ERR_WORKSPACE;
-    P6Args pa;
-    pa.A = (const __bf16*)Ap; pa.B = (const __bf16*)Bp;
-    pa.a_plane = a_plane; pa.b_plane = b_plane;
-    pa.tca = lda >> 4; pa.tcb = ldb >> 4;
-    pa.alpha_dev = alpha_dev; pa.col_out = col_out;
-    SplitArgs& g = pa.out;
-    g.A = nullptr; g.B = nullptr; g.C = C; g.bias = bias; g.M = M; g.N = N; g.K = K;
-    g.lda = 0; g.ldb = 0; g.ldc = ldc; g.alpha = alpha; g.beta = beta;
-    g.split_k = split_k;
-    g.k_tiles_per_split = (max(1, (st_total + split_k - 1) / split_k) + 1) & ~1;     // even: see gemm_p6_kernel
-    g.partial = workspace;
-    hipStream_t st = (hipStream_t)stream;
-    // tile height: 128 rows (two workgroups per CU) unless RENET_P6_TILE=256 (one 8-wave workgroup per CU)
-    static int tile_h = 0;
-    if (!tile_h) {
-        const char* e_ = getenv("RENET_P6_TILE");
-        tile_h = (e_ && atoi(e_) == 256) ? 256 : 128;
-    }
-    const int nbx = (N + BN - 1) / BN, nby = (M + tile_h - 1) / tile_h;
-    g.xcd_order = panel_width(tile_order(), nbx, nby, tile_h, K, split_k, tile_h == 256 ? 32 : 64);
-    // persistent grid: at most `slots` workgroups (two per CU for the 128-row tile, one for the 256-row tile), a multiple of 8
-    // when the items outnumber it (a workgroup then stays on one XCD's share of the tile sequence); RENET_P6_PERSISTENT=1
-    // selects it (default: one workgroup per item)
-    pa.nbx = nbx; pa.nby = nby; pa.nbz = split_k;
-    static int persistent = -1;
-    if (persistent < 0) {
-        const char* e_ = getenv("RENET_P6_PERSISTENT");
-        persistent = (e_ && e_[0] == '1') ? 1 : 0;      // measured: no gain (profiles/r06_a_planes_ablation.md, v6): off by default
-    }
-    const long items = (long)nbx * nby * split_k;
-    const long slots = tile_h == 256 ? 256 : 512;
-    if (items > 0x7fffffffL) return RENET_ERR_UNSUPPORTED;
-    dim3 grid((unsigned)((persistent && items > slots) ? slots : items), 1, 1);
-    int e;
-#define RENET_P6_LAUNCH(WMV)                                                   \
-    do {                                                                       \
-        if (!a_tr && !b_tr) e = launch_p6<false, false, WMV>(pa, grid, st);    \
-        else if (!a_tr && b_tr) e = launch_p6<false, true, WMV>(pa, grid, st); \
-        else if (a_tr && !b_tr) e = launch_p6<true, false, WMV>(pa, grid, st); \
-        else e = launch_p6<true, true, WMV>(pa, grid, st);                     \
-    } while (0)
-    if (tile_h == 256) RENET_P6_LAUNCH(4);
-    else RENET_P6_LAUNCH(2);
-#undef RENET_P6_LAUNCH
-    if (e != RENET_OK) return e;
-    if (split_k > 1) {
-        const size_t total = (size_t)M * N;
-        const int blocks = (int)min((size_t)2048, (total + 255) / 256);
-        RENET_LAUNCH(p6_reduce_kernel, dim3(blocks), dim3(256), 0, st, workspace, split_k, M, N, alpha, alpha_dev, beta,
-                     bias, C, ldc, col_out);
-        RENET_LAUNCH_CHECK();
-    }
-    return RENET_OK;
 }
 
 }  // extern "C"

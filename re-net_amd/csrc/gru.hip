@@ -1275,12 +1275,8 @@ __global__ __launch_bounds__(256) void transpose_kernel(const float* __restrict_
 }
 
 bool use_f32() {                        // RENET_GEMM=f32: exact-fp32 products everywhere (gemm.hip too)
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("RENET_GEMM");
-        v = (e && strcmp(e, "f32") == 0) ? 1 : 0;
-    }
-    return v == 1;
+    static const bool v = renet_env_is("RENET_GEMM", "f32");
+    return v;
 }
 
 template <class KernelT>
@@ -1321,30 +1317,21 @@ int launch_fwd_x(const FwdProbsB& ps, int np, const Layouts& ly, hipStream_t st)
     return RENET_OK;
 }
 
-// RENET_GRU_FWD=ring selects the per-unit-block kernel (gru_fwd_bf_kernel) at H <= 200 as well, for A/B runs
-inline bool fwd_stream_kernel() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("RENET_GRU_FWD");
-        v = (e && strcmp(e, "ring") == 0) ? 0 : 1;
-    }
-    return v == 1;
-}
-
 template <int H, int NPL = 3>
 int launch_fwd_bf(const FwdProbsB& ps, int np, const Layouts& ly, hipStream_t st) {
-    using C = Cfg<H>;
-    if constexpr (NPL == 3 && H <= 200) {
-        if (fwd_stream_kernel()) return launch_fwd_x<H>(ps, np, ly, st);
+    if constexpr (NPL == 3 && H <= 200) {                  // the continuous-stream kernel (profiles/r06_f_gru.md)
+        return launch_fwd_x<H>(ps, np, ly, st);
+    } else {                                               // the per-unit-block kernel: H = 400 and the one-plane mode
+        using C = Cfg<H>;
+        constexpr int WV = NPL == 1 ? nw1<H>() : nw3<H>();
+        const size_t lds = (size_t)2 * MT * C::LDH * sizeof(float) + (size_t)3 * MT * BCfg<H>::LDP * sizeof(__bf16);
+        static bool attr_set = false;
+        const int e = set_lds(gru_fwd_bf_kernel<H, NPL, WV>, lds, attr_set);
+        if (e != RENET_OK) return e;
+        RENET_LAUNCH((gru_fwd_bf_kernel<H, NPL, WV>), dim3((max_rows(ly) + MT - 1) / MT, np), dim3(WV * 64), lds, st, ps, ly);
+        RENET_LAUNCH_CHECK();
+        return RENET_OK;
     }
-    constexpr int WV = NPL == 1 ? nw1<H>() : nw3<H>();
-    const size_t lds = (size_t)2 * MT * C::LDH * sizeof(float) + (size_t)3 * MT * BCfg<H>::LDP * sizeof(__bf16);
-    static bool attr_set = false;
-    const int e = set_lds(gru_fwd_bf_kernel<H, NPL, WV>, lds, attr_set);
-    if (e != RENET_OK) return e;
-    RENET_LAUNCH((gru_fwd_bf_kernel<H, NPL, WV>), dim3((max_rows(ly) + MT - 1) / MT, np), dim3(WV * 64), lds, st, ps, ly);
-    RENET_LAUNCH_CHECK();
-    return RENET_OK;
 }
 
 template <int H>
@@ -1385,13 +1372,8 @@ inline size_t kp_of(int K) { return (size_t)((K + 31) / 32) * 32; }
 // while the persistent workgroups drift apart and overlap the two.  With the W_hh stream of the persistent workgroups
 // de-synchronised (rot_k / rot_u in the kernels: 188 -> 142 us at H = 200, 858 -> ~790 us at H = 400) the persistent
 // kernels are the default everywhere; RENET_GRU=steps selects the per-step launches.
-bool use_persistent(int H) {
-    const char* e = getenv("RENET_GRU");
-    if (e && strcmp(e, "persistent") == 0) return true;
-    if (e && strcmp(e, "steps") == 0) return false;
-    (void)H;
-    return true;
-}
+// (Read per launch, unlike every other switch: tests/test_gpu_parity.py runs both structures in ONE process.)
+bool use_persistent() { return !renet_env_is("RENET_GRU", "steps"); }
 
 struct StepState {                      // per problem: bf16 plane ping-pong of the A operand + fp32 dh
     __bf16* A[2];
@@ -1539,10 +1521,8 @@ int make_layouts(int n, const int32_t* const* step_off, const int* Ls, const int
         for (int j = 0; j <= MAXL; ++j) ly.so[i].off[j] = 0;
     }
     for (int k = 0; k < MAXP; ++k) ly.lay_of[k] = 0;
-    {
-        const char* e = getenv("RENET_GRU_ROT");
-        ly.rot_mod = e ? atoi(e) : 0;
-    }
+    static const int rot_mod = renet_env_int("RENET_GRU_ROT", 0, 0, 0x7fffffff);
+    ly.rot_mod = rot_mod;
     for (int k = 0; k < n; ++k) {
         int l = -1;
         for (int i = 0; i < nl; ++i)
@@ -1642,7 +1622,7 @@ static int gru_fwd_impl(int npl, int n, const float* const* Gi, const int32_t* c
             default: return launch_fwd<400>(ps, n, ly, st);
         }
     }
-    const bool steps = npl == 3 && !use_persistent(H);
+    const bool steps = npl == 3 && !use_persistent();
     int Bmax = 0;
     for (int k = 0; k < n; ++k) Bmax = B_of[k] > Bmax ? B_of[k] : Bmax;
     const size_t per = renet_gru_workspace(steps ? Bmax : 0, H);
@@ -1753,7 +1733,7 @@ static int gru_bwd_impl(int npl, int n, const float* const* dh_last, const int32
     if (H != 100 && H != 200 && H != 400) return RENET_ERR_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
     const bool f32 = npl == 0 || (use_f32() && npl == 3);
-    const bool steps = npl == 3 && !f32 && !use_persistent(H);
+    const bool steps = npl == 3 && !f32 && !use_persistent();
     if (bounds && (f32 || steps || npl != 3)) return RENET_ERR_UNSUPPORTED;   // only the persistent bf16x6 kernel emits them
     int Bmax = 0;
     for (int k = 0; k < n; ++k) Bmax = B_of[k] > Bmax ? B_of[k] : Bmax;

@@ -655,11 +655,7 @@ int launch_gather_items(const ItemArgs& a, bool tr, bool pruned, hipStream_t st)
 
 // edges in flight per wave (tuning knob, read once): RENET_GATHER_UNR in {2, 3, 4, 6, 8}; 0 / unset = default
 int gather_unr() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("RENET_GATHER_UNR");
-        v = e ? atoi(e) : 0;
-    }
+    static const int v = renet_env_int("RENET_GATHER_UNR", 0, 0, 8);
     return v;
 }
 

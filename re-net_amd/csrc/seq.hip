@@ -4,7 +4,7 @@
 
 namespace {
 
-// Magnitude bounds for the f16x3 GEMMs (gemm_h3.h), produced by the kernel that WRITES the operand instead of a
+// Magnitude bounds for the f16x3 GEMMs (gemm_h3.hip), produced by the kernel that WRITES the operand instead of a
 // separate pass over it: every workgroup's maximum of |value written| goes to part[blockIdx.x] (grid <= 1024 = the
 // number of partial maxima renet_gemm_f32_h3 accepts).  The maximum over the partials is the tensor's exact maximum,
 // so the GEMMs scale -- and round -- exactly as with renet_maxabs_partials.
@@ -390,7 +390,7 @@ __global__ __launch_bounds__(1024) void softmax_ce_lds_kernel(const float* logit
     }
 }
 
-// ---- the CE gradient as THREE bf16 PLANES (round 6): the operand format of renet_gemm_planes (gemm_p6.h) -----------
+// ---- the CE gradient as THREE bf16 PLANES (round 6): the operand format of renet_gemm_planes (gemm_planes.hip) -----------
 // dl = (softmax - onehot) * grad_scale is never stored as fp32: each value leaves this kernel as p1 = rne(dl),
 // p2 = rne(dl - p1), p3 = rne(dl - p1 - p2) -- the split the bf16x6 GEMM loaders (gemm_split.hip: store_items) do per k-tile
 // -- into planes [3][rows16][ld16]; 6 bytes per element instead of 4, and the backward GEMMs that consume it (dfeat, dW)
@@ -921,12 +921,7 @@ static int softmax_ce_impl(const float* logits, const int32_t* target, int B, in
     if (B < 0 || C <= 0 || ld < C) return RENET_ERR_BADARG;
     if (B == 0) return RENET_OK;
     const size_t lds = (size_t)C * sizeof(float);
-    static int reg_ok = -1;                 // RENET_SOFTMAX_REG=0: the LDS-staged kernel for every wide row (A/B runs)
-    if (reg_ok < 0) {
-        const char* e_ = getenv("RENET_SOFTMAX_REG");
-        reg_ok = (e_ && e_[0] == '0') ? 0 : 1;
-    }
-    if (reg_ok && !dl16 && C >= 4096 && C <= 48 * 512) {
+    if (!dl16 && C >= 4096 && C <= 48 * 512) {
         const dim3 grid(B), blk(512);
         hipStream_t st = (hipStream_t)stream;
         if (C <= 16 * 512) RENET_LAUNCH((softmax_ce_reg_kernel<16>), grid, blk, 0, st, logits, target, C, ld, grad_scale, row_loss, dlogits);
@@ -968,11 +963,8 @@ int renet_softmax_ce_planes(const float* logits, const int32_t* target, int B, i
     }
     const bool aligned = (ld & 3) == 0 && (reinterpret_cast<uintptr_t>(logits) & 15) == 0 &&
                          (reinterpret_cast<uintptr_t>(dl_planes) & 7) == 0 && (plane & 3) == 0;
-    static int rows4 = -1;                 // RENET_SOFTMAX_ROWS=1: one row per workgroup (the first planes writer), for A/B runs
-    if (rows4 < 0) {
-        const char* e_ = getenv("RENET_SOFTMAX_ROWS");
-        rows4 = (e_ && e_[0] == '1') ? 0 : 1;
-    }
+    // RENET_SOFTMAX_ROWS=1: one row per workgroup (the first planes writer), for A/B runs
+    static const bool rows4 = !renet_env_flag("RENET_SOFTMAX_ROWS", false);
     if (aligned && rows4 && C >= 2048 && ld16 <= 12 * 2048 && (reinterpret_cast<uintptr_t>(dl_planes) & 15) == 0 &&
         (plane & 7) == 0) {
         const int quads = (B + 3) / 4;

@@ -365,12 +365,7 @@ int renet_step_backward(const RenetStepModel* mp, const RenetStepBatch* bp, cons
         CK(renet_gru_bwd_layouts(2, dhl, so, ls, D, whh, sv, dgi, dgh, F(L.gru_ws), L.gru_ws_bytes, s.main));
     }
     // The parameter gradients of both encoders (~0.4 ms of chip-filling GEMMs that feed only the optimizer) run on the side
-    // stream; RENET_STEP_LATE_FORK=1 forks them behind the dX GEMMs instead of in front (A/B: profiles/r06_d_step_plan.md).
-    static int late_fork = -1;
-    if (late_fork < 0) {
-        const char* e_ = getenv("RENET_STEP_LATE_FORK");
-        late_fork = (e_ && e_[0] == '1') ? 1 : 0;
-    }
+    // stream, forked in front of the dX GEMMs (behind them: 1 % slower, profiles/r06_d_step_plan.md).
     auto gru_param_grads = [&]() -> int {
         const float* xs[2] = {F(L.X), F(L.Xr)};
         const int in[2] = {4 * D, 3 * D};
@@ -391,7 +386,7 @@ int renet_step_backward(const RenetStepModel* mp, const RenetStepBatch* bp, cons
         if (!ev_gru_done) return 0;
         return (int)hipEventRecord((hipEvent_t)ev_gru_done, s.side);
     };
-    if (!late_fork) {
+    {
         s.fork();
         int rc_ = gru_param_grads();
         if (!rc_) rc_ = gru_done();
@@ -400,12 +395,6 @@ int renet_step_backward(const RenetStepModel* mp, const RenetStepBatch* bp, cons
     // dX: only the columns the sequence assembly reads (the trailing D columns are the constant global embedding)
     CK(gemm(s.main, wsm, L.gemm_ws_bytes, 0, 0, S, 3 * D, 3 * D, F(L.dgi0), 3 * D, m.wih, 4 * D, 0.f, F(L.dX), 4 * D, nullptr));
     CK(gemm(s.main, wsm, L.gemm_ws_bytes, 0, 0, S, 2 * D, 3 * D, F(L.dgi1), 3 * D, m.wih_r, 3 * D, 0.f, F(L.dXr), 3 * D, nullptr));
-    if (late_fork) {
-        s.fork();
-        int rc_ = gru_param_grads();
-        if (!rc_) rc_ = gru_done();
-        if (rc_) return rc_;
-    }
 
     // ---- ops.SeqAssembleFn.backward
     CK(renet_seq_assemble_bwd(F(L.dX), F(L.dXr), b.step_off, b.L, S, B, D, p, r->seed_x, r->seed_xr, F(L.d_rows), F(L.d_ent_seq),

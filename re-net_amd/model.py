@@ -22,10 +22,6 @@ import renet_hip as K
 from Aggregator import RGCNAggregator
 from utils import *        # noqa: F401,F403  (the reference's model.py re-exports utils the same way)
 
-# both score heads of a pass as one autograd Function (ops.DualHeadCEFn: the relation head on a second stream);
-# RENET_DUAL_HEAD=0 keeps the two ops.HeadCEFn calls
-DUAL_HEAD = os.environ.get('RENET_DUAL_HEAD', '1') != '0'
-
 
 def _moded(fn):
     """Runs a model method inside the model's own GEMM-mode scope (`self.gemm_mode`: None = the process default,
@@ -283,7 +279,7 @@ class RENet(nn.Module):
         self.aggregator.last_batch = g
         # the same launch sequence issued from C (csrc/step.cpp): two C-ABI calls per step instead of ~55; bit-identical
         import step_plan
-        if DUAL_HEAD and step_plan.eligible(self, prep):
+        if step_plan.eligible(self, prep):
             return step_plan.StepFn.apply(self, prep, row_tap, *step_plan.model_params(self))
         # a shard of a batch whose graph every rank replicates (prepare_both(shard=...)): rank-independent dropout
         # masks at the graph-side sites, so that the N-rank step equals the 1-rank step
@@ -298,17 +294,11 @@ class RENet(nn.Module):
         # data-parallel split) contributes share x that, so that the ranks' losses and gradients SUM to the batch's
         scale = 2.0 * getattr(prep, 'share', 1.0)
         seed1, seed2 = (ops.next_seed(), ops.next_seed()) if p > 0 else (0, 0)
-        if DUAL_HEAD:
-            return ops.DualHeadCEFn.apply(self.ent_embeds, prep.s_idx, s_h, self.rel_embeds, prep.r_idx,
-                                          self.linear.weight, self.linear.bias, prep.o_idx, s_q,
-                                          self.linear_r.weight, self.linear_r.bias, prep.r_label, prep.plan_s,
-                                          prep.plan_r, p, seed1, seed2, scale, 0.1, row_tap)
-        loss_sub = ops.HeadCEFn.apply(self.ent_embeds, prep.s_idx, s_h, self.rel_embeds, prep.r_idx,
-                                      self.linear.weight, self.linear.bias, prep.o_idx, prep.plan_s,
-                                      prep.plan_r, p, seed1, scale)
-        loss_r = ops.HeadCEFn.apply(self.ent_embeds, prep.s_idx, s_q, None, None, self.linear_r.weight,
-                                    self.linear_r.bias, prep.r_label, prep.plan_s, None, p, seed2, scale)
-        return loss_sub + 0.1 * loss_r
+        # both score heads as one autograd Function (ops.DualHeadCEFn: the relation head on a second stream)
+        return ops.DualHeadCEFn.apply(self.ent_embeds, prep.s_idx, s_h, self.rel_embeds, prep.r_idx,
+                                      self.linear.weight, self.linear.bias, prep.o_idx, s_q,
+                                      self.linear_r.weight, self.linear_r.bias, prep.r_label, prep.plan_s,
+                                      prep.plan_r, p, seed1, seed2, scale, 0.1, row_tap)
 
     def prepare(self, triplets, hist, graph_dict, subject=True):
         """Host + upload half of one direction of a training step: batch graph, packed layout and plans,
@@ -323,17 +313,10 @@ class RENet(nn.Module):
         rel_embeds = self.rel_embeds[:self.num_rels] if subject else self.rel_embeds[self.num_rels:]
         p = self.drop_p if self.training else 0.0
         seed1, seed2 = (ops.next_seed(), ops.next_seed()) if p > 0 else (0, 0)
-        if DUAL_HEAD:                                                                     # model.py:89-103
-            return ops.DualHeadCEFn.apply(self.ent_embeds, prep.s_idx, s_h, rel_embeds, prep.r_idx,
-                                          self.linear.weight, self.linear.bias, prep.o_idx, s_q,
-                                          self.linear_r.weight, self.linear_r.bias, prep.r_idx, prep.plan_s,
-                                          prep.plan_r, p, seed1, seed2, 1.0, 0.1)
-        loss_sub = ops.HeadCEFn.apply(self.ent_embeds, prep.s_idx, s_h, rel_embeds, prep.r_idx,
-                                      self.linear.weight, self.linear.bias, prep.o_idx, prep.plan_s,
-                                      prep.plan_r, p, seed1)                              # model.py:89-91
-        loss_r = ops.HeadCEFn.apply(self.ent_embeds, prep.s_idx, s_q, None, None, self.linear_r.weight,
-                                    self.linear_r.bias, prep.r_idx, prep.plan_s, None, p, seed2)   # model.py:98-100
-        return loss_sub + 0.1 * loss_r                                                    # model.py:103
+        return ops.DualHeadCEFn.apply(self.ent_embeds, prep.s_idx, s_h, rel_embeds, prep.r_idx,      # model.py:89-103
+                                      self.linear.weight, self.linear.bias, prep.o_idx, s_q,
+                                      self.linear_r.weight, self.linear_r.bias, prep.r_idx, prep.plan_s,
+                                      prep.plan_r, p, seed1, seed2, 1.0, 0.1)
 
     def _encode(self, prep):
         rel_embeds = self.rel_embeds[:self.num_rels] if prep.subject else self.rel_embeds[self.num_rels:]
@@ -382,7 +365,7 @@ class RENet(nn.Module):
         list layout, or graph.FlatHistory objects."""
         if not torch.is_grad_enabled():
             self._fused_pending = None                 # (a no_grad forward between the two calls of a fused step: start over)
-        if self.fuse_directions and self.training and torch.is_grad_enabled() and DUAL_HEAD:
+        if self.fuse_directions and self.training and torch.is_grad_enabled():
             out = self._forward_fused(triplets, s_hist, o_hist, graph_dict, subject)
             if out is not None:
                 return out

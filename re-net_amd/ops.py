@@ -664,7 +664,7 @@ def _head_forward(a, ia, hmid, c, ic, weight, bias, target, drop_p, seed, grad_s
     if need_grad and debug_tap is None and K.use_planes(weight, weight.shape[0]):
         # PLANES path (round 6, the entity head): every operand of the head's three GEMMs is split into its bf16 terms ONCE
         # -- the weight per optimizer step, feat here, the CE gradient by the kernel that computes it -- and the GEMMs run
-        # without conversion work (csrc/gemm_p6.h).  The fp32 logits live in a scratch buffer with 16-byte aligned rows
+        # without conversion work (csrc/gemm_planes.hip).  The fp32 logits live in a scratch buffer with 16-byte aligned rows
         # and are dropped after the loss; no fp32 copy of the gradient exists.
         b_, c_ = feat.shape[0], weight.shape[0]
         w_pl = K.weight_planes(weight)

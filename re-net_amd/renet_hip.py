@@ -568,7 +568,7 @@ def auto_split_k(m, n, k):
 # 'bf16x6' : fp32 operands split into 3 bf16 terms, 6 term products on v_mfma_f32_32x32x16_bf16 with fp32
 #            accumulation (gemm_split.hip): fp32-class accuracy at 2.67x the matrix-pipe rate
 # 'f16x3'  : fp32 operands, scaled per TENSOR by a power of two, split into 2 binary16 terms (22 significant bits),
-#            3 term products on v_mfma_f32_32x32x16_f16 (gemm_h3.h): GEMM errors within a small multiple of fp32's
+#            3 term products on v_mfma_f32_32x32x16_f16 (gemm_h3.hip): GEMM errors within a small multiple of fp32's
 #            own accumulation error (include/renet_hip.h), half the matrix instructions of bf16x6
 # Default since round 4: 'bf16x6', the 24-bit split (fp32-class: every operand bit enters the product).  'f16x3' (22-bit
 # operands, the round-3 default) is the opt-in FAST mode, 'f32' the exact-product mode; bench.py reports all three.
@@ -690,7 +690,7 @@ def _as_bf16(x):
 # The entity score head's three GEMMs (logits, dfeat, dW: 2/3 of the step's GEMM flops) re-split every operand element
 # once per output tile that reads it (csrc/gemm_split.hip); here a tensor is split ONCE, by the kernel that produces it
 # (softmax_ce_planes: the CE gradient; HipAdam: the head weight; pack_planes: the features), and the GEMM
-# (csrc/gemm_p6.h) stages the planes by LDS-DMA with no conversion work in its k-loop.  Same arithmetic (three RNE terms,
+# (csrc/gemm_planes.hip) stages the planes by LDS-DMA with no conversion work in its k-loop.  Same arithmetic (three RNE terms,
 # six products, fp32 accumulation) as the in-loop split.  RENET_PLANES=0 keeps the in-loop split everywhere.
 PLANES = os.environ.get('RENET_PLANES', '1') != '0'
 PLANES_MIN_CLASSES = int(os.environ.get('RENET_PLANES_MIN_CLASSES', '2048'))
@@ -698,7 +698,7 @@ PLANES_MIN_CLASSES = int(os.environ.get('RENET_PLANES_MIN_CLASSES', '2048'))
 
 class PlanesMat(object):
     """A matrix [R, C] as three bf16 planes in ONE tensor p [3, Rp, Cp] (Rp, Cp multiples of 256, zero padding).  The
-    elements of a plane are NOT row-major: they are stored in the T16 tile format of csrc/gemm_p6.h (16 x 16 tiles of 512
+    elements of a plane are NOT row-major: they are stored in the T16 tile format of csrc/gemm_planes.hip (16 x 16 tiles of 512
     bytes; csrc/common.h renet_t16_off, tools/p6_layout_sim.py) -- p's trailing two dimensions only size the buffer;
     planes_to_dense() gives the row-major view (tests)."""
     __slots__ = ('p', 'R', 'C')

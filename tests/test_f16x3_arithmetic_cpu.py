@@ -1,4 +1,4 @@
-"""The arithmetic of the f16x3 GEMM (re-net_amd/csrc/gemm_h3.h) restated in numpy -- TEST INFRASTRUCTURE, CPU only:
+"""The arithmetic of the f16x3 GEMM (re-net_amd/csrc/gemm_h3.hip) restated in numpy -- TEST INFRASTRUCTURE, CPU only:
 tensor scale from a magnitude bound, two binary16 planes per operand, three exact f16 x f16 products accumulated in
 fp32, cross terms scaled by 2^-11 once.  Checks the error claims the header makes, independently of any GPU: every
 element is represented to 2^-22 relative (two 11-bit significands) at any tensor magnitude, GEMM results stay in the

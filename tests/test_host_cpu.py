@@ -402,7 +402,7 @@ def test_ctypes_signatures_match_the_header():
 
 
 def _tile_of_block(L, nbx, nby, panel=8, nbz=1):
-    """Python restatement of tile_of_block (csrc/gemm_split.hip): linear dispatch index (x fastest, then y, then z) ->
+    """Python restatement of tile_of_block (csrc/gemm_tiles.h): linear dispatch index (x fastest, then y, then z) ->
     (bx, by) for nbz == 1, (bx, by, bz) for split-K grids."""
     nb = nbx * nby
     if nbz == 1:
@@ -426,7 +426,7 @@ def test_gemm_virtual_tile_order_is_a_bijection():
     """The XCD-aware tile order of the bf16x6 GEMM must visit every tile exactly once for every grid shape (the
     formula here mirrors the device code line by line; the GPU tests cover a handful of shapes, this covers all
     small ones), and consecutive workgroups of one XCD must share a slab of the long operand."""
-    src = open(os.path.join(ROOT, 're-net_amd', 'csrc', 'gemm_split.hip')).read()
+    src = open(os.path.join(ROOT, 're-net_amd', 'csrc', 'gemm_tiles.h')).read()
     for frag in ('(L & 7) * per + (L >> 3)', 'const int w = min(ns, xcd_order);', 'const int wp = min(w, ns - p * w);',
                  'const int l = r / wp, sh = p * w + (r - l * wp);', '(L3 & 7) * per3 + (L3 >> 3)',
                  'const int L3 = blockIdx.x + nbx * (blockIdx.y + nby * blockIdx.z);', 'bz = v / nb;'):

@@ -1,6 +1,6 @@
 """CPU model of the planes GEMM's data path (tools/p6_layout_sim.py): the T16 plane format -> LDS-DMA pieces -> LDS image
 -> MFMA fragments, for both consumer roles, and the LDS bank-conflict count of the fragment reads.  No GPU needed: the
-model is the specification the kernel (csrc/gemm_p6.h) and the producers (renet_pack_planes, renet_softmax_ce_planes)
+model is the specification the kernel (csrc/gemm_planes.hip) and the producers (renet_pack_planes, renet_softmax_ce_planes)
 implement; the GPU tests (tests/test_gpu_planes.py) check the kernels against fp64 products."""
 import os
 import sys

@@ -22,7 +22,7 @@ SHAPES = ['2048,23033,600,0,1', '2048,600,23033,0,0,6', '23033,600,2048,1,0', '1
 
 def build(only=None):
     os.makedirs(OUT, exist_ok=True)
-    src = [os.path.join(ROOT, 're-net_amd', 'csrc', f) for f in ('gemm_split.hip', 'gemm.hip', 'gemm_skinny.hip')]
+    src = [os.path.join(ROOT, 're-net_amd', 'csrc', f) for f in ('gemm_split.hip', 'gemm_h3.hip', 'gemm.hip', 'gemm_skinny.hip')]
     procs = []
     for name, flags in VARIANTS.items():
         if only and name not in only:

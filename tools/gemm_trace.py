@@ -19,7 +19,7 @@ BLOCKS, STEPS = 64, 320
 
 def build():
     os.makedirs(OUT, exist_ok=True)
-    src = [os.path.join(ROOT, 're-net_amd', 'csrc', f) for f in ('gemm_split.hip', 'gemm.hip', 'gemm_skinny.hip')]
+    src = [os.path.join(ROOT, 're-net_amd', 'csrc', f) for f in ('gemm_split.hip', 'gemm_h3.hip', 'gemm.hip', 'gemm_skinny.hip')]
     extra = sys.argv[2:]
     cmd = ['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared',
            '-DRENET_GEMM_TRACE', '-I' + os.path.join(ROOT, 'include')] + src + ['-o', LIB] + extra

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""CPU model of the planes GEMM's data movement (csrc/gemm_p6.h): the T16 tiled plane format in HBM -> the 1 KB LDS-DMA
+"""CPU model of the planes GEMM's data movement (csrc/gemm_planes.hip): the T16 tiled plane format in HBM -> the 1 KB LDS-DMA
 pieces -> the half-stage image in LDS -> the MFMA fragments read with ds_read_b128 (K-contiguous role) or
 ds_read_b64_tr_b16 (K-strided role).  Checks (a) that every lane of every fragment receives the matrix element the
 32x32x16 MFMA layout expects, for both roles, and (b) LDS bank conflicts of the fragment reads against the lane groups of

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Ablation builds of the planes GEMM (csrc/gemm_p6.h): probe libraries with one component of its k-loop removed, built
+"""Ablation builds of the planes GEMM (csrc/gemm_planes.hip): probe libraries with one component of its k-loop removed, built
 into tools/_trace/ (git-ignored, shipped to the GPU box) and selected with RENET_HIP_LIB.  `python tools/p6_probe.py build`
 here; on the GPU box `RENET_HIP_LIB=tools/_trace/p6_nodma.so python tools/planes_bench.py`."""
 import os
@@ -19,12 +19,12 @@ def build(extra=None):
     variants = dict(VARIANTS)
     if extra:
         variants = {k: v for k, v in variants.items() if k in extra}
-    others = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith('.o') and f != 'gemm_split.o']
+    others = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith('.o') and f != 'gemm_planes.o']
     procs = []
     for name, flags in variants.items():
         obj = os.path.join(OUT, 'p6_%s.o' % name)
         cmd = [HIPCC, '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-function'] + flags + \
-            ['-c', os.path.join(CSRC, 'gemm_split.hip'), '-o', obj]
+            ['-c', os.path.join(CSRC, 'gemm_planes.hip'), '-o', obj]
         procs.append((name, obj, subprocess.Popen(cmd)))
     for name, obj, p in procs:
         if p.wait() != 0:

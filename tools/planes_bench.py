@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Times the planes GEMM (csrc/gemm_p6.h) against the in-loop-split bf16x6 kernels on the entity score head's three GEMMs
+"""Times the planes GEMM (csrc/gemm_planes.hip) against the in-loop-split bf16x6 kernels on the entity score head's three GEMMs
 of the ICEWS18-shaped merged step (and a square reference shape), plus the producers (pack_planes, softmax_ce_planes vs
 softmax_ce).  GPU only.  Usage: python tools/planes_bench.py [--iters 20]"""
 import argparse

@@ -1,4 +1,4 @@
-// f16x3 operand split (gemm_h3.h store_items_h): the compiler's sequence (v_pk_mul, v_cvt_pk_f16_f32, 2 x v_cvt_f32_f16,
+// f16x3 operand split (gemm_h3.hip store_items_h): the compiler's sequence (v_pk_mul, v_cvt_pk_f16_f32, 2 x v_cvt_f32_f16,
 // v_pk_fma, v_cvt_pk_f16_f32 per PAIR = 14 VALU per 4 elements) against a v_fma_mix formulation (h1 = mixlo/mixhi(x s),
 // r = fma_mix_f32(x, s, -h1), h2 = mixlo/mixhi(r * 2048): 12 per 4 elements, no conversions back to f32).
 // Prints whether the two agree bit for bit and the s_memtime ticks per 4 elements of each (one wave, registers only).
