@@ -562,6 +562,7 @@ typedef struct {
     int32_t* plan_target[4];
     int32_t* counts;                           /* [RENET_BB_NCOUNTS] */
     int cap_nodes, cap_edges;
+    int32_t* seg_ptr;                          /* [G + 1] node offsets of the member graphs: renet_build_full_graphs only */
 } RenetBatchOut;
 
 enum {
@@ -578,6 +579,30 @@ size_t renet_build_batch_workspace(const RenetStoreDev* store, int B, int cap_no
 int renet_build_batch_both(const RenetStoreDev* store, const int32_t* idx_dev, int B, int seq_len, int heavy_thresh,
                            int group_budget, int chunk, const RenetBatchOut* out, void* workspace,
                            size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * DEVICE builder for the FULL-GRAPH batches of the global model (graph.build_full_graphs; reference Aggregator.py:44-55 /
+ * 87-98: dgl.batch of the whole graphs of a list of timestamps).  Resident: the per-timestamp node lists and the facts with
+ * LOCAL endpoints (graph.TimeGraph.ent / ls / r / lo, concatenated in graph_dict order).  tidx_dev[G] (device int32,
+ * G <= 1024) indexes that order; a repeated index gives two member graphs.  Fills, of RenetBatchOut: seg_ptr, node_ent,
+ * row_ptr, col, etype, norm, heavy_rows, e_src, e_dst, chunk_ptr, chunk_type, type_chunk_ptr, it_src, it_type, grp_ptr,
+ * plan_*[0] and counts -- bit for bit the arrays of graph.build_full_graphs (tests/test_gpu_full_graph_builder.py).  There is
+ * no row prefix (nA = N, n_groups_out = n_groups): node_slot, the *2 arrays, the sequence arrays and plans 1-3 are not
+ * touched.  Same protocol as renet_build_batch_both: no host synchronisation, stages launch over the capacities and guard
+ * on counts; N > cap_nodes / E > cap_edges set RENET_BB_ERR_NODES / _EDGES, an index outside [0, T) RENET_BB_ERR_TIME, and
+ * the batch is then EMPTY (N = E = 0).  N and E follow from node_ptr / trip_ptr, so a caller can size the buffers exactly. */
+typedef struct {
+    const int32_t* node_ptr;                   /* [T + 1] node range of every timestamp                               */
+    const int32_t* node_ent_all;               /* [n_nodes] entity of every node (sorted inside a timestamp)          */
+    const int32_t* trip_ptr;                   /* [T + 1] fact range of every timestamp                               */
+    const int32_t *trip_ls, *trip_r, *trip_lo; /* [n_facts] local subject, relation, local object                     */
+    int T, n_nodes, n_facts, num_ent, num_rels;
+} RenetFullStoreDev;
+
+size_t renet_build_full_graphs_workspace(const RenetFullStoreDev* store, int G, int cap_nodes, int cap_edges);
+int renet_build_full_graphs(const RenetFullStoreDev* store, const int32_t* tidx_dev, int G, int heavy_thresh,
+                            int group_items, int chunk, RenetBatchOut* out, void* workspace, size_t workspace_bytes,
+                            void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * THE MERGED TRAINING STEP AS ONE LAUNCH LIST (round 6; csrc/step.cpp): one iteration of train.py:136-139 --

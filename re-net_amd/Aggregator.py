@@ -9,6 +9,8 @@ What differs from the reference internally (results are the same):
     one kernel that writes the PackedSequence data directly (time-major), dropout fused;
   * the length sort is computed once (stable) and shared with the caller through `last_batch`.
 """
+import os
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -177,17 +179,35 @@ class RGCNAggregator_global(nn.Module):
                                dropout=dropout)
         self.rgcn2 = RGCNLayer(h_dim, h_dim, 2 * num_rels, num_bases, activation=None, self_loop=True,
                                dropout=dropout)
+        # build the full-graph batch on the device (gpu_builder.FullGraphBatch)?  None = follow RENET_GLOBAL_DEVICE_BUILDER
+        # (default off); True / False = this model's own choice
+        self.device_builder = None
+
+    def _full_graphs(self, times, ent_embeds, graph_dict):
+        """The batch graph of the full graphs of `times`: from the device builder when it is switched on and the model is on a
+        GPU -- the same arrays, bit for bit -- else from the host builder.  The device builder takes 1 .. 1024 member graphs
+        per batch; anything else stays with the host builder."""
+        on = self.device_builder
+        if on is None:
+            on = os.environ.get('RENET_GLOBAL_DEVICE_BUILDER', '0') == '1'
+        if on and ent_embeds.is_cuda:
+            import gpu_builder
+            if 0 < len(times) <= gpu_builder.MAX_FULL_GRAPHS:
+                fs = gpu_builder.full_graph_store_for(graph_dict, self.num_rels, ent_embeds.device)
+                g = gpu_builder.FullGraphBatch(fs, fs.store.index_of(np.asarray(times, dtype=np.int64)))
+                g.finalize()
+                return g
+        return G.DeviceGraph(G.build_full_graphs(graph_dict, times), ent_embeds.device)
 
     def pooled(self, times, ent_embeds, graph_dict, reverse):
         """Batch the FULL graphs of `times`, two RGCN layers, per-graph max/mean readout
         (Aggregator.py:44-61 / 87-105) -> [len(times), h]."""
-        hb = G.build_full_graphs(graph_dict, times)
-        g = G.DeviceGraph(hb, ent_embeds.device)
+        g = self._full_graphs(times, ent_embeds, graph_dict)
         g.ndata['h'] = ops.TableRows(ent_embeds, g.node_ent, g.plan_node_ent)               # deferred gather
         self.rgcn1(g, reverse)
         self.rgcn2(g, reverse)
         h2 = g.ndata.pop('h')
-        return ops.SegmentPoolFn.apply(h2, g.seg_ptr, hb.G, 1 if self.maxpool == 1 else 0)
+        return ops.SegmentPoolFn.apply(h2, g.seg_ptr, g.G, 1 if self.maxpool == 1 else 0)
 
     def forward(self, t_list, ent_embeds, graph_dict, reverse):
         """Aggregator.py:27-73.  t_list: timestamps sorted descending (global_model.py:45); zeros (no

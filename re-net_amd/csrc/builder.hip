@@ -9,6 +9,9 @@
 // every stage launches over a capacity and guards on device-side counts.  Output = the arrays of graph.HostBatch,
 // bit for bit (tests/test_gpu_builder.py compares every array with the host builder's).
 // Integer / index work: rocPRIM radix sorts and scans + small hand-written kernels; HBM-bound, no MFMA.
+// Second entry, renet_build_full_graphs: the global model's batches of FULL graphs (graph.build_full_graphs).  Its front
+// (fg_* kernels) only concatenates resident per-timestamp graphs; everything behind the edge list is build_tail, shared
+// with renet_build_batch_both.
 #include <cstring>
 #include "common.h"
 #include <rocprim/rocprim.hpp>
@@ -477,6 +480,7 @@ __global__ __launch_bounds__(256) void bb_apply_orders_kernel(const int32_t* __r
         col[i] = src[a]; etype[i] = et[a];
         e_src[i] = src[b]; e_dst[i] = dst[b];
     }
+    if (!e_src2) return;                                   // (full-graph batches have no row prefix)
     const int E_out = row_ptr[counts[RENET_BB_NA]];
     if (i < E_out) { const int c = ord_t2[i]; e_src2[i] = src[c]; e_dst2[i] = dst[c]; }
 }
@@ -630,6 +634,118 @@ __global__ void bb_finish_kernel(const int32_t* __restrict__ row_ptr, const int3
     if (t == 0) counts[RENET_BB_EOUT] = row_ptr[counts[RENET_BB_NA]];
 }
 
+// ================================================================================================================
+// FULL-GRAPH batches of the global model (graph.build_full_graphs; reference Aggregator.py:44-55 / 87-98: dgl.batch of
+// the whole graphs of a list of timestamps).  Nothing is induced or renumbered here: the per-timestamp node lists and
+// LOCAL fact endpoints are resident (RenetFullStoreDev), member graph k is the graph of timestamp index tidx[k] shifted
+// by the node offset of k.  Three front kernels leave the edge list where the shared tail (build_tail) expects it.
+struct FullStore {
+    const int32_t* node_ptr;
+    const int32_t* node_ent_all;
+    const int32_t* trip_ptr;
+    const int32_t *trip_ls, *trip_r, *trip_lo;
+    int T, num_rels;
+};
+
+// ---- full-graph stage A (ONE workgroup, G <= 1024): node / fact counts of the member graphs and their scans --------
+__global__ __launch_bounds__(1024) void fg_counts_kernel(FullStore st, const int32_t* __restrict__ tidx, int G, int cap_nodes,
+                                                         int cap_edges, int32_t* __restrict__ gti, int32_t* __restrict__ seg_ptr,
+                                                         int32_t* __restrict__ fact_off, int32_t* __restrict__ counts) {
+    __shared__ int wsum[16];
+    __shared__ int s_bad;
+    const int k = threadIdx.x;
+    if (k == 0) s_bad = 0;
+    __syncthreads();
+    int ti = -1, nn = 0, nf = 0;
+    if (k < G) {
+        ti = tidx[k];
+        if (ti < 0 || ti >= st.T) { ti = -1; s_bad = 1; }            // (not a timestamp of the store: an empty member graph)
+        else { nn = st.node_ptr[ti + 1] - st.node_ptr[ti]; nf = st.trip_ptr[ti + 1] - st.trip_ptr[ti]; }
+        gti[k] = ti;
+    }
+    int N, F;
+    const int noff = block_excl_scan_1024(nn, &N, wsum);
+    const int foff = block_excl_scan_1024(nf, &F, wsum);               // (its first barrier also publishes s_bad)
+    int e = s_bad ? RENET_BB_ERR_TIME : 0;
+    if (N > cap_nodes) e |= RENET_BB_ERR_NODES;
+    if (2 * (long long)F > cap_edges) e |= RENET_BB_ERR_EDGES;
+    if (k < G) { seg_ptr[k] = noff; fact_off[k] = foff; }
+    if (k == 0) {
+        seg_ptr[G] = N; fact_off[G] = F;
+        if (e) { N = 0; F = 0; }                                       // every later stage then sees an EMPTY graph (no OOB access)
+        counts[RENET_BB_ERR] = e;
+        counts[RENET_BB_TB] = G;
+        counts[RENET_BB_N] = N; counts[RENET_BB_NA] = N;
+        counts[RENET_BB_FACTS] = F; counts[RENET_BB_E2] = F; counts[RENET_BB_E] = 2 * F; counts[RENET_BB_EOUT] = 2 * F;
+    }
+}
+
+// last k in [0, G) with off[k] <= v (off non-decreasing, off[0] = 0 <= v; member graphs may be empty)
+__device__ __forceinline__ int last_le_i32(const int32_t* off, int G, int v) {
+    int lo = 0, hi = G;
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (off[mid] <= v) lo = mid; else hi = mid; }
+    return lo;
+}
+
+// ---- full-graph stage B: node_ent = ragged copy of the member graphs' node lists ----------------------------------------
+__global__ __launch_bounds__(256) void fg_nodes_kernel(FullStore st, const int32_t* __restrict__ counts, int G, int cap_nodes,
+                                                       const int32_t* __restrict__ gti, const int32_t* __restrict__ seg_ptr,
+                                                       int32_t* __restrict__ node_ent) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= cap_nodes || v >= counts[RENET_BB_N]) return;
+    const int k = last_le_i32(seg_ptr, G, v);
+    node_ent[v] = st.node_ent_all[st.node_ptr[gti[k]] + (v - seg_ptr[k])];
+}
+
+// ---- full-graph stage C: the edge list, in the order of graph.build_full_graphs' concatenation: member graph k owns
+// positions [2 fact_off[k], 2 fact_off[k + 1]): first ls -> lo with type r for all its facts, then lo -> ls with type
+// r + R (graph.TimeGraph.edges; the halves are per GRAPH).  Also what bb_expand_kernel leaves for the tail: the sort
+// keys (sentinels behind E), iota, the in-degrees and the relation histogram.
+__global__ __launch_bounds__(256) void fg_edges_kernel(FullStore st, const int32_t* __restrict__ counts, int G, int cap_edges,
+                                                       int key_bits, const int32_t* __restrict__ gti,
+                                                       const int32_t* __restrict__ seg_ptr, const int32_t* __restrict__ fact_off,
+                                                       int32_t* __restrict__ src, int32_t* __restrict__ dst,
+                                                       int32_t* __restrict__ et, uint32_t* __restrict__ key_dt,
+                                                       uint32_t* __restrict__ key_t, int32_t* __restrict__ iota,
+                                                       int32_t* __restrict__ deg, int32_t* __restrict__ tc,
+                                                       int32_t* __restrict__ err) {
+    __shared__ int h1[1024];                               // (workgroup-local histogram, flushed once: see bb_expand_kernel)
+    const int T2 = 2 * st.num_rels;
+    for (int i = threadIdx.x; i < T2; i += blockDim.x) h1[i] = 0;
+    __syncthreads();
+    const int E = counts[RENET_BB_E], N = counts[RENET_BB_N];
+    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < cap_edges; e += gridDim.x * blockDim.x) {
+        iota[e] = e;
+        if (e >= E) {                                     // sentinels: sorted behind every valid key
+            key_dt[e] = 1u << key_bits;
+            key_t[e] = (uint32_t)T2;
+            continue;
+        }
+        const int k = last_le_i32(fact_off, G, e >> 1);    // 2 fact_off[k] <= e  <=>  fact_off[k] <= e / 2
+        const int f0 = fact_off[k], nf = fact_off[k + 1] - f0, off = seg_ptr[k];
+        const int local = e - 2 * f0, rev = local >= nf;
+        const int j = st.trip_ptr[gti[k]] + (rev ? local - nf : local);
+        const int a = st.trip_ls[j] + off, b = st.trip_lo[j] + off;
+        const int s = rev ? b : a, d = rev ? a : b;
+        const int t = st.trip_r[j] + (rev ? st.num_rels : 0);
+        if ((unsigned)d >= (unsigned)N || (unsigned)s >= (unsigned)N || (unsigned)t >= (unsigned)T2) {
+            // (the store is range-checked on the host; never index with a bad id all the same)
+            atomicOr(err, RENET_BB_ERR_EDGES);
+            src[e] = 0; dst[e] = 0; et[e] = 0;
+            key_dt[e] = 1u << key_bits; key_t[e] = (uint32_t)T2;
+            continue;
+        }
+        src[e] = s; dst[e] = d; et[e] = t;
+        key_dt[e] = (uint32_t)d * (uint32_t)T2 + (uint32_t)t;
+        key_t[e] = (uint32_t)t;
+        atomicAdd(&deg[d], 1);
+        atomicAdd(&h1[t], 1);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < T2; i += blockDim.x)
+        if (h1[i]) atomicAdd(&tc[i], h1[i]);
+}
+
 inline int bits_for(uint64_t v) { int b = 1; while (b < 63 && (1ull << b) <= v) ++b; return b; }
 
 #define BB_HIP(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return (int)e__; } while (0)
@@ -660,27 +776,9 @@ size_t rocprim_temp_bytes(int cap_nodes, int cap_edges, int cap_facts) {
     return (m + 255) & ~(size_t)255;
 }
 
-struct Bufs {
-    int32_t* seq_first;
-    int32_t* seq_len_s;
-    int32_t* seq_start;
-    int32_t* step_snap;
-    int32_t* step_dense;
-    int32_t* step_packed;
-    int32_t* slot_used;
-    int32_t* slot_of_dense;
-    int32_t* slot_ti;
-    int32_t* slot_group;
-    int32_t* fact_off;
-    uint32_t* table;
-    int32_t* new_id;
-    int2* tile_cnt;
-    int32_t* flag;
-    int32_t* pos;
-    int32_t* fslot;
-    int32_t* half_src;
-    int32_t* half_dst;
-    int32_t* half_et;
+// scratch of the shared tail (build_tail): everything from the edge list (src, dst, et, the sort keys, the in-degree and
+// relation histograms) to the outputs.  `pruned` = the batch has a row prefix [0, nA) with layouts of its own.
+struct TailBufs {
     int32_t* src;
     int32_t* dst;
     int32_t* et;
@@ -708,9 +806,64 @@ struct Bufs {
     uint32_t* pkey;
     int32_t* pflag;
     int32_t* ppos;
-    
+
     void* tmp;
     size_t tmp_bytes;
+    bool carve_tail(Carver& cv, int cap_nodes, int cap_edges, int cap_steps, int cap_facts, bool pruned) {
+        src = cv.take<int32_t>(cap_edges);
+        dst = cv.take<int32_t>(cap_edges);
+        et = cv.take<int32_t>(cap_edges);
+        key_dt = cv.take<uint32_t>(cap_edges);
+        key_t = cv.take<uint32_t>(cap_edges);
+        key_t2 = pruned ? cv.take<uint32_t>(cap_edges) : nullptr;
+        key_sorted = cv.take<uint32_t>(max(cap_edges, max(cap_nodes, cap_steps)));
+        iota = cv.take<int32_t>(max(cap_edges, max(cap_nodes, cap_steps)));
+        ord_dt = cv.take<int32_t>(cap_edges);
+        ord_t = cv.take<int32_t>(cap_edges);
+        ord_t2 = pruned ? cv.take<int32_t>(cap_edges) : nullptr;
+        deg = cv.take<int32_t>(cap_nodes + 2);
+        tc = cv.take<int32_t>(1024);
+        tc2 = pruned ? cv.take<int32_t>(1024) : nullptr;
+        heavy_flag = cv.take<int32_t>(cap_nodes + 2);
+        heavy_pos = cv.take<int32_t>(cap_nodes + 2);
+        item_cnt = cv.take<int32_t>(cap_nodes + 2);
+        item_start = cv.take<int32_t>(cap_nodes + 2);
+        light_id = cv.take<int32_t>(cap_nodes + 2);
+        prev_light = cv.take<int32_t>(cap_nodes + 2);
+        first_flag = cv.take<int32_t>(cap_nodes + 2);
+        first_pos = cv.take<int32_t>(cap_nodes + 2);
+        first_out = cv.take<int32_t>(cap_nodes + 2);
+        first_out_pos = pruned ? cv.take<int32_t>(cap_nodes + 2) : nullptr;
+        pkey = cv.take<uint32_t>(max(cap_nodes, cap_steps));
+        pflag = cv.take<int32_t>(max(cap_nodes, cap_steps) + 2);
+        ppos = cv.take<int32_t>(max(cap_nodes, cap_steps) + 2);
+        tmp_bytes = rocprim_temp_bytes(cap_nodes, cap_edges, cap_facts);
+        tmp = cv.take<char>(tmp_bytes);
+        return tmp != nullptr && cv.ok;
+    }
+};
+
+struct Bufs : TailBufs {
+    int32_t* seq_first;
+    int32_t* seq_len_s;
+    int32_t* seq_start;
+    int32_t* step_snap;
+    int32_t* step_dense;
+    int32_t* step_packed;
+    int32_t* slot_used;
+    int32_t* slot_of_dense;
+    int32_t* slot_ti;
+    int32_t* slot_group;
+    int32_t* fact_off;
+    uint32_t* table;
+    int32_t* new_id;
+    int2* tile_cnt;
+    int32_t* flag;
+    int32_t* pos;
+    int32_t* fslot;
+    int32_t* half_src;
+    int32_t* half_dst;
+    int32_t* half_et;
     // carves every scratch array out of `cv`; false if it does not fit
     bool carve(Carver& cv, const RenetStoreDev* sd, int B, int cap_nodes, int cap_edges) {
         const int cap_facts = 2 * sd->n_facts, cap_steps = 2 * B * BB_MAXL;
@@ -736,38 +889,100 @@ struct Bufs {
         half_src = cv.take<int32_t>(cap_edges / 2);
         half_dst = cv.take<int32_t>(cap_edges / 2);
         half_et = cv.take<int32_t>(cap_edges / 2);
-        src = cv.take<int32_t>(cap_edges);
-        dst = cv.take<int32_t>(cap_edges);
-        et = cv.take<int32_t>(cap_edges);
-        key_dt = cv.take<uint32_t>(cap_edges);
-        key_t = cv.take<uint32_t>(cap_edges);
-        key_t2 = cv.take<uint32_t>(cap_edges);
-        key_sorted = cv.take<uint32_t>(max(cap_edges, max(cap_nodes, cap_steps)));
-        iota = cv.take<int32_t>(max(cap_edges, max(cap_nodes, cap_steps)));
-        ord_dt = cv.take<int32_t>(cap_edges);
-        ord_t = cv.take<int32_t>(cap_edges);
-        ord_t2 = cv.take<int32_t>(cap_edges);
-        deg = cv.take<int32_t>(cap_nodes + 2);
-        tc = cv.take<int32_t>(1024);
-        tc2 = cv.take<int32_t>(1024);
-        heavy_flag = cv.take<int32_t>(cap_nodes + 2);
-        heavy_pos = cv.take<int32_t>(cap_nodes + 2);
-        item_cnt = cv.take<int32_t>(cap_nodes + 2);
-        item_start = cv.take<int32_t>(cap_nodes + 2);
-        light_id = cv.take<int32_t>(cap_nodes + 2);
-        prev_light = cv.take<int32_t>(cap_nodes + 2);
-        first_flag = cv.take<int32_t>(cap_nodes + 2);
-        first_pos = cv.take<int32_t>(cap_nodes + 2);
-        first_out = cv.take<int32_t>(cap_nodes + 2);
-        first_out_pos = cv.take<int32_t>(cap_nodes + 2);
-        pkey = cv.take<uint32_t>(max(cap_nodes, cap_steps));
-        pflag = cv.take<int32_t>(max(cap_nodes, cap_steps) + 2);
-        ppos = cv.take<int32_t>(max(cap_nodes, cap_steps) + 2);
-        tmp_bytes = rocprim_temp_bytes(cap_nodes, cap_edges, cap_facts);
-        tmp = cv.take<char>(tmp_bytes);
-        return tmp != nullptr && cv.ok;
+        return carve_tail(cv, cap_nodes, cap_edges, cap_steps, cap_facts, true);
     }
 };
+
+// scratch of the full-graph front (renet_build_full_graphs) + the tail
+struct FullBufs : TailBufs {
+    int32_t* gti;                  // [G] validated timestamp index of every member graph
+    int32_t* fact_off;             // [G + 1] scan of the fact counts
+    bool carve(Carver& cv, int G, int cap_nodes, int cap_edges) {
+        gti = cv.take<int32_t>(G);
+        fact_off = cv.take<int32_t>(G + 1);
+        return carve_tail(cv, cap_nodes, cap_edges, 0, 0, false);
+    }
+};
+
+// ---- the shared tail: stages F (sorts, rows, chunks), G (item stream, wave groups) and H (the first n_plans plans) over an
+// edge list that a front has left in bf.src / dst / et with its keys, bf.deg and the histograms.  pruned = false: the
+// batch has no row prefix (nA = N): the *2 lists, n_chunks2 and n_groups_out's own scan are not computed.
+int build_tail(const TailBufs& bf, const RenetBatchOut* out, int cap_nodes, int cap_edges, int cap_steps, int num_ent, int T2,
+               int key_bits, int heavy_thr, int group_budget, int chunk, int n_plans, int B, bool pruned, hipStream_t st) {
+    int32_t* counts = out->counts;
+    int32_t* err = counts + RENET_BB_ERR;
+    const int cap_chunks = cap_edges / chunk + T2 + 1;
+    size_t tb = bf.tmp_bytes;
+    BB_HIP(rocprim::radix_sort_pairs(bf.tmp, tb, bf.key_dt, bf.key_sorted, bf.iota, bf.ord_dt, (size_t)cap_edges, 0, key_bits + 1, st));
+    const int tbits = bits_for((uint64_t)T2) ;
+    tb = bf.tmp_bytes;
+    BB_HIP(rocprim::radix_sort_pairs(bf.tmp, tb, bf.key_t, bf.key_sorted, bf.iota, bf.ord_t, (size_t)cap_edges, 0, tbits, st));
+    if (pruned) {
+        tb = bf.tmp_bytes;
+        BB_HIP(rocprim::radix_sort_pairs(bf.tmp, tb, bf.key_t2, bf.key_sorted, bf.iota, bf.ord_t2, (size_t)cap_edges, 0, tbits, st));
+    }
+    // rows
+    tb = bf.tmp_bytes;
+    BB_HIP(rocprim::exclusive_scan(bf.tmp, tb, bf.deg, out->row_ptr, 0, (size_t)(cap_nodes + 1), rocprim::plus<int>(), st));
+    RENET_LAUNCH(bb_rows_kernel, dim3((cap_nodes + 1 + 255) / 256), dim3(256), 0, st, counts, cap_nodes, heavy_thr, bf.deg,
+                 out->norm, bf.heavy_flag, bf.item_cnt, bf.light_id);
+    RENET_LAUNCH_CHECK();
+    RENET_LAUNCH(bb_apply_orders_kernel, dim3((cap_edges + 255) / 256), dim3(256), 0, st, counts, cap_edges, bf.src, bf.dst, bf.et,
+                 bf.ord_dt, bf.ord_t, bf.ord_t2, out->row_ptr, out->col, out->etype, out->e_src, out->e_dst,
+                 pruned ? out->e_src2 : nullptr, pruned ? out->e_dst2 : nullptr);
+    RENET_LAUNCH_CHECK();
+    tb = bf.tmp_bytes;
+    BB_HIP(rocprim::exclusive_scan(bf.tmp, tb, bf.heavy_flag, bf.heavy_pos, 0, (size_t)(cap_nodes + 1), rocprim::plus<int>(), st));
+    RENET_LAUNCH(bb_heavy_kernel, dim3((cap_nodes + 255) / 256), dim3(256), 0, st, counts, counts, cap_nodes, bf.heavy_flag,
+                 bf.heavy_pos, out->heavy_rows);
+    RENET_LAUNCH_CHECK();
+    RENET_LAUNCH(bb_chunks_kernel, dim3(pruned ? 2 : 1), dim3(1024), 0, st, bf.tc, bf.tc2, T2, chunk, cap_chunks, out->type_chunk_ptr,
+                 out->type_chunk_ptr2, out->chunk_type, out->chunk_ptr, out->chunk_type2, out->chunk_ptr2, counts, err);
+    RENET_LAUNCH_CHECK();
+    // gather item plan
+    tb = bf.tmp_bytes;
+    BB_HIP(rocprim::exclusive_scan(bf.tmp, tb, bf.item_cnt, bf.item_start, 0, (size_t)(cap_nodes + 1), rocprim::plus<int>(), st));
+    tb = bf.tmp_bytes;
+    BB_HIP(rocprim::exclusive_scan(bf.tmp, tb, bf.light_id, bf.prev_light, -1, (size_t)(cap_nodes + 1), rocprim::maximum<int>(), st));
+    RENET_LAUNCH(bb_items_kernel, dim3((cap_nodes + 1 + 255) / 256), dim3(256), 0, st, counts, group_budget, out->row_ptr,
+                 out->col, out->etype, bf.item_cnt, bf.item_start, bf.prev_light, out->it_src, out->it_type, bf.first_flag, bf.first_out);
+    RENET_LAUNCH_CHECK();
+    tb = bf.tmp_bytes;
+    BB_HIP(rocprim::exclusive_scan(bf.tmp, tb, bf.first_flag, bf.first_pos, 0, (size_t)(cap_nodes + 1), rocprim::plus<int>(), st));
+    if (pruned) {
+        tb = bf.tmp_bytes;
+        BB_HIP(rocprim::exclusive_scan(bf.tmp, tb, bf.first_out, bf.first_out_pos, 0, (size_t)(cap_nodes + 1), rocprim::plus<int>(), st));
+    }
+    // (without a row prefix every group is a group of the prefix: first_out == first_flag, n_groups_out == n_groups)
+    RENET_LAUNCH(bb_groups_kernel, dim3((cap_nodes + 255) / 256), dim3(256), 0, st, counts, counts, cap_nodes, bf.first_flag,
+                 bf.first_pos, pruned ? bf.first_out_pos : bf.first_pos, pruned ? bf.first_out : bf.first_flag, bf.item_start,
+                 bf.item_cnt, out->grp_ptr);
+    RENET_LAUNCH_CHECK();
+    // segmented-add plans: 0 node_ent (N rows), 1 subj_row (S rows), 2 s_sorted (2B), 3 r_sorted (2B)
+    for (int pl = 0; pl < n_plans; ++pl) {
+        const int32_t* idx = pl == 0 ? out->node_ent : pl == 1 ? out->subj_row : pl == 2 ? out->s_sorted : out->r_sorted;
+        const int32_t* n_ptr = pl == 0 ? counts + RENET_BB_N : pl == 1 ? counts + RENET_BB_S : nullptr;
+        const int n_fixed = 2 * B;
+        const int cap = pl == 0 ? cap_nodes : pl == 1 ? cap_steps : 2 * B;
+        const uint64_t bound = pl == 0 ? (uint64_t)num_ent : pl == 1 ? (uint64_t)cap_nodes
+                               : pl == 2 ? (uint64_t)num_ent : (uint64_t)T2;
+        const int kb = bits_for(bound);
+        RENET_LAUNCH(bb_plan_keys_kernel, dim3((cap + 255) / 256), dim3(256), 0, st, idx, n_ptr, n_fixed, cap,
+                     (uint32_t)(1u << kb), bf.pkey, bf.iota);
+        RENET_LAUNCH_CHECK();
+        tb = bf.tmp_bytes;
+        BB_HIP(rocprim::radix_sort_pairs(bf.tmp, tb, bf.pkey, bf.key_sorted, bf.iota, out->plan_order[pl], (size_t)cap, 0, kb + 1, st));
+        RENET_LAUNCH(bb_plan_flags_kernel, dim3((cap + 1 + 255) / 256), dim3(256), 0, st, bf.key_sorted, n_ptr, n_fixed, cap,
+                     bf.pflag);
+        RENET_LAUNCH_CHECK();
+        tb = bf.tmp_bytes;
+        BB_HIP(rocprim::exclusive_scan(bf.tmp, tb, bf.pflag, bf.ppos, 0, (size_t)(cap + 1), rocprim::plus<int>(), st));
+        RENET_LAUNCH(bb_plan_segs_kernel, dim3((cap + 255) / 256), dim3(256), 0, st, bf.key_sorted, n_ptr, n_fixed, cap, bf.pflag,
+                     bf.ppos, out->plan_seg[pl], out->plan_target[pl], counts + RENET_BB_NSEG0 + pl);
+        RENET_LAUNCH_CHECK();
+    }
+    return RENET_OK;
+}
 
 }  // namespace
 
@@ -801,7 +1016,6 @@ int renet_build_batch_both(const RenetStoreDev* sd, const int32_t* idx_dev, int 
     const int T2 = 2 * sd->num_rels;
     const size_t entries_cap = (size_t)2 * sd->T * sd->num_ent;
     const int n_tiles = (int)((entries_cap + NUM_TILE - 1) / NUM_TILE);
-    const int cap_chunks = cap_edges / chunk + T2 + 1;
     if ((uint64_t)cap_nodes * T2 >= (1ull << 31)) return RENET_ERR_UNSUPPORTED;
     const int key_bits = bits_for((uint64_t)cap_nodes * T2);
 
@@ -855,72 +1069,59 @@ int renet_build_batch_both(const RenetStoreDev* sd, const int32_t* idx_dev, int 
     RENET_LAUNCH(bb_expand_kernel, dim3(min((cap_edges + 255) / 256, 1024)), dim3(256), 0, st, counts, sd->num_rels, cap_edges,
                  key_bits, bf.half_src, bf.half_dst, bf.half_et, bf.src, bf.dst, bf.et, bf.key_dt, bf.key_t, bf.key_t2, bf.iota, bf.deg, bf.tc, bf.tc2);
     RENET_LAUNCH_CHECK();
-    tb = bf.tmp_bytes;
-    BB_HIP(rocprim::radix_sort_pairs(bf.tmp, tb, bf.key_dt, bf.key_sorted, bf.iota, bf.ord_dt, (size_t)cap_edges, 0, key_bits + 1, st));
-    const int tbits = bits_for((uint64_t)T2) ;
-    tb = bf.tmp_bytes;
-    BB_HIP(rocprim::radix_sort_pairs(bf.tmp, tb, bf.key_t, bf.key_sorted, bf.iota, bf.ord_t, (size_t)cap_edges, 0, tbits, st));
-    tb = bf.tmp_bytes;
-    BB_HIP(rocprim::radix_sort_pairs(bf.tmp, tb, bf.key_t2, bf.key_sorted, bf.iota, bf.ord_t2, (size_t)cap_edges, 0, tbits, st));
-    // rows
-    tb = bf.tmp_bytes;
-    BB_HIP(rocprim::exclusive_scan(bf.tmp, tb, bf.deg, out->row_ptr, 0, (size_t)(cap_nodes + 1), rocprim::plus<int>(), st));
-    RENET_LAUNCH(bb_rows_kernel, dim3((cap_nodes + 1 + 255) / 256), dim3(256), 0, st, counts, cap_nodes, heavy_thr, bf.deg,
-                 out->norm, bf.heavy_flag, bf.item_cnt, bf.light_id);
-    RENET_LAUNCH_CHECK();
-    RENET_LAUNCH(bb_apply_orders_kernel, dim3((cap_edges + 255) / 256), dim3(256), 0, st, counts, cap_edges, bf.src, bf.dst, bf.et,
-                 bf.ord_dt, bf.ord_t, bf.ord_t2, out->row_ptr, out->col, out->etype, out->e_src, out->e_dst, out->e_src2,
-                 out->e_dst2);
-    RENET_LAUNCH_CHECK();
-    tb = bf.tmp_bytes;
-    BB_HIP(rocprim::exclusive_scan(bf.tmp, tb, bf.heavy_flag, bf.heavy_pos, 0, (size_t)(cap_nodes + 1), rocprim::plus<int>(), st));
-    RENET_LAUNCH(bb_heavy_kernel, dim3((cap_nodes + 255) / 256), dim3(256), 0, st, counts, counts, cap_nodes, bf.heavy_flag,
-                 bf.heavy_pos, out->heavy_rows);
-    RENET_LAUNCH_CHECK();
-    RENET_LAUNCH(bb_chunks_kernel, dim3(2), dim3(1024), 0, st, bf.tc, bf.tc2, T2, chunk, cap_chunks, out->type_chunk_ptr,
-                 out->type_chunk_ptr2, out->chunk_type, out->chunk_ptr, out->chunk_type2, out->chunk_ptr2, counts, err);
-    RENET_LAUNCH_CHECK();
-    // gather item plan
-    tb = bf.tmp_bytes;
-    BB_HIP(rocprim::exclusive_scan(bf.tmp, tb, bf.item_cnt, bf.item_start, 0, (size_t)(cap_nodes + 1), rocprim::plus<int>(), st));
-    tb = bf.tmp_bytes;
-    BB_HIP(rocprim::exclusive_scan(bf.tmp, tb, bf.light_id, bf.prev_light, -1, (size_t)(cap_nodes + 1), rocprim::maximum<int>(), st));
-    RENET_LAUNCH(bb_items_kernel, dim3((cap_nodes + 1 + 255) / 256), dim3(256), 0, st, counts, group_budget, out->row_ptr,
-                 out->col, out->etype, bf.item_cnt, bf.item_start, bf.prev_light, out->it_src, out->it_type, bf.first_flag, bf.first_out);
-    RENET_LAUNCH_CHECK();
-    tb = bf.tmp_bytes;
-    BB_HIP(rocprim::exclusive_scan(bf.tmp, tb, bf.first_flag, bf.first_pos, 0, (size_t)(cap_nodes + 1), rocprim::plus<int>(), st));
-    tb = bf.tmp_bytes;
-    BB_HIP(rocprim::exclusive_scan(bf.tmp, tb, bf.first_out, bf.first_out_pos, 0, (size_t)(cap_nodes + 1), rocprim::plus<int>(), st));
-    RENET_LAUNCH(bb_groups_kernel, dim3((cap_nodes + 255) / 256), dim3(256), 0, st, counts, counts, cap_nodes, bf.first_flag,
-                 bf.first_pos, bf.first_out_pos, bf.first_out, bf.item_start, bf.item_cnt, out->grp_ptr);
-    RENET_LAUNCH_CHECK();
-    // segmented-add plans: 0 node_ent (N rows), 1 subj_row (S rows), 2 s_sorted (2B), 3 r_sorted (2B)
-    for (int pl = 0; pl < 4; ++pl) {
-        const int32_t* idx = pl == 0 ? out->node_ent : pl == 1 ? out->subj_row : pl == 2 ? out->s_sorted : out->r_sorted;
-        const int32_t* n_ptr = pl == 0 ? counts + RENET_BB_N : pl == 1 ? counts + RENET_BB_S : nullptr;
-        const int n_fixed = 2 * B;
-        const int cap = pl == 0 ? cap_nodes : pl == 1 ? cap_steps : 2 * B;
-        const uint64_t bound = pl == 0 ? (uint64_t)sd->num_ent : pl == 1 ? (uint64_t)cap_nodes
-                               : pl == 2 ? (uint64_t)sd->num_ent : (uint64_t)T2;
-        const int kb = bits_for(bound);
-        RENET_LAUNCH(bb_plan_keys_kernel, dim3((cap + 255) / 256), dim3(256), 0, st, idx, n_ptr, n_fixed, cap,
-                     (uint32_t)(1u << kb), bf.pkey, bf.iota);
-        RENET_LAUNCH_CHECK();
-        tb = bf.tmp_bytes;
-        BB_HIP(rocprim::radix_sort_pairs(bf.tmp, tb, bf.pkey, bf.key_sorted, bf.iota, out->plan_order[pl], (size_t)cap, 0, kb + 1, st));
-        RENET_LAUNCH(bb_plan_flags_kernel, dim3((cap + 1 + 255) / 256), dim3(256), 0, st, bf.key_sorted, n_ptr, n_fixed, cap,
-                     bf.pflag);
-        RENET_LAUNCH_CHECK();
-        tb = bf.tmp_bytes;
-        BB_HIP(rocprim::exclusive_scan(bf.tmp, tb, bf.pflag, bf.ppos, 0, (size_t)(cap + 1), rocprim::plus<int>(), st));
-        RENET_LAUNCH(bb_plan_segs_kernel, dim3((cap + 255) / 256), dim3(256), 0, st, bf.key_sorted, n_ptr, n_fixed, cap, bf.pflag,
-                     bf.ppos, out->plan_seg[pl], out->plan_target[pl], counts + RENET_BB_NSEG0 + pl);
-        RENET_LAUNCH_CHECK();
-    }
+    const int rc = build_tail(bf, out, cap_nodes, cap_edges, cap_steps, sd->num_ent, T2, key_bits, heavy_thr, group_budget, chunk,
+                              4, B, true, st);
+    if (rc != RENET_OK) return rc;
     RENET_LAUNCH(bb_finish_kernel, dim3(1), dim3(64), 0, st, out->row_ptr, out->step_off, counts);
     RENET_LAUNCH_CHECK();
     return RENET_OK;
+}
+
+size_t renet_build_full_graphs_workspace(const RenetFullStoreDev* sd, int G, int cap_nodes, int cap_edges) {
+    if (!sd || G <= 0 || G > 1024 || cap_nodes <= 0 || cap_edges <= 0) return 0;
+    Carver dry{reinterpret_cast<char*>(256), ~(size_t)0 >> 2};          // never dereferenced
+    FullBufs b;
+    b.carve(dry, G, cap_nodes, max(cap_edges & ~1, 2));
+    return dry.used + 256;
+}
+
+int renet_build_full_graphs(const RenetFullStoreDev* sd, const int32_t* tidx_dev, int G, int heavy_thr, int group_items,
+                            int chunk, RenetBatchOut* out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!sd || !out || !tidx_dev || G <= 0 || G > 1024 || out->cap_nodes <= 0 || out->cap_edges <= 0 || !out->seg_ptr)
+        return RENET_ERR_BADARG;
+    if (2 * sd->num_rels > 1024 || sd->num_rels <= 0 || sd->T <= 0 || group_items + heavy_thr + 1 > 64 || chunk <= 0)
+        return RENET_ERR_UNSUPPORTED;
+    if (workspace_bytes < renet_build_full_graphs_workspace(sd, G, out->cap_nodes, out->cap_edges)) return RENET_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    FullStore S;
+    S.node_ptr = sd->node_ptr; S.node_ent_all = sd->node_ent_all; S.trip_ptr = sd->trip_ptr;
+    S.trip_ls = sd->trip_ls; S.trip_r = sd->trip_r; S.trip_lo = sd->trip_lo; S.T = sd->T; S.num_rels = sd->num_rels;
+    const int cap_nodes = out->cap_nodes, cap_edges = max(out->cap_edges & ~1, 2);
+    const int T2 = 2 * sd->num_rels;
+    if ((uint64_t)cap_nodes * T2 >= (1ull << 31)) return RENET_ERR_UNSUPPORTED;
+    const int key_bits = bits_for((uint64_t)cap_nodes * T2);
+
+    Carver cv{reinterpret_cast<char*>(workspace), workspace_bytes};
+    FullBufs bf;
+    if (!bf.carve(cv, G, cap_nodes, cap_edges)) return RENET_ERR_WORKSPACE;
+    int32_t* counts = out->counts;
+
+    BB_HIP(hipMemsetAsync(counts, 0, RENET_BB_NCOUNTS * sizeof(int32_t), st));
+    BB_HIP(hipMemsetAsync(bf.deg, 0, (size_t)(cap_nodes + 2) * sizeof(int32_t), st));
+    BB_HIP(hipMemsetAsync(bf.tc, 0, 1024 * sizeof(int32_t), st));
+
+    RENET_LAUNCH(fg_counts_kernel, dim3(1), dim3(1024), 0, st, S, tidx_dev, G, cap_nodes, out->cap_edges & ~1, bf.gti,
+                 out->seg_ptr, bf.fact_off, counts);
+    RENET_LAUNCH_CHECK();
+    RENET_LAUNCH(fg_nodes_kernel, dim3((cap_nodes + 255) / 256), dim3(256), 0, st, S, counts, G, cap_nodes, bf.gti, out->seg_ptr,
+                 out->node_ent);
+    RENET_LAUNCH_CHECK();
+    RENET_LAUNCH(fg_edges_kernel, dim3(min((cap_edges + 255) / 256, 1024)), dim3(256), 0, st, S, counts, G, cap_edges, key_bits,
+                 bf.gti, out->seg_ptr, bf.fact_off, bf.src, bf.dst, bf.et, bf.key_dt, bf.key_t, bf.iota, bf.deg, bf.tc,
+                 counts + RENET_BB_ERR);
+    RENET_LAUNCH_CHECK();
+    // only plan 0 (node_ent): a full-graph batch has no sequences
+    return build_tail(bf, out, cap_nodes, cap_edges, 0, sd->num_ent, T2, key_bits, heavy_thr, group_items, chunk, 1, 0, false, st);
 }
 
 }  // extern "C"

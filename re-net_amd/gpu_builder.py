@@ -6,7 +6,12 @@ history index of preprocess.HistoryIndex and the per-timestamp fact lists of gra
 batch is built from its B quadruple indices by kernels: 4 KB up, ~100 bytes of counts back, no synchronisation in
 between.  `DeviceBatch` then exposes the same attributes as graph.DeviceGraph (the arrays are bit-identical to the host
 builder's: tests/test_gpu_builder.py), so model.RENet.loss_prepared_both runs on it unchanged.
-Replaces, for that case, utils.py:209-244 + 115-131 + dgl.batch of the reference."""
+Replaces, for that case, utils.py:209-244 + 115-131 + dgl.batch of the reference.
+
+The global model's full-graph batches (graph.build_full_graphs; Aggregator.py:44-55 / 87-98) have a builder of their own at
+the end of this file: `FullGraphStore` keeps the per-timestamp node lists and local fact endpoints resident,
+`FullGraphBatch` is the union of the full graphs of a list of timestamps (csrc/builder.hip: renet_build_full_graphs, the
+same tail kernels behind a three-kernel front), again bit-identical to the host builder (tests/test_gpu_full_graph_builder.py)."""
 import ctypes
 
 import numpy as np
@@ -37,7 +42,13 @@ class _BatchOut(ctypes.Structure):
                                   'row_ent', 'row_rel', 'glob_row', 's_sorted', 'r_sorted', 'rel_label', 'ent_label', 'perm',
                                   'step_off')] + \
                [('plan_order', _P * 4), ('plan_seg', _P * 4), ('plan_target', _P * 4), ('counts', _P),
-                ('cap_nodes', ctypes.c_int), ('cap_edges', ctypes.c_int)]
+                ('cap_nodes', ctypes.c_int), ('cap_edges', ctypes.c_int), ('seg_ptr', _P)]
+
+
+class _FullStoreDev(ctypes.Structure):
+    _fields_ = [('node_ptr', _P), ('node_ent_all', _P), ('trip_ptr', _P), ('trip_ls', _P), ('trip_r', _P), ('trip_lo', _P),
+                ('T', ctypes.c_int), ('n_nodes', ctypes.c_int), ('n_facts', ctypes.c_int), ('num_ent', ctypes.c_int),
+                ('num_rels', ctypes.c_int)]
 
 
 def _bind():
@@ -356,3 +367,242 @@ class DeviceBatch(object):
         if self._table_items is None:
             self._table_items = K.compose_table_items(self)
         return self._table_items
+
+
+# ---- full-graph batches of the global model (csrc/builder.hip: renet_build_full_graphs) -----------------------------------
+MAX_FULL_GRAPHS = 1024       # member graphs per call (one workgroup scans their counts)
+
+
+class FullGraphStore(DeviceStore):
+    """What a FULL-graph batch (graph.build_full_graphs: the global model, Aggregator.py:44-55 / 87-98) needs resident: per
+    timestamp of graph_dict, in the dict's order, the node list `ent` and the facts with their LOCAL endpoints (ls, r, lo)
+    of graph.TimeGraph.  `host` holds the int32 arrays; they are uploaded once when `device` is given (device=None: host
+    arrays only, nothing touches a GPU)."""
+
+    def __init__(self, graph_dict, num_rels, device=None):             # (no DeviceStore.__init__: no dataset here)
+        store = G.store_for(graph_dict)
+        gs = store._graphs
+        self.store = store                                              # (index_of maps timestamps to positions)
+        self.num_rels = int(num_rels)
+        self.T = len(gs)
+        node_ptr = np.concatenate(([0], np.cumsum(store.node_cnt))).astype(np.int64)
+        trip_ptr = np.asarray(store.trip_ptr, dtype=np.int64)
+        cat = lambda xs: np.concatenate(xs) if xs else np.zeros(0, np.int64)
+        ent, ls, lo = cat([g.ent for g in gs]), cat([g.ls for g in gs]), cat([g.lo for g in gs])
+        r = np.asarray(store.trip_r, dtype=np.int64)
+        # the kernels index with these unchecked (a guard on the device reports, it does not repair): validate once, here
+        if 2 * self.num_rels > 1024 or self.num_rels <= 0:
+            raise ValueError('the device builder handles at most 512 relations')
+        if int(node_ptr[-1]) >= 2 ** 31 or 2 * int(trip_ptr[-1]) >= 2 ** 31:
+            raise ValueError('node / edge counts must fit int32')
+        if len(ent) and (ent.min() < 0 or ent.max() >= 2 ** 31 - 1):
+            raise ValueError('entity ids must fit int32')
+        if len(r) and (r.min() < 0 or r.max() >= self.num_rels):
+            raise ValueError('relation id outside [0, num_rels)')
+        n_of_fact = np.repeat(store.node_cnt, np.diff(trip_ptr))
+        if len(ls) and (min(ls.min(), lo.min()) < 0 or np.any(ls >= n_of_fact) or np.any(lo >= n_of_fact)):
+            raise ValueError('local node id outside its graph')
+        self.num_ent = int(ent.max()) + 1 if len(ent) else 1
+        self.n_nodes, self.n_facts = int(node_ptr[-1]), int(trip_ptr[-1])
+        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+        self.host = dict(node_ptr=i32(node_ptr), node_ent_all=i32(ent), trip_ptr=i32(trip_ptr), trip_ls=i32(ls),
+                         trip_r=i32(r), trip_lo=i32(lo))
+        self.device = device
+        self._pinned_free = []
+        self.t, self.c = None, None
+        if device is not None:
+            self.t = {n: torch.from_numpy(a).to(device) for n, a in self.host.items()}
+            sd = _FullStoreDev()
+            for n in self.host:
+                setattr(sd, n, self.t[n].data_ptr())
+            sd.T, sd.n_nodes, sd.n_facts, sd.num_ent, sd.num_rels = self.T, self.n_nodes, self.n_facts, self.num_ent, self.num_rels
+            self.c = sd
+
+    def sizes(self, tidx):
+        """(node offsets [G + 1], fact offsets [G + 1]) of the member graphs tidx -- N and E / 2 are their last entries."""
+        tidx = np.asarray(tidx, dtype=np.int64).reshape(-1)
+        if len(tidx) and (tidx.min() < 0 or tidx.max() >= self.T):
+            raise KeyError('timestamp index outside the store')
+        npt, tpt = self.host['node_ptr'].astype(np.int64), self.host['trip_ptr'].astype(np.int64)
+        return (np.concatenate(([0], np.cumsum(npt[tidx + 1] - npt[tidx]))),
+                np.concatenate(([0], np.cumsum(tpt[tidx + 1] - tpt[tidx]))))
+
+    def host_edges(self, tidx):
+        """numpy specification of the device front (fg_edges_kernel): (node_ent, src, dst, et) of the batch of member graphs
+        tidx.  Member graph k owns edge positions [2 fact_off[k], 2 fact_off[k + 1]): its facts forward (ls -> lo, type r),
+        then reversed (lo -> ls, type r + R) -- the order of graph.build_full_graphs' concatenation, which decides every tie
+        of the stable sorts behind it."""
+        tidx = np.asarray(tidx, dtype=np.int64).reshape(-1)
+        noff, foff = self.sizes(tidx)
+        h = {n: a.astype(np.int64) for n, a in self.host.items()}
+        nf = np.diff(foff)
+        node_ent = h['node_ent_all'][G.ragged_arange(h['node_ptr'][tidx], np.diff(noff))]
+        j = G.ragged_arange(h['trip_ptr'][tidx], nf)                    # store fact of every batch fact, graph-major
+        k = np.repeat(np.arange(len(tidx), dtype=np.int64), nf)
+        e = np.arange(len(j), dtype=np.int64) - foff[k]                 # fact number inside its graph
+        a, b, r = h['trip_ls'][j] + noff[k], h['trip_lo'][j] + noff[k], h['trip_r'][j]
+        E = 2 * int(foff[-1])
+        src, dst, et = np.empty(E, np.int64), np.empty(E, np.int64), np.empty(E, np.int64)
+        fwd, rev = 2 * foff[k] + e, 2 * foff[k] + nf[k] + e
+        src[fwd], dst[fwd], et[fwd] = a, b, r
+        src[rev], dst[rev], et[rev] = b, a, r + self.num_rels
+        return node_ent, src, dst, et
+
+
+_full_stores = {}
+
+
+def full_graph_store_for(graph_dict, num_rels, device=None):
+    """The resident FullGraphStore of graph_dict on `device`, rebuilt when the graph store object changed (graph.store_for
+    re-creates it when the dict gained timestamps).  Keyed on the dict's identity, validated by the IDENTITY of its graph
+    store -- no key is hashed per call.  Entries die with their graph_dict (weak reference), at most 8 stay resident."""
+    import weakref
+    store = G.store_for(graph_dict)
+    key = (id(graph_dict), str(device))
+    ent = _full_stores.get(key)
+    if ent is None or ent[0] is not store or ent[1].num_rels != int(num_rels):
+        if len(_full_stores) > 8:
+            _full_stores.clear()
+        ent = (store, FullGraphStore(graph_dict, num_rels, device))
+        _full_stores[key] = ent
+        try:
+            weakref.finalize(graph_dict, _full_stores.pop, key, None)
+        except TypeError:                    # (a plain dict cannot be weakly referenced: the size bound above applies)
+            pass
+    return ent[1]
+
+
+def build_full_graphs_raw(store, tidx_dev, n_graphs, cap_nodes, cap_edges, stream=None):
+    """Allocates the outputs for the given capacities and makes the C call (renet_build_full_graphs) on `stream`.  Returns
+    (views, norm, keep): the int32 output views by name (incl. 'counts', still on the device), the fp32 norm, and the
+    objects that must stay alive until the kernels have run.  Nothing is synchronised or read back here."""
+    L = _bind()
+    dev = store.device
+    cn, ce = int(cap_nodes), int(cap_edges)
+    T2 = 2 * store.num_rels
+    cc = ce // G.CHUNK + T2 + 2
+    sizes = dict(seg_ptr=n_graphs + 1, node_ent=cn, row_ptr=cn + 2, col=ce, etype=ce, heavy_rows=cn, e_src=ce, e_dst=ce,
+                 chunk_ptr=cc + 1, chunk_type=cc, type_chunk_ptr=T2 + 1, it_src=ce + cn, it_type=ce + cn, grp_ptr=cn + 2,
+                 counts=NCOUNTS, plan_order0=cn, plan_seg0=cn + 1, plan_target0=cn)
+    offs, tot = {}, 0
+    for n, m in sizes.items():
+        offs[n] = tot
+        tot += (m + 63) & ~63
+    st = stream if stream is not None else torch.cuda.current_stream()
+    nbytes = L.renet_build_full_graphs_workspace(ctypes.addressof(store.c), n_graphs, cn, ce)
+    with torch.cuda.stream(st):              # the buffers belong to the stream the builder runs on
+        buf = torch.empty(tot, device=dev, dtype=torch.int32)
+        norm = torch.empty(cn, device=dev, dtype=torch.float32)
+        ws = torch.empty(nbytes // 4 + 64, device=dev, dtype=torch.int32)
+    v = {n: buf[o:o + sizes[n]] for n, o in offs.items()}
+    out = _BatchOut()
+    for n, _ in _BatchOut._fields_:
+        if n in v:
+            setattr(out, n, v[n].data_ptr())
+    out.norm = norm.data_ptr()
+    for f in ('plan_order', 'plan_seg', 'plan_target'):
+        setattr(out, f, (_P * 4)(v[f + '0'].data_ptr(), None, None, None))
+    out.cap_nodes, out.cap_edges = cn, ce
+    rc = L.renet_build_full_graphs(ctypes.addressof(store.c), tidx_dev.data_ptr(), int(n_graphs), G.HEAVY, G.GROUP_ITEMS,
+                                   G.CHUNK, ctypes.addressof(out), ws.data_ptr(), nbytes, st.cuda_stream)
+    if rc != 0:
+        raise K.RenetHipError('renet_build_full_graphs failed with code %d' % rc)
+    return v, norm, (buf, ws, out, tidx_dev)
+
+
+class FullGraphBatch(object):
+    """The disjoint union of the full graphs of store timestamps `tidx` (a repeated index = two member graphs), built on
+    the device.  After finalize() it carries the attributes of graph.DeviceGraph for a graph.build_full_graphs batch, the
+    arrays bit-identical (tests/test_gpu_full_graph_builder.py).  N and E are known on the host before the launch: the
+    buffers are sized exactly, and the only data read back is the counts."""
+
+    def __init__(self, store, tidx, stream=None):
+        tidx = np.ascontiguousarray(tidx, dtype=np.int64).reshape(-1)
+        if not 0 < len(tidx) <= MAX_FULL_GRAPHS:
+            raise ValueError('a full-graph batch has 1 .. %d member graphs' % MAX_FULL_GRAPHS)
+        noff, foff = store.sizes(tidx)
+        self.store, self.G = store, int(len(tidx))
+        self._sizes = (int(noff[-1]), 2 * int(foff[-1]))
+        st = stream if stream is not None else torch.cuda.current_stream()
+        with torch.cuda.stream(st):
+            idx_dev = torch.from_numpy(tidx.astype(np.int32)).to(store.device, non_blocking=True)
+        self._v, self._norm, self._keep = build_full_graphs_raw(store, idx_dev, self.G, max(self._sizes[0], 1),
+                                                               max(self._sizes[1], 2), st)
+        self._counts_host = store._take_pinned()     # owned by this batch until finalize() / release
+        self._stream = st
+        with torch.cuda.stream(st):
+            self._counts_host.copy_(self._v['counts'], non_blocking=True)
+            self._done = torch.cuda.Event()
+            self._done.record(st)
+        self._final = False
+
+    def finalize(self):
+        """Waits for the counts and slices the outputs to their sizes.  The capacities are exact, so an error bit here is
+        a store that does not describe its graphs: it raises."""
+        if self._final:
+            return True
+        self._done.synchronize()
+        c = self._counts_host.numpy().astype(np.int64)      # (a copy: the pinned buffer goes back to the free-list)
+        self.store._give_pinned(self._counts_host)
+        self._counts_host = None
+        buf, _, _, _ = self._keep
+        self._keep = buf                                     # (workspace, struct and indices are done with)
+        cur = torch.cuda.current_stream()
+        if cur != self._stream:                  # built on a side stream, consumed on this one
+            buf.record_stream(cur)
+            self._norm.record_stream(cur)
+        N, E = int(c[C_N]), int(c[C_E])
+        if c[C_ERR] != 0 or (N, E) != self._sizes:
+            raise K.RenetHipError('full-graph builder: error bits %d, N %d E %d where the store gives %s'
+                                  % (c[C_ERR], N, E, self._sizes))
+        v = self._v
+        self.N = self.nA = N
+        self.E = self.E_out = E
+        self.num_types = 2 * self.store.num_rels
+        self.heavy_thresh = G.HEAVY
+        self.seg_ptr, self.node_ent = v['seg_ptr'], v['node_ent'][:N]
+        self.row_ptr, self.col, self.etype = v['row_ptr'][:N + 1], v['col'][:E], v['etype'][:E]
+        self.norm = self._norm[:N]
+        nh = int(c[C_NHEAVY])
+        self.heavy_rows = v['heavy_rows'][:nh] if nh else None
+        self.heavy_rows_out = self.heavy_rows                # no row prefix: nA = N
+        self.e_src, self.e_dst = v['e_src'][:E], v['e_dst'][:E]
+        self.n_chunks = int(c[C_NCHUNKS])
+        self.chunk_ptr, self.chunk_type = v['chunk_ptr'][:self.n_chunks + 1], v['chunk_type'][:self.n_chunks]
+        self.type_chunk_ptr = v['type_chunk_ptr']
+        ni = int(c[C_NITEMS])
+        self.it_src, self.it_type = v['it_src'][:ni], v['it_type'][:ni]
+        self.n_groups = self.n_groups_out = int(c[C_NGROUPS])
+        self.grp_ptr = v['grp_ptr'][:self.n_groups + 1]
+        p = G.SegPlan()
+        u = int(c[C_NSEG0])
+        p.order, p.seg_ptr, p.target, p.num_segments = v['plan_order0'][:N], v['plan_seg0'][:u + 1], v['plan_target0'][:u], u
+        self.plan_node_ent = p
+        self.ndata = {}
+        self._table_items = None
+        self.host = _FullHost(self)
+        self._final = True
+        return True
+
+    def __del__(self):
+        # a batch dropped before finalize(): its copy may still be in flight -- wait for it before the buffer is reused
+        try:
+            if getattr(self, '_counts_host', None) is not None:
+                self._done.synchronize()
+                self.store._give_pinned(self._counts_host)
+                self._counts_host = None
+        except Exception:       # interpreter shutdown
+            pass
+
+    def table_items(self):
+        if self._table_items is None:
+            self._table_items = K.compose_table_items(self)
+        return self._table_items
+
+
+class _FullHost(object):
+    """Host-side view of a FullGraphBatch: the scalars of the graph.HostBatch that graph.build_full_graphs returns."""
+
+    def __init__(self, b):
+        self.G, self.N, self.E, self.nA, self.num_types = b.G, b.N, b.E, b.nA, b.num_types
+        self.n_chunks, self.n_groups, self.n_groups_out, self.heavy_thresh = b.n_chunks, b.n_groups, b.n_groups_out, b.heavy_thresh
