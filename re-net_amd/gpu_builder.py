@@ -4,15 +4,21 @@ The host builder (graph.build_batch_both: numpy front + the native passes of csr
 merged batch against a ~3.6 ms device step.  Here the dataset is resident in HBM -- the quadruples, the per-role
 history index of preprocess.HistoryIndex and the per-timestamp fact lists of graph.GraphStore (`DeviceStore`) -- and a
 batch is built from its B quadruple indices by kernels: 4 KB up, ~100 bytes of counts back, no synchronisation in
-between.  `DeviceBatch` then exposes the same attributes as graph.DeviceGraph (the arrays are bit-identical to the host
-builder's: tests/test_gpu_builder.py), so model.RENet.loss_prepared_both runs on it unchanged.
+between.  `DeviceBatch` then carries the attributes of graph.BatchGraph, as graph.DeviceGraph does (the arrays are
+bit-identical to the host builder's: tests/test_gpu_builder.py), so model.RENet.loss_prepared_both runs on it unchanged.
 Replaces, for that case, utils.py:209-244 + 115-131 + dgl.batch of the reference.
 
-The global model's full-graph batches (graph.build_full_graphs; Aggregator.py:44-55 / 87-98) have a builder of their own at
-the end of this file: `FullGraphStore` keeps the per-timestamp node lists and local fact endpoints resident,
-`FullGraphBatch` is the union of the full graphs of a list of timestamps (csrc/builder.hip: renet_build_full_graphs, the
-same tail kernels behind a three-kernel front), again bit-identical to the host builder (tests/test_gpu_full_graph_builder.py)."""
+The global model's full-graph batches (graph.build_full_graphs; Aggregator.py:44-55 / 87-98) are built the same way:
+`FullGraphStore` keeps the per-timestamp node lists and local fact endpoints resident, `FullGraphBatch` is the union of the
+full graphs of a list of timestamps (csrc/builder.hip: renet_build_full_graphs, the same tail kernels behind a three-kernel
+front), again bit-identical to the host builder (tests/test_gpu_full_graph_builder.py).
+
+Layout of this file: the ctypes mirrors of the structs and count slots of include/renet_hip.h (tests/test_host_cpu.py holds
+them to the header); `_Store`, the base of the resident stores, and the per-graph_dict cache `_cached_store`; `_launch`,
+the one place that lays out, allocates and calls a builder front; `_PendingBatch`, the life cycle of a batch from the
+launch to finalize(), of which `DeviceBatch` and `FullGraphBatch` are a front plus the fields each adds."""
 import ctypes
+import weakref
 
 import numpy as np
 import torch
@@ -59,47 +65,21 @@ def _i32(a, dev):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
 
 
-class DeviceStore(object):
-    """The dataset, resident on the device: quadruples, both history indices, the graph store, the sorted timestamps of
-    the global-embedding table."""
+def _check_int32(what, *arrays, limit=2 ** 31):
+    """ValueError('<what> must fit int32') unless every value of `arrays` lies in [0, limit)."""
+    for a in arrays:
+        if len(a) and (int(a.max()) >= limit or int(a.min()) < 0):
+            raise ValueError(what + ' must fit int32')
 
-    def __init__(self, quads, hist_s, hist_o, graph_dict, global_emb, num_ent, num_rels, device):
-        quads = np.asarray(quads, dtype=np.int64)
-        store = G.store_for(graph_dict)
-        times = np.asarray(store.times, dtype=np.int64)
-        if len(times) > 1 and np.any(np.diff(times) <= 0):
-            raise ValueError('graph_dict must be in ascending time order')
-        for arr in (quads, store.trip_s, store.trip_o, times):
-            if len(arr) and (arr.max() >= 2 ** 31 or arr.min() < 0):
-                raise ValueError('ids / timestamps must fit int32')
+
+class _Store(object):
+    """What every resident store shares: its device, num_ent / num_rels and the pinned 256-byte count buffers.  Those are a
+    free-list, not a ring -- every pending batch OWNS its buffer from the async D2H copy until finalize() has read it
+    (with a shared ring of 8, the ninth pending batch overwrote the counts of the first)."""
+
+    def __init__(self, device, num_ent, num_rels):
         self.device = device
         self.num_ent, self.num_rels = int(num_ent), int(num_rels)
-        self.n_quads = len(quads)
-        self.t = dict(q_s=_i32(quads[:, 0], device), q_r=_i32(quads[:, 1], device), q_o=_i32(quads[:, 2], device),
-                      times=_i32(times, device), trip_ptr=_i32(store.trip_ptr, device), trip_s=_i32(store.trip_s, device),
-                      trip_r=_i32(store.trip_r, device), trip_o=_i32(store.trip_o, device),
-                      glob_times=_i32(sorted(int(t) for t in global_emb.keys()), device))
-        for r, h in enumerate((hist_s, hist_o)):
-            self.t['h_first%d' % r] = _i32(h.first, device)
-            self.t['h_count%d' % r] = _i32(h.count, device)
-            self.t['snap_t%d' % r] = _i32(h.snap_t, device)
-            self.t['snap_ptr%d' % r] = _i32(h.snap_ptr, device)
-            self.t['nbr_o%d' % r] = _i32(h.nbr_o, device)
-        self.history_len = int(hist_s.history_len)
-        self.n_facts = int(len(store.trip_s))
-        sd = _StoreDev()
-        for n in ('q_s', 'q_r', 'q_o', 'times', 'trip_ptr', 'trip_s', 'trip_r', 'trip_o', 'glob_times'):
-            setattr(sd, n, self.t[n].data_ptr())
-        for n in ('h_first', 'h_count', 'snap_t', 'snap_ptr', 'nbr_o'):
-            setattr(sd, n, (_P * 2)(self.t[n + '0'].data_ptr(), self.t[n + '1'].data_ptr()))
-        sd.T, sd.n_glob, sd.n_facts = len(times), int(self.t['glob_times'].numel()), self.n_facts
-        sd.num_ent, sd.num_rels = self.num_ent, self.num_rels
-        self.c = sd
-        # capacities: grown on demand (an overflow is reported in the counts and the batch rebuilt)
-        self.cap_nodes, self.cap_edges = 1 << 17, 1 << 19
-        # pinned 256-byte count buffers: a free-list, not a ring -- every DeviceBatch OWNS its buffer from the async
-        # D2H copy until finalize() has read it (ADVICE r3: with a shared ring of 8, the ninth pending batch overwrote
-        # the counts of the first)
         self._pinned_free = []
 
     def _take_pinned(self):
@@ -112,56 +92,83 @@ class DeviceStore(object):
             self._pinned_free.append(buf)
 
 
-class GraphDeviceStore(DeviceStore):
+class GraphDeviceStore(_Store):
     """The part of a DeviceStore that a batch does NOT bring itself: the per-timestamp fact lists of the graph store and the
     timestamps of the global-embedding table.  Used by the reference's LIST API (RENet.forward with nested history lists,
     train.py:136-137): there the quadruples and their histories arrive with every call (ListBatchStore uploads them, ~160 KB),
-    so no dataset has to be registered with the model.  Cached per (graph store, global_emb size) in graph_store_for()."""
+    so no dataset has to be registered with the model.  Cached per (graph store, global_emb timestamps) in graph_store_for()."""
 
-    def __init__(self, graph_dict, global_emb, num_ent, num_rels, device):      # (no DeviceStore.__init__: no dataset here)
+    def __init__(self, graph_dict, global_emb, num_ent, num_rels, device):
+        _Store.__init__(self, device, num_ent, num_rels)
         store = G.store_for(graph_dict)
         times = np.asarray(store.times, dtype=np.int64)
         if len(times) > 1 and np.any(np.diff(times) <= 0):
             raise ValueError('graph_dict must be in ascending time order')
-        for arr in (store.trip_s, store.trip_o, times):
-            if len(arr) and (arr.max() >= 2 ** 31 or arr.min() < 0):
-                raise ValueError('ids / timestamps must fit int32')
-        self.device = device
-        self.num_ent, self.num_rels = int(num_ent), int(num_rels)
+        _check_int32('ids / timestamps', store.trip_s, store.trip_o, times)
         self.n_quads = 0
         self.t = dict(times=_i32(times, device), trip_ptr=_i32(store.trip_ptr, device), trip_s=_i32(store.trip_s, device),
                       trip_r=_i32(store.trip_r, device), trip_o=_i32(store.trip_o, device),
                       glob_times=_i32(sorted(int(t) for t in global_emb.keys()), device))
         self.n_facts = int(len(store.trip_s))
         self.T, self.n_glob = len(times), int(self.t['glob_times'].numel())
+        # capacities: grown on demand (an overflow is reported in the counts and the batch rebuilt)
         self.cap_nodes, self.cap_edges = 1 << 17, 1 << 19
-        self._pinned_free = []
         self.c = None                         # (a ListBatchStore fills a struct per batch)
+
+
+class DeviceStore(GraphDeviceStore):
+    """The dataset, resident on the device: quadruples, both history indices, the graph store, the sorted timestamps of
+    the global-embedding table."""
+
+    def __init__(self, quads, hist_s, hist_o, graph_dict, global_emb, num_ent, num_rels, device):
+        GraphDeviceStore.__init__(self, graph_dict, global_emb, num_ent, num_rels, device)
+        quads = np.asarray(quads, dtype=np.int64)
+        _check_int32('ids / timestamps', quads)
+        self.n_quads = len(quads)
+        self.t.update(q_s=_i32(quads[:, 0], device), q_r=_i32(quads[:, 1], device), q_o=_i32(quads[:, 2], device))
+        for r, h in enumerate((hist_s, hist_o)):
+            self.t['h_first%d' % r] = _i32(h.first, device)
+            self.t['h_count%d' % r] = _i32(h.count, device)
+            self.t['snap_t%d' % r] = _i32(h.snap_t, device)
+            self.t['snap_ptr%d' % r] = _i32(h.snap_ptr, device)
+            self.t['nbr_o%d' % r] = _i32(h.nbr_o, device)
+        self.history_len = int(hist_s.history_len)
+        sd = _StoreDev()
+        for n in ('q_s', 'q_r', 'q_o', 'times', 'trip_ptr', 'trip_s', 'trip_r', 'trip_o', 'glob_times'):
+            setattr(sd, n, self.t[n].data_ptr())
+        for n in ('h_first', 'h_count', 'snap_t', 'snap_ptr', 'nbr_o'):
+            setattr(sd, n, (_P * 2)(self.t[n + '0'].data_ptr(), self.t[n + '1'].data_ptr()))
+        sd.T, sd.n_glob, sd.n_facts = self.T, self.n_glob, self.n_facts
+        sd.num_ent, sd.num_rels = self.num_ent, self.num_rels
+        self.c = sd
+
+
+def _cached_store(cache, graph_dict, device, stamp, make):
+    """The entry of `cache` for graph_dict on `device`, made by make() when there is none, when the graph store object changed
+    (graph.store_for re-creates it when the dict gained timestamps) or when `stamp` did.  Keyed on the dict's identity;
+    entries die with their graph_dict (weak reference), at most 8 stay resident."""
+    store = G.store_for(graph_dict)
+    key = (id(graph_dict), str(device))
+    ent = cache.get(key)
+    if ent is None or ent[0] is not store or ent[1] != stamp:
+        if len(cache) > 8:
+            cache.clear()
+        ent = cache[key] = (store, stamp, make())
+        try:
+            weakref.finalize(graph_dict, cache.pop, key, None)
+        except TypeError:                    # (a plain dict cannot be weakly referenced: the size bound above applies)
+            pass
+    return ent[2]
 
 
 _graph_stores = {}
 
 
 def graph_store_for(graph_dict, global_emb, num_ent, num_rels, device):
-    """The resident GraphDeviceStore of (graph_dict, global_emb) on `device`; rebuilt when the graph store object changed
-    (graph.store_for re-creates it when the dict gained timestamps) or the global-embedding table's TIMESTAMPS changed (the
-    store holds their sorted list: the same count with different keys must not reuse it).  Entries die with their
-    graph_dict (weak reference), at most 8 stay resident."""
-    import weakref
-    store = G.store_for(graph_dict)
-    key = (id(graph_dict), str(device))
-    stamp = hash(tuple(sorted(int(t) for t in global_emb.keys())))
-    ent = _graph_stores.get(key)
-    if ent is None or ent[0] is not store or ent[1] != stamp:
-        if len(_graph_stores) > 8:
-            _graph_stores.clear()
-        ent = (store, stamp, GraphDeviceStore(graph_dict, global_emb, num_ent, num_rels, device))
-        _graph_stores[key] = ent
-        try:
-            weakref.finalize(graph_dict, _graph_stores.pop, key, None)
-        except TypeError:                    # (a plain dict cannot be weakly referenced: the size bound above applies)
-            pass
-    return ent[2]
+    """The resident GraphDeviceStore of (graph_dict, global_emb) on `device`; rebuilt also when the global-embedding table's
+    TIMESTAMPS changed (the store holds their sorted list: the same count with different keys must not reuse it)."""
+    return _cached_store(_graph_stores, graph_dict, device, hash(tuple(sorted(int(t) for t in global_emb.keys()))),
+                         lambda: GraphDeviceStore(graph_dict, global_emb, num_ent, num_rels, device))
 
 
 class ListBatchStore(object):
@@ -180,9 +187,7 @@ class ListBatchStore(object):
         parts = [trip[:, 0], trip[:, 1], trip[:, 2]]
         for fh in (fs, fo):
             parts += [fh.seq_ptr[:-1], np.diff(fh.seq_ptr), fh.step_t, fh.nbr_ptr, fh.nbr_o]
-        for a in parts:
-            if len(a) and (int(a.max()) >= 2 ** 31 or int(a.min()) < 0):
-                raise ValueError('ids / timestamps must fit int32')
+        _check_int32('ids / timestamps', *parts)
         offs, tot = [], 0
         for a in parts:
             offs.append(tot)
@@ -233,54 +238,62 @@ class _Host(object):
         return self._perm
 
 
-class DeviceBatch(object):
-    """A merged batch built on the device.  After finalize() it carries the attributes of graph.DeviceGraph."""
+# the two fronts of csrc/builder.hip: (workspace size, build) of the C ABI
+_FRONT_BOTH = ('renet_build_batch_workspace', 'renet_build_batch_both')
+_FRONT_FULL = ('renet_build_full_graphs_workspace', 'renet_build_full_graphs')
 
-    def __init__(self, store, idx, seq_len, stream=None):
-        L = _bind()
-        self.store, dev = store, store.device
-        self.B = int(len(idx))
-        B2 = 2 * self.B
-        cn, ce = store.cap_nodes, store.cap_edges
-        cs = B2 * MAXL
-        T2 = 2 * store.num_rels
-        cc = ce // G.CHUNK + T2 + 2
-        sizes = dict(node_ent=cn, node_slot=cn, row_ptr=cn + 2, col=ce, etype=ce, heavy_rows=cn, e_src=ce, e_dst=ce,
-                     chunk_ptr=cc + 1, chunk_type=cc, type_chunk_ptr=T2 + 1, e_src2=ce, e_dst2=ce, chunk_ptr2=cc + 1,
-                     chunk_type2=cc, type_chunk_ptr2=T2 + 1, it_src=ce + cn, it_type=ce + cn, grp_ptr=cn + 2,
-                     subj_row=cs, row_seq=cs, row_ent=cs, row_rel=cs, glob_row=cs, s_sorted=B2, r_sorted=B2,
-                     rel_label=B2, ent_label=B2, perm=B2, step_off=MAXL + 1, counts=NCOUNTS,
-                     plan_order0=cn, plan_seg0=cn + 1, plan_target0=cn, plan_order1=cs, plan_seg1=cs + 1, plan_target1=cs,
-                     plan_order2=B2, plan_seg2=B2 + 1, plan_target2=B2, plan_order3=B2, plan_seg3=B2 + 1, plan_target3=B2)
-        offs, tot = {}, 0
-        for n, m in sizes.items():
-            offs[n] = tot
-            tot += (m + 63) & ~63
+
+def _launch(front, store, idx_dev, n, lead, own, cn, ce, stream):
+    """One builder call on `stream`: lays the int32 outputs out as 64-int aligned slices of ONE buffer -- the graph part that
+    every front fills for capacities (cn, ce), then the front's `own` {name: size} -- allocates buffer / norm / workspace on
+    the stream, fills the _BatchOut (views by field name, the plans that have slices) and calls front(store, idx_dev, n,
+    *lead, ...).  Returns (views, norm, keep): the int32 output views by name (incl. 'counts', still on the device), the fp32
+    norm, and the objects that must stay alive until the kernels have run, the buffer first.  Nothing is synchronised or
+    read back here."""
+    L = _bind()
+    T2 = 2 * store.num_rels
+    cc = ce // G.CHUNK + T2 + 2
+    sizes = dict(node_ent=cn, row_ptr=cn + 2, col=ce, etype=ce, heavy_rows=cn, e_src=ce, e_dst=ce, chunk_ptr=cc + 1,
+                 chunk_type=cc, type_chunk_ptr=T2 + 1, it_src=ce + cn, it_type=ce + cn, grp_ptr=cn + 2, counts=NCOUNTS,
+                 plan_order0=cn, plan_seg0=cn + 1, plan_target0=cn, **own)
+    offs, tot = {}, 0
+    for f, m in sizes.items():
+        offs[f] = tot
+        tot += (m + 63) & ~63
+    nbytes = getattr(L, front[0])(ctypes.addressof(store.c), n, cn, ce)
+    with torch.cuda.stream(stream):          # the buffers belong to the stream the builder runs on
+        buf = torch.empty(tot, device=store.device, dtype=torch.int32)
+        norm = torch.empty(cn, device=store.device, dtype=torch.float32)
+        ws = torch.empty(nbytes // 4 + 64, device=store.device, dtype=torch.int32)
+    v = {f: buf[o:o + sizes[f]] for f, o in offs.items()}
+    out = _BatchOut()
+    for f, _ in _BatchOut._fields_:
+        if f in v:
+            setattr(out, f, v[f].data_ptr())
+    out.norm = norm.data_ptr()
+    for f in ('plan_order', 'plan_seg', 'plan_target'):
+        setattr(out, f, (_P * 4)(*[v[f + str(k)].data_ptr() if f + str(k) in v else None for k in range(4)]))
+    out.cap_nodes, out.cap_edges = cn, ce
+    rc = getattr(L, front[1])(ctypes.addressof(store.c), idx_dev.data_ptr(), n, *lead, G.HEAVY, G.GROUP_ITEMS, G.CHUNK,
+                              ctypes.addressof(out), ws.data_ptr(), nbytes, stream.cuda_stream)
+    if rc != 0:
+        raise K.RenetHipError('%s failed with code %d' % (front[1], rc))
+    return v, norm, (buf, ws, out, idx_dev)
+
+
+class _PendingBatch(G.BatchGraph):
+    """A batch graph whose builder kernels have been enqueued: the index upload, one _launch, and the hand-over of the counts
+    through a pinned buffer of the store (async copy + event).  finalize() waits for the counts and slices the graph part
+    of graph.BatchGraph out of the views; a subclass names its front and its own slices, judges the counts (_accept) and
+    slices what it adds (_own_part)."""
+
+    def __init__(self, front, store, idx, lead, own, cn, ce, stream):
+        G.BatchGraph.__init__(self)
+        self.store = store
         st = stream if stream is not None else torch.cuda.current_stream()
-        with torch.cuda.stream(st):              # the buffers belong to the stream the builder runs on
-            self._buf = torch.empty(tot, device=dev, dtype=torch.int32)
-            self._norm = torch.empty(cn, device=dev, dtype=torch.float32)
-        self._v = {n: self._buf[o:o + sizes[n]] for n, o in offs.items()}
-        out = _BatchOut()
-        for n, _ in _BatchOut._fields_:
-            if n in self._v:
-                setattr(out, n, self._v[n].data_ptr())
-        out.norm = self._norm.data_ptr()
-        for f in ('plan_order', 'plan_seg', 'plan_target'):
-            setattr(out, f, (_P * 4)(*[self._v['%s%d' % (f, k)].data_ptr() for k in range(4)]))
-        out.counts = self._v['counts'].data_ptr()
-        out.cap_nodes, out.cap_edges = cn, ce
-        self._caps = (cn, ce)
-        nbytes = L.renet_build_batch_workspace(ctypes.addressof(store.c), self.B, cn, ce)
         with torch.cuda.stream(st):
-            ws = torch.empty(nbytes // 4 + 64, device=dev, dtype=torch.int32)
-            self._idx = torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int32)).to(dev, non_blocking=True)
-        self._out = out                      # (kept alive: the call reads the struct through its address)
-        rc = L.renet_build_batch_both(ctypes.addressof(store.c), self._idx.data_ptr(), self.B, int(seq_len), G.HEAVY,
-                                      G.GROUP_ITEMS, G.CHUNK, ctypes.addressof(out), ws.data_ptr(), nbytes, st.cuda_stream)
-        if rc != 0:
-            raise K.RenetHipError('renet_build_batch_both failed with code %d' % rc)
-        self._ws = ws                       # stays alive until the kernels have run (freed in finalize)
+            idx_dev = torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int32)).to(store.device, non_blocking=True)
+        self._v, self._norm, self._keep = _launch(front, store, idx_dev, len(idx), lead, own, cn, ce, st)
         self._counts_host = store._take_pinned()     # owned by this batch until finalize() / release
         self._stream = st
         with torch.cuda.stream(st):
@@ -290,68 +303,54 @@ class DeviceBatch(object):
         self._final = False
 
     def finalize(self):
-        """Waits for the counts, slices the outputs to their sizes, composes the table-addressed item arrays.
-        Returns False if a capacity was exceeded (the store's capacities are then doubled: rebuild)."""
+        """Waits for the counts, slices the outputs to their sizes.  True when the batch is ready (and on every later call);
+        False if the subclass turned the counts down (DeviceBatch: a capacity was exceeded, rebuild)."""
         if self._final:
             return True
         self._done.synchronize()
         c = self._counts_host.numpy().astype(np.int64)      # (a copy: the pinned buffer goes back to the free-list)
         self.store._give_pinned(self._counts_host)
         self._counts_host = None
-        self._ws = None
+        self._buf, self._keep = self._keep[0], None          # (workspace, struct and indices are done with)
         cur = torch.cuda.current_stream()
         if cur != self._stream:                  # built on a side stream, consumed on this one
             self._buf.record_stream(cur)
             self._norm.record_stream(cur)
-        if c[C_ERR] != 0:
-            if c[C_ERR] & 4:
-                self.store.cap_nodes *= 2
-            if c[C_ERR] & 8:
-                self.store.cap_edges *= 2
-            if c[C_ERR] & 3:
-                raise KeyError('a history timestamp is missing from graph_dict / global_emb')
+        if not self._accept(c):
             return False
-        v = self._v
-        N, nA, E, S = int(c[C_N]), int(c[C_NA]), int(c[C_E]), int(c[C_S])
-        self.N, self.nA, self.E, self.S, self.nnz, self.L = N, nA, E, S, int(c[C_NNZ]), int(c[C_L])
-        self.B = 2 * self.B                      # sequences of the merged batch (graph.HostBatch.B)
-        self.num_types = 2 * self.store.num_rels
-        self.heavy_thresh = G.HEAVY
-        self.node_ent, self.node_slot = v['node_ent'][:N], v['node_slot'][:N]
-        self.row_ptr, self.col, self.etype = v['row_ptr'][:N + 1], v['col'][:E], v['etype'][:E]
-        self.norm = self._norm[:N]
-        nh, nho = int(c[C_NHEAVY]), int(c[C_NHEAVY_OUT])
-        self.heavy_rows = v['heavy_rows'][:nh] if nh else None
-        self.heavy_rows_out = v['heavy_rows'][:nho] if nho else None
-        self.e_src, self.e_dst = v['e_src'][:E], v['e_dst'][:E]
-        self.n_chunks, self.n_chunks2 = int(c[C_NCHUNKS]), int(c[C_NCHUNKS2])
-        self.chunk_ptr, self.chunk_type = v['chunk_ptr'][:self.n_chunks + 1], v['chunk_type'][:self.n_chunks]
-        self.type_chunk_ptr, self.type_chunk_ptr2 = v['type_chunk_ptr'], v['type_chunk_ptr2']
-        self.chunk_ptr2, self.chunk_type2 = v['chunk_ptr2'][:self.n_chunks2 + 1], v['chunk_type2'][:self.n_chunks2]
-        self.E_out = int(c[C_EOUT])
-        self.e_src2, self.e_dst2 = v['e_src2'][:self.E_out], v['e_dst2'][:self.E_out]
-        ni = int(c[C_NITEMS])
-        self.it_src, self.it_type = v['it_src'][:ni], v['it_type'][:ni]
-        self.n_groups, self.n_groups_out = int(c[C_NGROUPS]), int(c[C_NGROUPS_OUT])
-        self.grp_ptr = v['grp_ptr'][:self.n_groups + 1]
-        for n in ('subj_row', 'row_seq', 'row_ent', 'row_rel', 'glob_row'):
-            setattr(self, n, v[n][:S])
-        for n in ('s_sorted', 'r_sorted', 'rel_label', 'ent_label'):
-            setattr(self, n, v[n])
-        self.step_off = v['step_off'][:self.L + 1]
-        for k, name in enumerate(('plan_node_ent', 'plan_subj_row', 'plan_s', 'plan_r')):
-            p = G.SegPlan()
-            u = int(c[C_NSEG0 + k])
-            n_rows = (N, S, self.B, self.B)[k]
-            p.order, p.seg_ptr, p.target = v['plan_order%d' % k][:n_rows], v['plan_seg%d' % k][:u + 1], v['plan_target%d' % k][:u]
-            p.num_segments = u
-            setattr(self, name, p)
-        self.ndata = {}
-        self._table_items = None
-        # the few host-side values the model still needs (packing of the GRU launches, reporting)
-        self.host = _Host(self, c)
+        self._graph_part(c)
+        self._own_part(c)
         self._final = True
         return True
+
+    def _plan(self, k, n_rows, c):
+        v, u, p = self._v, int(c[C_NSEG0 + k]), G.SegPlan()
+        p.order, p.seg_ptr, p.target = v['plan_order%d' % k][:n_rows], v['plan_seg%d' % k][:u + 1], v['plan_target%d' % k][:u]
+        p.num_segments = u
+        return p
+
+    def _graph_part(self, c):
+        """The graph part of graph.BatchGraph, for a batch without a row prefix (nA = N)."""
+        v = self._v
+        N, E = int(c[C_N]), int(c[C_E])
+        self.N = self.nA = N
+        self.E = self.E_out = E
+        self.num_types = 2 * self.store.num_rels
+        self.heavy_thresh = G.HEAVY
+        self.node_ent = v['node_ent'][:N]
+        self.row_ptr, self.col, self.etype = v['row_ptr'][:N + 1], v['col'][:E], v['etype'][:E]
+        self.norm = self._norm[:N]
+        nh = int(c[C_NHEAVY])
+        self.heavy_rows = self.heavy_rows_out = v['heavy_rows'][:nh] if nh else None
+        self.e_src, self.e_dst = v['e_src'][:E], v['e_dst'][:E]
+        self.n_chunks = int(c[C_NCHUNKS])
+        self.chunk_ptr, self.chunk_type = v['chunk_ptr'][:self.n_chunks + 1], v['chunk_type'][:self.n_chunks]
+        self.type_chunk_ptr = v['type_chunk_ptr']
+        ni = int(c[C_NITEMS])
+        self.it_src, self.it_type = v['it_src'][:ni], v['it_type'][:ni]
+        self.n_groups = self.n_groups_out = int(c[C_NGROUPS])
+        self.grp_ptr = v['grp_ptr'][:self.n_groups + 1]
+        self.plan_node_ent = self._plan(0, N, c)
 
     def __del__(self):
         # a batch dropped before finalize(): its copy may still be in flight -- wait for it before the buffer is reused
@@ -363,52 +362,92 @@ class DeviceBatch(object):
         except Exception:       # interpreter shutdown
             pass
 
-    def table_items(self):
-        if self._table_items is None:
-            self._table_items = K.compose_table_items(self)
-        return self._table_items
+
+class DeviceBatch(_PendingBatch):
+    """A merged batch built on the device from the quadruple indices `idx` of `store`.  After finalize() it carries the
+    attributes of graph.BatchGraph, graph and sequence part, with the row prefix [0, nA) of the subject rows."""
+
+    def __init__(self, store, idx, seq_len, stream=None):
+        self.n_quads = int(len(idx))
+        self.B = B2 = 2 * self.n_quads              # sequences of the merged batch (graph.HostBatch.B)
+        cn, ce = store.cap_nodes, store.cap_edges
+        cs = B2 * MAXL
+        T2 = 2 * store.num_rels
+        cc = ce // G.CHUNK + T2 + 2
+        own = dict(node_slot=cn, e_src2=ce, e_dst2=ce, chunk_ptr2=cc + 1, chunk_type2=cc, type_chunk_ptr2=T2 + 1,
+                   subj_row=cs, row_seq=cs, row_ent=cs, row_rel=cs, glob_row=cs, s_sorted=B2, r_sorted=B2,
+                   rel_label=B2, ent_label=B2, perm=B2, step_off=MAXL + 1,
+                   plan_order1=cs, plan_seg1=cs + 1, plan_target1=cs,
+                   plan_order2=B2, plan_seg2=B2 + 1, plan_target2=B2, plan_order3=B2, plan_seg3=B2 + 1, plan_target3=B2)
+        _PendingBatch.__init__(self, _FRONT_BOTH, store, idx, (int(seq_len),), own, cn, ce, stream)
+
+    def _accept(self, c):
+        """False if a capacity was exceeded (the store's capacities are then doubled: rebuild)."""
+        err = c[C_ERR]
+        if err & 4:
+            self.store.cap_nodes *= 2
+        if err & 8:
+            self.store.cap_edges *= 2
+        if err & 3:
+            raise KeyError('a history timestamp is missing from graph_dict / global_emb')
+        return err == 0
+
+    def _own_part(self, c):
+        v = self._v
+        N, S = self.N, int(c[C_S])
+        self.nA, self.E_out, self.S, self.nnz, self.L = int(c[C_NA]), int(c[C_EOUT]), S, int(c[C_NNZ]), int(c[C_L])
+        self.node_slot = v['node_slot'][:N]
+        nho = int(c[C_NHEAVY_OUT])
+        self.heavy_rows_out = v['heavy_rows'][:nho] if nho else None
+        self.n_chunks2, self.n_groups_out = int(c[C_NCHUNKS2]), int(c[C_NGROUPS_OUT])
+        self.type_chunk_ptr2 = v['type_chunk_ptr2']
+        self.chunk_ptr2, self.chunk_type2 = v['chunk_ptr2'][:self.n_chunks2 + 1], v['chunk_type2'][:self.n_chunks2]
+        self.e_src2, self.e_dst2 = v['e_src2'][:self.E_out], v['e_dst2'][:self.E_out]
+        for n in ('subj_row', 'row_seq', 'row_ent', 'row_rel', 'glob_row'):
+            setattr(self, n, v[n][:S])
+        for n in ('s_sorted', 'r_sorted', 'rel_label', 'ent_label'):
+            setattr(self, n, v[n])
+        self.step_off = v['step_off'][:self.L + 1]
+        self.plan_subj_row, self.plan_s, self.plan_r = self._plan(1, S, c), self._plan(2, self.B, c), self._plan(3, self.B, c)
+        # the few host-side values the model still needs (packing of the GRU launches, reporting)
+        self.host = _Host(self, c)
 
 
 # ---- full-graph batches of the global model (csrc/builder.hip: renet_build_full_graphs) -----------------------------------
 MAX_FULL_GRAPHS = 1024       # member graphs per call (one workgroup scans their counts)
 
 
-class FullGraphStore(DeviceStore):
+class FullGraphStore(_Store):
     """What a FULL-graph batch (graph.build_full_graphs: the global model, Aggregator.py:44-55 / 87-98) needs resident: per
     timestamp of graph_dict, in the dict's order, the node list `ent` and the facts with their LOCAL endpoints (ls, r, lo)
     of graph.TimeGraph.  `host` holds the int32 arrays; they are uploaded once when `device` is given (device=None: host
     arrays only, nothing touches a GPU)."""
 
-    def __init__(self, graph_dict, num_rels, device=None):             # (no DeviceStore.__init__: no dataset here)
+    def __init__(self, graph_dict, num_rels, device=None):
         store = G.store_for(graph_dict)
         gs = store._graphs
         self.store = store                                              # (index_of maps timestamps to positions)
-        self.num_rels = int(num_rels)
         self.T = len(gs)
         node_ptr = np.concatenate(([0], np.cumsum(store.node_cnt))).astype(np.int64)
         trip_ptr = np.asarray(store.trip_ptr, dtype=np.int64)
         cat = lambda xs: np.concatenate(xs) if xs else np.zeros(0, np.int64)
         ent, ls, lo = cat([g.ent for g in gs]), cat([g.ls for g in gs]), cat([g.lo for g in gs])
         r = np.asarray(store.trip_r, dtype=np.int64)
+        _Store.__init__(self, device, int(ent.max()) + 1 if len(ent) else 1, num_rels)
         # the kernels index with these unchecked (a guard on the device reports, it does not repair): validate once, here
         if 2 * self.num_rels > 1024 or self.num_rels <= 0:
             raise ValueError('the device builder handles at most 512 relations')
-        if int(node_ptr[-1]) >= 2 ** 31 or 2 * int(trip_ptr[-1]) >= 2 ** 31:
-            raise ValueError('node / edge counts must fit int32')
-        if len(ent) and (ent.min() < 0 or ent.max() >= 2 ** 31 - 1):
-            raise ValueError('entity ids must fit int32')
+        _check_int32('node / edge counts', node_ptr[-1:], 2 * trip_ptr[-1:])
+        _check_int32('entity ids', ent, limit=2 ** 31 - 1)
         if len(r) and (r.min() < 0 or r.max() >= self.num_rels):
             raise ValueError('relation id outside [0, num_rels)')
         n_of_fact = np.repeat(store.node_cnt, np.diff(trip_ptr))
         if len(ls) and (min(ls.min(), lo.min()) < 0 or np.any(ls >= n_of_fact) or np.any(lo >= n_of_fact)):
             raise ValueError('local node id outside its graph')
-        self.num_ent = int(ent.max()) + 1 if len(ent) else 1
         self.n_nodes, self.n_facts = int(node_ptr[-1]), int(trip_ptr[-1])
         i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
         self.host = dict(node_ptr=i32(node_ptr), node_ent_all=i32(ent), trip_ptr=i32(trip_ptr), trip_ls=i32(ls),
                          trip_r=i32(r), trip_lo=i32(lo))
-        self.device = device
-        self._pinned_free = []
         self.t, self.c = None, None
         if device is not None:
             self.t = {n: torch.from_numpy(a).to(device) for n, a in self.host.items()}
@@ -453,151 +492,17 @@ _full_stores = {}
 
 
 def full_graph_store_for(graph_dict, num_rels, device=None):
-    """The resident FullGraphStore of graph_dict on `device`, rebuilt when the graph store object changed (graph.store_for
-    re-creates it when the dict gained timestamps).  Keyed on the dict's identity, validated by the IDENTITY of its graph
-    store -- no key is hashed per call.  Entries die with their graph_dict (weak reference), at most 8 stay resident."""
-    import weakref
-    store = G.store_for(graph_dict)
-    key = (id(graph_dict), str(device))
-    ent = _full_stores.get(key)
-    if ent is None or ent[0] is not store or ent[1].num_rels != int(num_rels):
-        if len(_full_stores) > 8:
-            _full_stores.clear()
-        ent = (store, FullGraphStore(graph_dict, num_rels, device))
-        _full_stores[key] = ent
-        try:
-            weakref.finalize(graph_dict, _full_stores.pop, key, None)
-        except TypeError:                    # (a plain dict cannot be weakly referenced: the size bound above applies)
-            pass
-    return ent[1]
+    """The resident FullGraphStore of graph_dict on `device`, rebuilt also when num_rels changed.  Validated by the IDENTITY
+    of the dict's graph store -- no key is hashed per call."""
+    return _cached_store(_full_stores, graph_dict, device, int(num_rels), lambda: FullGraphStore(graph_dict, num_rels, device))
 
 
 def build_full_graphs_raw(store, tidx_dev, n_graphs, cap_nodes, cap_edges, stream=None):
-    """Allocates the outputs for the given capacities and makes the C call (renet_build_full_graphs) on `stream`.  Returns
-    (views, norm, keep): the int32 output views by name (incl. 'counts', still on the device), the fp32 norm, and the
-    objects that must stay alive until the kernels have run.  Nothing is synchronised or read back here."""
-    L = _bind()
-    dev = store.device
-    cn, ce = int(cap_nodes), int(cap_edges)
-    T2 = 2 * store.num_rels
-    cc = ce // G.CHUNK + T2 + 2
-    sizes = dict(seg_ptr=n_graphs + 1, node_ent=cn, row_ptr=cn + 2, col=ce, etype=ce, heavy_rows=cn, e_src=ce, e_dst=ce,
-                 chunk_ptr=cc + 1, chunk_type=cc, type_chunk_ptr=T2 + 1, it_src=ce + cn, it_type=ce + cn, grp_ptr=cn + 2,
-                 counts=NCOUNTS, plan_order0=cn, plan_seg0=cn + 1, plan_target0=cn)
-    offs, tot = {}, 0
-    for n, m in sizes.items():
-        offs[n] = tot
-        tot += (m + 63) & ~63
+    """The C call (renet_build_full_graphs) for the given capacities on `stream`, without a batch object: what _launch
+    returns.  (FullGraphBatch sizes the buffers exactly; the capacity-guard test calls this with capacities one too small.)"""
     st = stream if stream is not None else torch.cuda.current_stream()
-    nbytes = L.renet_build_full_graphs_workspace(ctypes.addressof(store.c), n_graphs, cn, ce)
-    with torch.cuda.stream(st):              # the buffers belong to the stream the builder runs on
-        buf = torch.empty(tot, device=dev, dtype=torch.int32)
-        norm = torch.empty(cn, device=dev, dtype=torch.float32)
-        ws = torch.empty(nbytes // 4 + 64, device=dev, dtype=torch.int32)
-    v = {n: buf[o:o + sizes[n]] for n, o in offs.items()}
-    out = _BatchOut()
-    for n, _ in _BatchOut._fields_:
-        if n in v:
-            setattr(out, n, v[n].data_ptr())
-    out.norm = norm.data_ptr()
-    for f in ('plan_order', 'plan_seg', 'plan_target'):
-        setattr(out, f, (_P * 4)(v[f + '0'].data_ptr(), None, None, None))
-    out.cap_nodes, out.cap_edges = cn, ce
-    rc = L.renet_build_full_graphs(ctypes.addressof(store.c), tidx_dev.data_ptr(), int(n_graphs), G.HEAVY, G.GROUP_ITEMS,
-                                   G.CHUNK, ctypes.addressof(out), ws.data_ptr(), nbytes, st.cuda_stream)
-    if rc != 0:
-        raise K.RenetHipError('renet_build_full_graphs failed with code %d' % rc)
-    return v, norm, (buf, ws, out, tidx_dev)
-
-
-class FullGraphBatch(object):
-    """The disjoint union of the full graphs of store timestamps `tidx` (a repeated index = two member graphs), built on
-    the device.  After finalize() it carries the attributes of graph.DeviceGraph for a graph.build_full_graphs batch, the
-    arrays bit-identical (tests/test_gpu_full_graph_builder.py).  N and E are known on the host before the launch: the
-    buffers are sized exactly, and the only data read back is the counts."""
-
-    def __init__(self, store, tidx, stream=None):
-        tidx = np.ascontiguousarray(tidx, dtype=np.int64).reshape(-1)
-        if not 0 < len(tidx) <= MAX_FULL_GRAPHS:
-            raise ValueError('a full-graph batch has 1 .. %d member graphs' % MAX_FULL_GRAPHS)
-        noff, foff = store.sizes(tidx)
-        self.store, self.G = store, int(len(tidx))
-        self._sizes = (int(noff[-1]), 2 * int(foff[-1]))
-        st = stream if stream is not None else torch.cuda.current_stream()
-        with torch.cuda.stream(st):
-            idx_dev = torch.from_numpy(tidx.astype(np.int32)).to(store.device, non_blocking=True)
-        self._v, self._norm, self._keep = build_full_graphs_raw(store, idx_dev, self.G, max(self._sizes[0], 1),
-                                                               max(self._sizes[1], 2), st)
-        self._counts_host = store._take_pinned()     # owned by this batch until finalize() / release
-        self._stream = st
-        with torch.cuda.stream(st):
-            self._counts_host.copy_(self._v['counts'], non_blocking=True)
-            self._done = torch.cuda.Event()
-            self._done.record(st)
-        self._final = False
-
-    def finalize(self):
-        """Waits for the counts and slices the outputs to their sizes.  The capacities are exact, so an error bit here is
-        a store that does not describe its graphs: it raises."""
-        if self._final:
-            return True
-        self._done.synchronize()
-        c = self._counts_host.numpy().astype(np.int64)      # (a copy: the pinned buffer goes back to the free-list)
-        self.store._give_pinned(self._counts_host)
-        self._counts_host = None
-        buf, _, _, _ = self._keep
-        self._keep = buf                                     # (workspace, struct and indices are done with)
-        cur = torch.cuda.current_stream()
-        if cur != self._stream:                  # built on a side stream, consumed on this one
-            buf.record_stream(cur)
-            self._norm.record_stream(cur)
-        N, E = int(c[C_N]), int(c[C_E])
-        if c[C_ERR] != 0 or (N, E) != self._sizes:
-            raise K.RenetHipError('full-graph builder: error bits %d, N %d E %d where the store gives %s'
-                                  % (c[C_ERR], N, E, self._sizes))
-        v = self._v
-        self.N = self.nA = N
-        self.E = self.E_out = E
-        self.num_types = 2 * self.store.num_rels
-        self.heavy_thresh = G.HEAVY
-        self.seg_ptr, self.node_ent = v['seg_ptr'], v['node_ent'][:N]
-        self.row_ptr, self.col, self.etype = v['row_ptr'][:N + 1], v['col'][:E], v['etype'][:E]
-        self.norm = self._norm[:N]
-        nh = int(c[C_NHEAVY])
-        self.heavy_rows = v['heavy_rows'][:nh] if nh else None
-        self.heavy_rows_out = self.heavy_rows                # no row prefix: nA = N
-        self.e_src, self.e_dst = v['e_src'][:E], v['e_dst'][:E]
-        self.n_chunks = int(c[C_NCHUNKS])
-        self.chunk_ptr, self.chunk_type = v['chunk_ptr'][:self.n_chunks + 1], v['chunk_type'][:self.n_chunks]
-        self.type_chunk_ptr = v['type_chunk_ptr']
-        ni = int(c[C_NITEMS])
-        self.it_src, self.it_type = v['it_src'][:ni], v['it_type'][:ni]
-        self.n_groups = self.n_groups_out = int(c[C_NGROUPS])
-        self.grp_ptr = v['grp_ptr'][:self.n_groups + 1]
-        p = G.SegPlan()
-        u = int(c[C_NSEG0])
-        p.order, p.seg_ptr, p.target, p.num_segments = v['plan_order0'][:N], v['plan_seg0'][:u + 1], v['plan_target0'][:u], u
-        self.plan_node_ent = p
-        self.ndata = {}
-        self._table_items = None
-        self.host = _FullHost(self)
-        self._final = True
-        return True
-
-    def __del__(self):
-        # a batch dropped before finalize(): its copy may still be in flight -- wait for it before the buffer is reused
-        try:
-            if getattr(self, '_counts_host', None) is not None:
-                self._done.synchronize()
-                self.store._give_pinned(self._counts_host)
-                self._counts_host = None
-        except Exception:       # interpreter shutdown
-            pass
-
-    def table_items(self):
-        if self._table_items is None:
-            self._table_items = K.compose_table_items(self)
-        return self._table_items
+    return _launch(_FRONT_FULL, store, tidx_dev, int(n_graphs), (), dict(seg_ptr=int(n_graphs) + 1), int(cap_nodes),
+                   int(cap_edges), st)
 
 
 class _FullHost(object):
@@ -606,3 +511,32 @@ class _FullHost(object):
     def __init__(self, b):
         self.G, self.N, self.E, self.nA, self.num_types = b.G, b.N, b.E, b.nA, b.num_types
         self.n_chunks, self.n_groups, self.n_groups_out, self.heavy_thresh = b.n_chunks, b.n_groups, b.n_groups_out, b.heavy_thresh
+
+
+class FullGraphBatch(_PendingBatch):
+    """The disjoint union of the full graphs of store timestamps `tidx` (a repeated index = two member graphs), built on
+    the device.  After finalize() it carries the graph part of graph.BatchGraph for a graph.build_full_graphs batch (no row
+    prefix, no *2 arrays; G and seg_ptr), the arrays bit-identical (tests/test_gpu_full_graph_builder.py).  N and E are known
+    on the host before the launch: the buffers are sized exactly, and the only data read back is the counts."""
+
+    def __init__(self, store, tidx, stream=None):
+        tidx = np.ascontiguousarray(tidx, dtype=np.int64).reshape(-1)
+        if not 0 < len(tidx) <= MAX_FULL_GRAPHS:
+            raise ValueError('a full-graph batch has 1 .. %d member graphs' % MAX_FULL_GRAPHS)
+        noff, foff = store.sizes(tidx)
+        self.G = int(len(tidx))
+        self._sizes = (int(noff[-1]), 2 * int(foff[-1]))
+        _PendingBatch.__init__(self, _FRONT_FULL, store, tidx, (), dict(seg_ptr=self.G + 1), max(self._sizes[0], 1),
+                               max(self._sizes[1], 2), stream)
+
+    def _accept(self, c):
+        """The capacities are exact, so an error bit here is a store that does not describe its graphs: it raises."""
+        N, E = int(c[C_N]), int(c[C_E])
+        if c[C_ERR] != 0 or (N, E) != self._sizes:
+            raise K.RenetHipError('full-graph builder: error bits %d, N %d E %d where the store gives %s'
+                                  % (c[C_ERR], N, E, self._sizes))
+        return True
+
+    def _own_part(self, c):
+        self.seg_ptr = self._v['seg_ptr']
+        self.host = _FullHost(self)

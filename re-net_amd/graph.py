@@ -891,12 +891,44 @@ def h2d(a, device):
     return pinned.to(device, non_blocking=True)
 
 
-class DeviceGraph(object):
+class BatchGraph(object):
+    """A batch graph on the device, whoever built it (DeviceGraph: uploaded from the host builder; gpu_builder.DeviceBatch /
+    FullGraphBatch: built by kernels).  What the layers, the model and step_plan read -- device int32 views unless noted:
+      graph part     N, E, nA, E_out, num_types, heavy_thresh; node_ent, row_ptr, col, etype, norm (fp32), heavy_rows /
+                     heavy_rows_out (None when empty), e_src, e_dst, n_chunks, chunk_ptr, chunk_type, type_chunk_ptr, it_src,
+                     it_type, n_groups, n_groups_out, grp_ptr; with a row prefix nA < N also e_src2, e_dst2, n_chunks2,
+                     chunk_ptr2, chunk_type2, type_chunk_ptr2; a full-graph batch has G and seg_ptr instead
+      sequence part  (merged training batch) S, B, nnz, L; subj_row, row_ent, row_rel, glob_row, s_sorted, r_sorted,
+                     rel_label, ent_label, step_off
+      plans          SegPlan plan_node_ent, and with the sequence part plan_subj_row, plan_s, plan_r
+      host view      `host`: the sizes, and for a merged batch step_off, batch_sizes, perm as numpy arrays
+      ndata          'h' lives here, as on the reference's DGL graph
+    This class owns what does not depend on the builder: ndata, the cached table_items(), and the values of a batch without
+    a row prefix (heavy_rows_out = None, nA = N) until the builder says otherwise."""
+
+    def __init__(self, N=None):
+        self.ndata = {}
+        self._table_items = None
+        self.heavy_rows_out = None
+        self.N = self.nA = N
+
+    def table_items(self):
+        """(it_src_t, it_type_t, col_t, e_src_t): the item stream / CSR columns / dW edge sources with every source
+        row replaced by its ENTITY id, for the first RGCN layer addressed through the entity table
+        (renet_hip.compose_table_items); composed on the device on first use."""
+        if self._table_items is None:
+            import renet_hip
+            self._table_items = renet_hip.compose_table_items(self)
+        return self._table_items
+
+
+class DeviceGraph(BatchGraph):
     """Device-resident view of a HostBatch / PackedBatch: ONE int32 upload + ONE float32 upload, sliced
-    into views."""
+    into views.  Carries the attributes of BatchGraph."""
 
     def __init__(self, hb, device):
         pb = hb if isinstance(hb, PackedBatch) else PackedBatch(hb)
+        BatchGraph.__init__(self, pb.scalars.get('N'))
         dev = h2d(pb.ints, device)
         self._buf = dev
         views = {nm: dev[o_:o_ + n] for nm, o_, n in zip(pb.names, pb.offs, pb.sizes)}
@@ -909,25 +941,10 @@ class DeviceGraph(object):
             p.num_segments = nseg
             setattr(self, pn, p)
         self.norm = h2d(pb.norm, device)
-        self.ndata = {}                  # 'h' lives here, as on the reference's DGL graph
         self.heavy_thresh = pb.scalars.get('heavy_thresh', HEAVY)
         for f in ('heavy_rows', 'heavy_rows_out'):
             if getattr(self, f, None) is not None and getattr(self, f).numel() == 0:
                 setattr(self, f, None)
-        if not hasattr(self, 'heavy_rows_out'):
-            self.heavy_rows_out = None
         for f, v in pb.scalars.items():
             setattr(self, f, v)
-        if not hasattr(self, 'nA'):
-            self.nA = getattr(self, 'N', None)
         self.host = hb if not isinstance(hb, PackedBatch) else _HostView(pb)
-        self._table_items = None
-
-    def table_items(self):
-        """(it_src_t, it_type_t, col_t, e_src_t): the item stream / CSR columns / dW edge sources with every source
-        row replaced by its ENTITY id, for the first RGCN layer addressed through the entity table
-        (renet_hip.compose_table_items); composed on the device on first use."""
-        if self._table_items is None:
-            import renet_hip
-            self._table_items = renet_hip.compose_table_items(self)
-        return self._table_items

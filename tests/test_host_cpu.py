@@ -401,6 +401,54 @@ def test_ctypes_signatures_match_the_header():
         assert (restype is None) == (ret == 'void') and (ret == 'void' or ckind[restype] in (kinds[ret], 'u64'))
 
 
+def _header_struct(hdr, name):
+    """[(field, 'ptr' | 'int', array length or 0)] of `typedef struct { ... } name;` in the comment-free header text, in
+    declaration order.  A '*' belongs to its declarator, as in C ('int32_t *a, *b', 'int32_t* a[2]', 'int T, n')."""
+    body = re.search(r'typedef\s+struct\s*\{([^{}]*)\}\s*%s\s*;' % name, hdr).group(1)
+    out = []
+    for decl in [d.strip() for d in body.split(';') if d.strip()]:
+        ctype, rest = re.match(r'(?:const\s+)?(\w+)\s*(.*)$', decl, re.S).groups()
+        for item in rest.split(','):
+            star, field, length = re.match(r'\s*(\*?)\s*(\w+)\s*(?:\[(\d+)\])?\s*$', item).groups()
+            assert star or ctype == 'int', (name, decl)          # (the mirrors know pointers and plain ints only)
+            out.append((field, 'ptr' if star else 'int', int(length or 0)))
+    return out
+
+
+def test_ctypes_struct_mirrors_match_the_header():
+    """The structs and count slots that gpu_builder.py restates by hand against include/renet_hip.h: field names, order,
+    pointer-or-int, array lengths; every RENET_BB_* value.  A field out of place here is a wild device write, not a Python
+    error (the builder kernels store through the pointers of RenetBatchOut)."""
+    import gpu_builder as GB
+    hdr = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', 'renet_hip.h')).read(), flags=re.S)
+
+    def mirror(cls):
+        out = []
+        for field, t in cls._fields_:
+            length = t._length_ if issubclass(t, ctypes.Array) else 0
+            base = t._type_ if length else t
+            assert base in (ctypes.c_void_p, ctypes.c_int), (cls.__name__, field, t)
+            out.append((field, 'ptr' if base is ctypes.c_void_p else 'int', length))
+        return out
+    for cname, cls, n_fields in (('RenetStoreDev', GB._StoreDev, 19), ('RenetBatchOut', GB._BatchOut, 38),
+                                 ('RenetFullStoreDev', GB._FullStoreDev, 11)):
+        want = _header_struct(hdr, cname)
+        assert len(want) == n_fields, (cname, len(want))              # (the parser saw the whole struct)
+        assert mirror(cls) == want, (cname, [(a, b) for a, b in zip(mirror(cls), want) if a != b])
+    body = re.search(r'enum\s*\{([^{}]*\bRENET_BB_NNZ\b[^{}]*)\}\s*;', hdr).group(1)
+    vals, nxt = {}, 0
+    for item in [x.strip() for x in body.split(',') if x.strip()]:
+        name, _, val = [x.strip() for x in item.partition('=')]
+        nxt = int(val) if val else nxt
+        vals[name] = nxt
+        nxt += 1
+    assert len(vals) == 24 and vals['RENET_BB_NNZ'] == 0 and vals['RENET_BB_STEP_OFF'] == 24
+    assert vals.pop('RENET_BB_NCOUNTS') == GB.NCOUNTS
+    mine = {n: getattr(GB, n) for n in dir(GB) if n.startswith('C_')}
+    assert mine == {'C_' + n[len('RENET_BB_'):]: v for n, v in vals.items()}
+    assert vals['RENET_BB_STEP_OFF'] + GB.MAXL + 1 <= GB.NCOUNTS           # step_off[0 .. MAXL] fits behind the slots
+
+
 def _tile_of_block(L, nbx, nby, panel=8, nbz=1):
     """Python restatement of tile_of_block (csrc/gemm_tiles.h): linear dispatch index (x fastest, then y, then z) ->
     (bx, by) for nbz == 1, (bx, by, bz) for split-K grids."""
