@@ -1272,25 +1272,51 @@ def _ptrs(tensors):
     return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
 
 
+def _offs(step_offs):
+    return ((ctypes.c_void_p * len(step_offs))(*[ctypes.cast(o, c_void_p).value for o in step_offs]),
+            (ctypes.c_int * len(step_offs))(*[len(o) - 1 for o in step_offs]))
+
+
+def _seqs(o):
+    return (o[1] - o[0]) if len(o) > 1 else 0
+
+
+_GRU_SUFFIX = {'bf16s': '_bf16', 'f32': '_f32'}          # current_mode() -> entry point suffix (any other mode: none)
+
+
+def _gru_call(n, step_offs, hdim, operands):
+    """What every recurrence call needs: checks the fp32 operands -> (bmax, workspace, its bytes, offset pointers, Ls)."""
+    for t in operands:
+        _f32(t)
+    bmax = max([_seqs(o) for o in step_offs] + [0])
+    nbytes = n * lib().renet_gru_workspace(int(bmax), hdim)
+    ws = torch.empty(max(nbytes // 4, 1), device=operands[0].device, dtype=torch.float32)
+    return (bmax, ws, nbytes) + _offs(step_offs)
+
+
+@contextlib.contextmanager
+def _gru_timed(hdim, packed):
+    """The enclosed library calls as 'gru_recurrence': h_{t-1} @ W_hh^T (backward: d_gates @ W_hh) per step, 2 * 3H * H
+    flops per packed row of the tensors in `packed`."""
+    t0 = _timer.begin() if _timer is not None else None
+    yield
+    if t0 is not None:
+        _timer.end('gru_recurrence', t0, flops=sum(2.0 * 3 * hdim * hdim * t.shape[0] for t in packed))
+
+
 def gru_fwd_multi(gis, step_off_host, hdim, w_hhs, b_hhs, out_rows=0):
     """n GRUs over the same packed layout in one launch -> ([h_last...], [saved...]); h_last has
     max(B, out_rows) rows, the ones past B zero."""
     L = len(step_off_host) - 1
-    b = step_off_host[1] - step_off_host[0] if L > 0 else 0
-    out_rows = max(int(out_rows), b)
+    out_rows = max(int(out_rows), _seqs(step_off_host))
     dev = gis[0].device
     hs = [torch.empty(out_rows, hdim, device=dev, dtype=torch.float32) for _ in gis]
     svs = [torch.empty(g.shape[0], 5 * hdim, device=dev, dtype=torch.float32) for g in gis]
-    for t in list(gis) + list(w_hhs) + list(b_hhs):
-        _f32(t)
-    nbytes = len(gis) * lib().renet_gru_workspace(b, hdim)
-    ws = torch.empty(max(nbytes // 4, 1), device=dev, dtype=torch.float32)
-    t0 = _timer.begin() if _timer is not None else None
-    _check(lib().renet_gru_fwd_multi(len(gis), _ptrs(gis), ctypes.cast(step_off_host, c_void_p), L, hdim,
-                                     _ptrs(w_hhs), _ptrs(b_hhs), _ptrs(hs), out_rows, _ptrs(svs), ws.data_ptr(),
-                                     nbytes, _stream()), 'gru_fwd_multi')
-    if t0 is not None:      # recurrence only: h_{t-1} @ W_hh^T per step, 2 * 3H * H flops per packed row
-        _timer.end('gru_recurrence', t0, flops=sum(2.0 * 3 * hdim * hdim * g.shape[0] for g in gis))
+    _, ws, nbytes, _, _ = _gru_call(len(gis), [step_off_host], hdim, list(gis) + list(w_hhs) + list(b_hhs))
+    with _gru_timed(hdim, gis):
+        _check(lib().renet_gru_fwd_multi(len(gis), _ptrs(gis), ctypes.cast(step_off_host, c_void_p), L, hdim,
+                                         _ptrs(w_hhs), _ptrs(b_hhs), _ptrs(hs), out_rows, _ptrs(svs), ws.data_ptr(),
+                                         nbytes, _stream()), 'gru_fwd_multi')
     return hs, svs
 
 
@@ -1300,22 +1326,12 @@ def gru_bwd_multi(dh_lasts, step_off_host, hdim, w_hhs, saveds):
     dev = saveds[0].device
     d_gis = [torch.empty(s.shape[0], 3 * hdim, device=dev, dtype=torch.float32) for s in saveds]
     d_ghs = [torch.empty(s.shape[0], 3 * hdim, device=dev, dtype=torch.float32) for s in saveds]
-    for t in list(dh_lasts) + list(w_hhs) + list(saveds):
-        _f32(t)
-    nbytes = n * lib().renet_gru_workspace(dh_lasts[0].shape[0], hdim)
-    ws = torch.empty(max(nbytes // 4, 1), device=dev, dtype=torch.float32)
-    t0 = _timer.begin() if _timer is not None else None
-    _check(lib().renet_gru_bwd_multi(n, _ptrs(dh_lasts), ctypes.cast(step_off_host, c_void_p), L, hdim,
-                                     _ptrs(w_hhs), _ptrs(saveds), _ptrs(d_gis), _ptrs(d_ghs), ws.data_ptr(),
-                                     nbytes, _stream()), 'gru_bwd_multi')
-    if t0 is not None:      # dh_{t-1} += d_gates @ W_hh per step: the same 2 * 3H * H flops per packed row
-        _timer.end('gru_recurrence', t0, flops=sum(2.0 * 3 * hdim * hdim * s_.shape[0] for s_ in saveds))
+    _, ws, nbytes, _, _ = _gru_call(n, [step_off_host], hdim, list(dh_lasts) + list(w_hhs) + list(saveds))
+    with _gru_timed(hdim, saveds):
+        _check(lib().renet_gru_bwd_multi(n, _ptrs(dh_lasts), ctypes.cast(step_off_host, c_void_p), L, hdim,
+                                         _ptrs(w_hhs), _ptrs(saveds), _ptrs(d_gis), _ptrs(d_ghs), ws.data_ptr(),
+                                         nbytes, _stream()), 'gru_bwd_multi')
     return d_gis, d_ghs
-
-
-def _offs(step_offs):
-    return ((ctypes.c_void_p * len(step_offs))(*[ctypes.cast(o, c_void_p).value for o in step_offs]),
-            (ctypes.c_int * len(step_offs))(*[len(o) - 1 for o in step_offs]))
 
 
 def gru_fwd_layouts(gis, step_offs, hdim, w_hhs, b_hhs, out_rows):
@@ -1324,24 +1340,14 @@ def gru_fwd_layouts(gis, step_offs, hdim, w_hhs, b_hhs, out_rows):
     -> ([h_last...], [saved...])."""
     n = len(gis)
     dev = gis[0].device
-    rows = [max(int(r), (o[1] - o[0]) if len(o) > 1 else 0) for r, o in zip(out_rows, step_offs)]
+    rows = [max(int(r), _seqs(o)) for r, o in zip(out_rows, step_offs)]
     hs = [torch.empty(r, hdim, device=dev, dtype=torch.float32) for r in rows]
     svs = [torch.empty(g.shape[0], 5 * hdim, device=dev, dtype=torch.float32) for g in gis]
-    for t in list(gis) + list(w_hhs) + list(b_hhs):
-        _f32(t)
-    bmax = max([(o[1] - o[0]) if len(o) > 1 else 0 for o in step_offs] + [0])
-    nbytes = n * lib().renet_gru_workspace(int(bmax), hdim)
-    ws = torch.empty(max(nbytes // 4, 1), device=dev, dtype=torch.float32)
-    so, ls = _offs(step_offs)
-    t0 = _timer.begin() if _timer is not None else None
-    md = current_mode()
-    fn = lib().renet_gru_fwd_layouts_bf16 if md == 'bf16s' else lib().renet_gru_fwd_layouts_f32 if md == 'f32' else \
-        lib().renet_gru_fwd_layouts
-    _check(fn(n, _ptrs(gis), so, ls, hdim, _ptrs(w_hhs), _ptrs(b_hhs), _ptrs(hs),
-                                       (ctypes.c_int * n)(*rows), _ptrs(svs), ws.data_ptr(), nbytes, _stream()),
-           'gru_fwd_layouts')
-    if t0 is not None:
-        _timer.end('gru_recurrence', t0, flops=sum(2.0 * 3 * hdim * hdim * g.shape[0] for g in gis))
+    _, ws, nbytes, so, ls = _gru_call(n, step_offs, hdim, list(gis) + list(w_hhs) + list(b_hhs))
+    fn = getattr(lib(), 'renet_gru_fwd_layouts' + _GRU_SUFFIX.get(current_mode(), ''))
+    with _gru_timed(hdim, gis):
+        _check(fn(n, _ptrs(gis), so, ls, hdim, _ptrs(w_hhs), _ptrs(b_hhs), _ptrs(hs), (ctypes.c_int * n)(*rows),
+                  _ptrs(svs), ws.data_ptr(), nbytes, _stream()), 'gru_fwd_layouts')
     return hs, svs
 
 
@@ -1359,50 +1365,31 @@ def gru_bwd_layouts(dh_lasts, step_offs, hdim, w_hhs, saveds, out_bf16=False):
         for m in d_gis + d_ghs:
             _check(lib().renet_bf16_zero_padding(m.p.data_ptr(), m.R, m.C, m.p.shape[1], m.p.shape[0], _stream()),
                    'bf16_zero_padding')
-        for t in list(dh_lasts) + list(w_hhs) + list(saveds):
-            _f32(t)
-        bmax = max([(o[1] - o[0]) if len(o) > 1 else 0 for o in step_offs] + [0])
-        nbytes = n * lib().renet_gru_workspace(int(bmax), hdim)
-        ws = torch.empty(max(nbytes // 4, 1), device=dev, dtype=torch.float32)
-        so, ls = _offs(step_offs)
-        t0 = _timer.begin() if _timer is not None else None
-        _check(lib().renet_gru_bwd_layouts_bf16out(n, _ptrs(dh_lasts), so, ls, hdim, _ptrs(w_hhs), _ptrs(saveds),
-                                                   _ptrs([m.p for m in d_gis]), _ptrs([m.p for m in d_ghs]),
-                                                   lds.pop(), ws.data_ptr(), nbytes, _stream()), 'gru_bwd_layouts_bf16out')
-        if t0 is not None:
-            _timer.end('gru_recurrence', t0, flops=sum(2.0 * 3 * hdim * hdim * s_.shape[0] for s_ in saveds))
-        return d_gis, d_ghs
-    d_gis = [torch.empty(s.shape[0], 3 * hdim, device=dev, dtype=torch.float32) for s in saveds]
-    d_ghs = [torch.empty(s.shape[0], 3 * hdim, device=dev, dtype=torch.float32) for s in saveds]
-    for t in list(dh_lasts) + list(w_hhs) + list(saveds):
-        _f32(t)
-    bmax = max([(o[1] - o[0]) if len(o) > 1 else 0 for o in step_offs] + [0])
-    nbytes = n * lib().renet_gru_workspace(int(bmax), hdim)
-    ws = torch.empty(max(nbytes // 4, 1), device=dev, dtype=torch.float32)
-    so, ls = _offs(step_offs)
-    t0 = _timer.begin() if _timer is not None else None
-    done = False
-    if _fused_bounds(d_gis[0]) and bmax > 0:
-        # the kernel that writes dGi also emits its operand bound (one max |dGi| per workgroup)
-        nparts = lib().renet_gru_bound_parts(int(bmax))
-        parts = torch.empty(n, nparts, device=dev, dtype=torch.float32)
-        rc = lib().renet_gru_bwd_layouts_bounds(n, _ptrs(dh_lasts), so, ls, hdim, _ptrs(w_hhs), _ptrs(saveds),
-                                                _ptrs(d_gis), _ptrs(d_ghs), _ptrs([parts[k] for k in range(n)]),
-                                                ws.data_ptr(), nbytes, _stream())
-        if rc == 0:
-            for k in range(n):
-                _note_bound(d_gis[k], parts[k], nparts)
-            done = True
-        elif rc != -2:                                   # RENET_ERR_UNSUPPORTED: another recurrence is selected
-            _check(rc, 'gru_bwd_layouts_bounds')
-    if not done:
-        md = current_mode()
-        fn = lib().renet_gru_bwd_layouts_bf16 if md == 'bf16s' else lib().renet_gru_bwd_layouts_f32 if md == 'f32' else \
-            lib().renet_gru_bwd_layouts
-        _check(fn(n, _ptrs(dh_lasts), so, ls, hdim, _ptrs(w_hhs), _ptrs(saveds), _ptrs(d_gis),
-                  _ptrs(d_ghs), ws.data_ptr(), nbytes, _stream()), 'gru_bwd_layouts')
-    if t0 is not None:
-        _timer.end('gru_recurrence', t0, flops=sum(2.0 * 3 * hdim * hdim * s_.shape[0] for s_ in saveds))
+    else:
+        d_gis = [torch.empty(s.shape[0], 3 * hdim, device=dev, dtype=torch.float32) for s in saveds]
+        d_ghs = [torch.empty(s.shape[0], 3 * hdim, device=dev, dtype=torch.float32) for s in saveds]
+    bmax, ws, nbytes, so, ls = _gru_call(n, step_offs, hdim, list(dh_lasts) + list(w_hhs) + list(saveds))
+    head = (n, _ptrs(dh_lasts), so, ls, hdim, _ptrs(w_hhs), _ptrs(saveds))
+    tail = (ws.data_ptr(), nbytes, _stream())
+    with _gru_timed(hdim, saveds):
+        if out_bf16:
+            _check(lib().renet_gru_bwd_layouts_bf16out(*head, _ptrs([m.p for m in d_gis]), _ptrs([m.p for m in d_ghs]),
+                                                       lds.pop(), *tail), 'gru_bwd_layouts_bf16out')
+            return d_gis, d_ghs
+        if _fused_bounds(d_gis[0]) and bmax > 0:
+            # the kernel that writes dGi also emits its operand bound (one max |dGi| per workgroup)
+            nparts = lib().renet_gru_bound_parts(int(bmax))
+            parts = torch.empty(n, nparts, device=dev, dtype=torch.float32)
+            rc = lib().renet_gru_bwd_layouts_bounds(*head, _ptrs(d_gis), _ptrs(d_ghs),
+                                                    _ptrs([parts[k] for k in range(n)]), *tail)
+            if rc == 0:
+                for k in range(n):
+                    _note_bound(d_gis[k], parts[k], nparts)
+                return d_gis, d_ghs
+            if rc != -2:                                     # RENET_ERR_UNSUPPORTED: another recurrence is selected
+                _check(rc, 'gru_bwd_layouts_bounds')
+        fn = getattr(lib(), 'renet_gru_bwd_layouts' + _GRU_SUFFIX.get(current_mode(), ''))
+        _check(fn(*head, _ptrs(d_gis), _ptrs(d_ghs), *tail), 'gru_bwd_layouts')
     return d_gis, d_ghs
 
 

@@ -485,6 +485,89 @@ def test_gru_matches_torch_cpu(dev, i, h, nseq, kernels, monkeypatch):
         np.testing.assert_allclose(p.grad.cpu().numpy(), getattr(ref, name).grad.numpy(), rtol=1e-3, atol=1e-4)
 
 
+def _gru_float64(gi, off, w_hh, b_hh, dh_last):
+    """The recurrence over packed rows in float64 -> (h_last [B, H], saved [S, 5H], dGi, dGh)."""
+    h_dim, nstep = w_hh.shape[1], len(off) - 1
+    gi = gi.double().requires_grad_(True)
+    h = torch.zeros(off[1] - off[0], h_dim, dtype=torch.float64, requires_grad=True)     # (so that every gh has a grad)
+    ghs, saved = [], []
+    for j in range(nstep):
+        bs = off[j + 1] - off[j]
+        hp = h[:bs]
+        gh = hp @ w_hh.double().t() + b_hh.double()
+        gh.retain_grad()
+        g = gi[off[j]:off[j + 1]]
+        r = torch.sigmoid(g[:, :h_dim] + gh[:, :h_dim])
+        z = torch.sigmoid(g[:, h_dim:2 * h_dim] + gh[:, h_dim:2 * h_dim])
+        n = torch.tanh(g[:, 2 * h_dim:] + r * gh[:, 2 * h_dim:])
+        saved.append(torch.cat([r, z, n, gh[:, 2 * h_dim:], hp], 1).detach())
+        h = torch.cat([(1 - z) * n + z * hp, h[bs:]])
+        ghs.append(gh)
+    (h * dh_last.double()).sum().backward()
+    return h.detach(), torch.cat(saved), gi.grad, torch.cat([g.grad for g in ghs])
+
+
+_GRU_LAYOUT_CASE = []
+
+
+def _gru_layout_case():
+    """Four problems (W0, A), (W1, A), (W0, B), (W1, B) over two packed layouts, and their float64 results (built once)."""
+    if not _GRU_LAYOUT_CASE:
+        import ctypes
+        torch.manual_seed(11)
+        h_dim = 100
+        ws = [(torch.randn(3 * h_dim, h_dim) * 0.05, torch.randn(3 * h_dim)) for _ in range(2)]
+        lays = []
+        for lens, nstep in (([5] * 20 + [4] * 6 + [3] * 5 + [2] * 3 + [1] * 3, 5), ([3] * 9 + [2] * 6 + [1] * 5, 3)):
+            off = [0]
+            for j in range(nstep):
+                off.append(off[-1] + sum(1 for n in lens if n > j))
+            lays.append((off, (ctypes.c_int32 * len(off))(*off), len(lens)))
+        probs = []
+        for off, off_c, b in lays:
+            for w_hh, b_hh in ws:
+                gi, dh = torch.randn(off[-1], 3 * h_dim), torch.randn(b, h_dim)
+                probs.append(dict(gi=gi, dh=dh, w_hh=w_hh, b_hh=b_hh, off=off_c, b=b,
+                                  ref=_gru_float64(gi, off, w_hh, b_hh, dh)))
+        _GRU_LAYOUT_CASE.append((h_dim, probs))
+    return _GRU_LAYOUT_CASE[0]
+
+
+@pytest.mark.parametrize('route', ['persistent', 'steps', 'f32'])
+def test_gru_layouts_four_problems_two_layouts_match_a_float64_recurrence(dev, route, monkeypatch):
+    """renet_gru_{fwd,bwd}_layouts directly: four problems, two layouts (three workgroup tiles with a partial last one,
+    tiles that finish early), two shared W_hh -- both bf16x6 structures (RENET_GRU) and the exact-fp32 kernels (per-model
+    mode 'f32') against a float64 recurrence, with the tolerances of test_gru_matches_torch_cpu."""
+    import contextlib
+    import renet_hip as K
+    if route == 'f32':
+        monkeypatch.delenv('RENET_GRU', raising=False)
+    else:
+        monkeypatch.setenv('RENET_GRU', route)
+    h_dim, probs = _gru_layout_case()
+    w_dev = {}                                   # problems of one W_hh pass the SAME device tensor (one plane split)
+    for p in probs:
+        w_dev.setdefault(id(p['w_hh']), (p['w_hh'].to(dev), p['b_hh'].to(dev)))
+    w_hhs = [w_dev[id(p['w_hh'])][0] for p in probs]
+    b_hhs = [w_dev[id(p['w_hh'])][1] for p in probs]
+    offs = [p['off'] for p in probs]
+    out_rows = [p['b'] + 3 if k < 2 else p['b'] for k, p in enumerate(probs)]
+    with K.gemm_mode('f32') if route == 'f32' else contextlib.nullcontext():
+        hs, svs = K.gru_fwd_layouts([p['gi'].to(dev) for p in probs], offs, h_dim, w_hhs, b_hhs, out_rows)
+        d_gis, d_ghs = K.gru_bwd_layouts([p['dh'].to(dev) for p in probs], offs, h_dim, w_hhs, svs)
+    for k, p in enumerate(probs):
+        h_ref, sv_ref, dgi_ref, dgh_ref = p['ref']
+        b = p['b']
+        assert hs[k].shape == (out_rows[k], h_dim) and float(hs[k][b:].abs().sum()) == 0.0, k
+        np.testing.assert_allclose(hs[k][:b].cpu().numpy(), h_ref.numpy(), rtol=1e-4, atol=1e-5, err_msg='h_last %d' % k)
+        sv = svs[k].cpu().numpy()
+        for c, name in enumerate(('r', 'z', 'n', 'hn', 'hp')):
+            np.testing.assert_allclose(sv[:, c * h_dim:(c + 1) * h_dim], sv_ref.numpy()[:, c * h_dim:(c + 1) * h_dim],
+                                       rtol=1e-4, atol=1e-5, err_msg='saved %s %d' % (name, k))
+        np.testing.assert_allclose(d_gis[k].cpu().numpy(), dgi_ref.numpy(), rtol=1e-3, atol=2e-5, err_msg='dGi %d' % k)
+        np.testing.assert_allclose(d_ghs[k].cpu().numpy(), dgh_ref.numpy(), rtol=1e-3, atol=2e-5, err_msg='dGh %d' % k)
+
+
 def test_fused_directions_of_forward_equal_the_two_calls_of_train_py(dev):
     """RENet.fuse_directions through the real kernels: train.py:136-138's two model() calls as one merged pass (eval-mode
     masks: dropout 0, so both forms are deterministic) -- per-direction values and the gradient of the sum."""

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Times the persistent GRU launches (forward, backward) of a given build of the library on the bench's shapes.
 
-  python tools/gru_bench.py build NAME [-DFLAG ...]   # here: tools/_trace/gru_NAME.so (gru.hip rebuilt with the flags)
+  python tools/gru_bench.py build NAME [-DFLAG ...]   # here: tools/_trace/gru_NAME.so (gru*.hip rebuilt with the flags)
   python tools/gru_bench.py run [LIB ...]             # on the GPU box: us per launch for each library (default: the product's)
 """
 import ctypes
@@ -17,12 +17,14 @@ OUT = os.path.join(ROOT, 'tools', '_trace')
 def build():
     name, flags = sys.argv[2], sys.argv[3:]
     os.makedirs(OUT, exist_ok=True)
-    obj = os.path.join(OUT, 'gru_%s.o' % name)
-    subprocess.check_call(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-function']
-                          + flags + ['-c', os.path.join(CSRC, 'gru.hip'), '-o', obj])
-    others = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith('.o') and f != 'gru.o']
+    gru = [f[:-4] for f in sorted(os.listdir(CSRC)) if f.startswith('gru') and f.endswith('.hip')]
+    objs = [os.path.join(OUT, '%s_%s.o' % (g, name)) for g in gru]
+    for g, obj in zip(gru, objs):
+        subprocess.check_call(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-function']
+                              + flags + ['-c', os.path.join(CSRC, g + '.hip'), '-o', obj])
+    others = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith('.o') and f[:-2] not in gru]
     lib = os.path.join(OUT, 'gru_%s.so' % name)
-    subprocess.check_call(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-shared', '-fPIC', '-o', lib, obj] + others)
+    subprocess.check_call(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-shared', '-fPIC', '-o', lib] + objs + others)
     print(lib)
 
 

@@ -5,6 +5,7 @@
   python tools/gru_trace.py run [H] [B] [L]  # on the GPU box: two GRUs of B sequences (bench-like length mix)
 """
 import ctypes
+import glob
 import os
 import subprocess
 import sys
@@ -18,7 +19,8 @@ BLOCKS, NW, MAXL, SLOTS = 32, 8, 32, 8
 def build():
     os.makedirs(OUT, exist_ok=True)
     cmd = ['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared', '-DRENET_GRU_TRACE',
-           '-I' + os.path.join(ROOT, 'include'), os.path.join(ROOT, 're-net_amd', 'csrc', 'gru.hip'), '-o', LIB] + sys.argv[2:]
+           '-I' + os.path.join(ROOT, 'include')] + sorted(glob.glob(os.path.join(ROOT, 're-net_amd', 'csrc', 'gru*.hip'))) + \
+          ['-o', LIB] + sys.argv[2:]          # the host front and the three kernel families (the traced one: gru_planes.hip)
     print(' '.join(cmd))
     subprocess.check_call(cmd)
 
