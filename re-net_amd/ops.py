@@ -238,6 +238,33 @@ def grad_target(t):
     return None
 
 
+# The three forms of "accumulate into the parameter's .grad slice and hand autograd None, else return a fresh gradient":
+def _gemm_grad(a, b, tgt):
+    """a^T @ b (auto split-K): accumulated into tgt (beta = 1) -> None, or -> the product."""
+    if tgt is not None:
+        K.gemm(a, b, ta=True, out=tgt, beta=1.0)
+        return None
+    return K.gemm(a, b, ta=True)
+
+
+def _colsum_grad(x, tgt):
+    """Column sums of x: accumulated into tgt -> None, or -> the sums."""
+    if tgt is not None:
+        K.colsum(x, out=tgt, beta=1.0)
+        return None
+    return K.colsum(x)
+
+
+def _segment_grad(src, plan, tgt, shape):
+    """Segment sums of src's rows (K.segment_add): added to tgt -> None, or -> zeros of `shape` plus the sums."""
+    if tgt is not None:
+        K.segment_add(src, plan, tgt)
+        return None
+    d = torch.zeros(shape, device=src.device, dtype=torch.float32)
+    K.segment_add(src, plan, d)
+    return d
+
+
 class GatherRowsFn(Function):
     """out = table[idx]  (utils.py:239 h0 = ent_embeds[id]); backward = deterministic segmented add."""
 
@@ -250,13 +277,7 @@ class GatherRowsFn(Function):
     @staticmethod
     @_bwd_mode
     def backward(ctx, g):
-        tgt = grad_target(ctx.src)
-        if tgt is not None:
-            K.segment_add(_c(g), ctx.plan, tgt)
-            return None, None, None
-        d = torch.zeros(ctx.shape, device=g.device, dtype=torch.float32)
-        K.segment_add(_c(g), ctx.plan, d)
-        return d, None, None
+        return _segment_grad(_c(g), ctx.plan, grad_target(ctx.src), ctx.shape), None, None
 
 
 class RGCNLayerFn(Function):
@@ -316,10 +337,7 @@ class RGCNLayerFn(Function):
             else:
                 K.rgcn_bwd_w(h, gn, g.e_src, g.e_dst, g.chunk_ptr, g.chunk_type, g.n_chunks, g.type_chunk_ptr,
                              g.num_types, ctx.shift, d_w, beta=1.0 if acc else 0.0)
-            if tgt_loop is not None:                                   # h^T @ g_loop (auto split-K), accumulated
-                K.gemm(h_op, gl_op, ta=True, out=tgt_loop, beta=1.0)
-                return None
-            return K.gemm(h_op, gl_op, ta=True)
+            return _gemm_grad(h_op, gl_op, tgt_loop)                   # h^T @ g_loop
         # the relation-block and self-loop weight gradients feed only the optimizer, and nothing else writes their
         # buffers: inside a declared step they run on the side stream, un-joined, under the rest of the backward pass
         sd = _deferred_scope(h.device, (h, gn, g_loop, getattr(gl_op, 'p', None), getattr(gl_op, 'part', None),
@@ -404,11 +422,7 @@ class RGCNTableLayerFn(Function):
         K.segment_add2(dh, g_loop, g.plan_node_ent, d_tab, gs)
         gs_op = K.operand(gs)
         K.gemm(gs_op, loop_weight, tb=True, out=d_tab, beta=1.0)          # += segsum(g_loop) @ W_loop^T
-        if tgt_loop is not None:
-            K.gemm(table, gs_op, ta=True, out=tgt_loop, beta=1.0)
-            d_loop = None
-        else:
-            d_loop = K.gemm(table, gs_op, ta=True)
+        d_loop = _gemm_grad(table, gs_op, tgt_loop)
         return (None if tgt_tab is not None else d_tab), None if acc else d_w, d_loop, None, None, None, None, None
 
 
@@ -442,20 +456,9 @@ class SeqAssembleFn(Function):
         tgt_ent, tgt_rel = grad_target(ctx.src_ent), grad_target(ctx.src_rel)
         d_rows, d_ent_seq, d_rel_seq = K.seq_assemble_bwd(_c(dx), _c(dxr), g.step_off, g.L, g.B, d, ctx.drop_p,
                                                           *ctx.seeds)
-        dev = dx.device
-        d_h2 = torch.zeros(ctx.shapes[0], device=dev, dtype=torch.float32)
-        K.segment_add(d_rows, g.plan_subj_row, d_h2)
-        d_ent = d_rel = None
-        if tgt_ent is not None:
-            K.segment_add(d_ent_seq, g.plan_s, tgt_ent)           # per-sequence sums, keyed by s[perm]
-        else:
-            d_ent = torch.zeros(ctx.shapes[1], device=dev, dtype=torch.float32)
-            K.segment_add(d_ent_seq, g.plan_s, d_ent)
-        if tgt_rel is not None:
-            K.segment_add(d_rel_seq, g.plan_r, tgt_rel)
-        else:
-            d_rel = torch.zeros(ctx.shapes[2], device=dev, dtype=torch.float32)
-            K.segment_add(d_rel_seq, g.plan_r, d_rel)
+        d_h2 = _segment_grad(d_rows, g.plan_subj_row, None, ctx.shapes[0])
+        d_ent = _segment_grad(d_ent_seq, g.plan_s, tgt_ent, ctx.shapes[1])       # per-sequence sums, keyed by s[perm]
+        d_rel = _segment_grad(d_rel_seq, g.plan_r, tgt_rel, ctx.shapes[2])
         return d_h2, d_ent, d_rel, None, None, None, None, None, None
 
 
@@ -545,28 +548,12 @@ class MultiGRUFn(Function):
             t_bi, t_bh = (grad_target(t) for t in ctx.src_b[k])
             dgi, dgh, xx, s_ = d_gis[k], d_ghs[k], xs[k], svs[k]
             x_op = ctx.x_ops[k] if ctx.x_ops is not None else xx
-            dwi = dwh = dbi = dbh = None
-            if t_ih is not None:
-                K.gemm(dgi_op, x_op, ta=True, out=t_ih, beta=1.0)
-            else:
-                dwi = K.gemm(dgi_op, x_op, ta=True)
+            dwi = _gemm_grad(dgi_op, x_op, t_ih)
             # |dGh| <= |dGi| elementwise (equal but for the n gate's factor r in (0, 1)) and |h| <= 1: both operand
             # bounds of the f16x3 GEMM are known without a pass over the tensors
             dgh_op = K.operand_like(dgh, dgi_op)
             hp_op = K.operand(s_[:, 4 * hdim:], bound=K.const_bound(1.0, s_.device))
-            if t_hh is not None:
-                K.gemm(dgh_op, hp_op, ta=True, out=t_hh, beta=1.0)
-            else:
-                dwh = K.gemm(dgh_op, hp_op, ta=True)
-            if t_bi is not None:
-                K.colsum(dgi, out=t_bi, beta=1.0)
-            else:
-                dbi = K.colsum(dgi)
-            if t_bh is not None:
-                K.colsum(dgh, out=t_bh, beta=1.0)
-            else:
-                dbh = K.colsum(dgh)
-            return [dwi, dwh, dbi, dbh]
+            return [dwi, _gemm_grad(dgh_op, hp_op, t_hh), _colsum_grad(dgi, t_bi), _colsum_grad(dgh, t_bh)]
 
         def input_grad(k, dgi_op):
             xx = xs[k]
@@ -719,25 +706,30 @@ def _head_backward(dlogits, feat, feat_op, weight, t_w, t_b, bias_side=None, bou
     dl_op = K.operand(dlogits, bound=bound)                          # consumed by dfeat and dW
     f_op = feat_op if feat_op is not None else feat
 
-    def bias_grad():
-        if t_b is not None:
-            K.colsum(dlogits, out=t_b, beta=1.0)
-            return None
-        return K.colsum(dlogits)
     if bias_side is not None:
         with bias_side():
-            d_b = bias_grad()
+            d_b = _colsum_grad(dlogits, t_b)
     dfeat = K.gemm(dl_op, weight)                                    # [B, parts*D]
     # (the weight gradient stays BEHIND dfeat on this stream: next to it on the side stream the two chip-filling GEMMs
     # were measured 2 % slower per step than back to back, tools/sessions/r04_s11.sh)
-    if t_w is not None:
-        K.gemm(dl_op, f_op, ta=True, out=t_w, beta=1.0)
-        d_w = None
-    else:
-        d_w = K.gemm(dl_op, f_op, ta=True)
+    d_w = _gemm_grad(dl_op, f_op, t_w)
     if bias_side is None:
-        d_b = bias_grad()
+        d_b = _colsum_grad(dlogits, t_b)
     return dfeat, d_w, d_b
+
+
+def _consume_ce_gradient(ctx):
+    """The saved (softmax - onehot) buffers of a head Function serve ONE backward pass: it scales them in place."""
+    if ctx.consumed:
+        raise RuntimeError('%s: the saved (softmax - onehot) buffers were scaled in place by the first backward pass; a '
+                           'second pass over the same graph is not supported' % type(ctx).__name__)
+    ctx.consumed = True
+
+
+def _scatter_head_rows(da_rows, dc_rows, plan_a, plan_c, t_a, t_c, a_shape, c_shape):
+    """Row gradients of a head's gathered inputs a[ia] and c[ic] (dc_rows None: a head without c) -> (d_a, d_c)."""
+    d_a = _segment_grad(da_rows, plan_a, t_a, a_shape)
+    return d_a, (_segment_grad(dc_rows, plan_c, t_c, c_shape) if dc_rows is not None else None)
 
 
 class HeadCEFn(Function):
@@ -772,10 +764,7 @@ class HeadCEFn(Function):
         feat, dlogits, weight = ctx.saved_tensors
         d, parts, drop_p, seed, plan_a, plan_c, a_shape, c_shape = ctx.meta
         t_a, t_c, t_w, t_b = [grad_target(t) for t in ctx.srcs]
-        if ctx.consumed:
-            raise RuntimeError('HeadCEFn: the saved (softmax - onehot) buffer was scaled in place by the first '
-                               'backward pass; a second pass over the same graph is not supported')
-        ctx.consumed = True
+        _consume_ce_gradient(ctx)
         # every gradient below is linear in dlogits: fold the upstream scalar (1 for `loss_s + loss_o`, 0.1 for
         # the relation head) into it ONCE, from device memory, instead of scaling three results
         if ctx.dl_bf16 is not None:
@@ -788,18 +777,7 @@ class HeadCEFn(Function):
             grad_done(ctx.srcs[2])
             grad_done(ctx.srcs[3])
         da_rows, dh, dc_rows = K.concat3_bwd(dfeat, d, parts, drop_p, seed)
-        d_a = d_c = None
-        if t_a is not None:
-            K.segment_add(da_rows, plan_a, t_a)
-        else:
-            d_a = torch.zeros(a_shape, device=g.device, dtype=torch.float32)
-            K.segment_add(da_rows, plan_a, d_a)
-        if parts == 3:
-            if t_c is not None:
-                K.segment_add(dc_rows, plan_c, t_c)
-            else:
-                d_c = torch.zeros(c_shape, device=g.device, dtype=torch.float32)
-                K.segment_add(dc_rows, plan_c, d_c)
+        d_a, d_c = _scatter_head_rows(da_rows, dc_rows, plan_a, plan_c, t_a, t_c, a_shape, c_shape)
         return d_a, None, dh, d_c, None, d_w, d_b, None, None, None, None, None, None
 
 
@@ -865,10 +843,7 @@ class DualHeadCEFn(Function):
         feat1, dl1, w1, feat2, dl2, w2 = ctx.saved_tensors
         d, drop_p, seed1, seed2, plan_a, plan_c, a_shape, c_shape = ctx.meta
         t_a, t_c, t_w1, t_b1, t_w2, t_b2 = [grad_target(t) for t in ctx.srcs]
-        if ctx.consumed:
-            raise RuntimeError('DualHeadCEFn: the saved (softmax - onehot) buffers were scaled in place by the first '
-                               'backward pass; a second pass over the same graph is not supported')
-        ctx.consumed = True
+        _consume_ce_gradient(ctx)
         b1_, fop1, b2_, fop2 = ctx.bf16
         dl1 = b1_ if b1_ is not None else dl1
         dl2 = b2_ if b2_ is not None else dl2
@@ -891,17 +866,7 @@ class DualHeadCEFn(Function):
             grad_done(ctx.srcs[4])
             grad_done(ctx.srcs[5])
         da1.add_(da2)                                        # same rows ent[s] in both heads: one scatter-add
-        d_a = d_c = None
-        if t_a is not None:
-            K.segment_add(da1, plan_a, t_a)
-        else:
-            d_a = torch.zeros(a_shape, device=g.device, dtype=torch.float32)
-            K.segment_add(da1, plan_a, d_a)
-        if t_c is not None:
-            K.segment_add(dc1, plan_c, t_c)
-        else:
-            d_c = torch.zeros(c_shape, device=g.device, dtype=torch.float32)
-            K.segment_add(dc1, plan_c, d_c)
+        d_a, d_c = _scatter_head_rows(da1, dc1, plan_a, plan_c, t_a, t_c, a_shape, c_shape)
         return (d_a, None, dh1, d_c, None, d_w1, d_b1, None, dh2, d_w2, d_b2, None) + (None,) * 8
 
 

@@ -6,8 +6,10 @@ There is NO fallback: if the library is missing or a call fails, this raises.
 """
 import contextlib
 import ctypes
+import functools
 import os
 import threading
+import weakref
 
 import torch
 
@@ -21,6 +23,16 @@ c_float = ctypes.c_float
 c_void_p = ctypes.c_void_p
 c_size_t = ctypes.c_size_t
 c_u64 = ctypes.c_uint64
+
+# argument lists that several entry points share verbatim
+_GEMM_ARGS = [c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p, c_int,
+              c_float, c_void_p, c_int, c_void_p, c_int, c_void_p, c_size_t, c_void_p]
+_RGCN_BWD_W_ARGS = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                    c_void_p, c_int, c_int, c_int, c_void_p, c_float, c_void_p, c_size_t, c_void_p]
+_GRU_FWD_LAYOUTS_ARGS = [c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                         c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+_GRU_BWD_LAYOUTS_ARGS = [c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                         c_void_p, c_void_p, c_size_t, c_void_p]
 
 _SIGNATURES = {
     'renet_version': (c_int, []),
@@ -53,17 +65,12 @@ _SIGNATURES = {
                                            c_void_p, c_void_p, c_void_p, c_void_p]),
     'renet_bound_parts': (c_int, [c_size_t]),
     'renet_rgcn_bwd_w_workspace': (c_size_t, [c_int, c_int]),
-    'renet_rgcn_bwd_w': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                                 c_void_p, c_int, c_int, c_int, c_void_p, c_float, c_void_p, c_size_t, c_void_p]),
-    'renet_rgcn_bwd_w64': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                                 c_void_p, c_int, c_int, c_int, c_void_p, c_float, c_void_p, c_size_t, c_void_p]),
+    'renet_rgcn_bwd_w': (c_int, _RGCN_BWD_W_ARGS),
+    'renet_rgcn_bwd_w64': (c_int, _RGCN_BWD_W_ARGS),
     'renet_gemm_workspace': (c_size_t, [c_int, c_int, c_int]),
-    'renet_gemm_f32': (c_int, [c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p, c_int,
-                               c_float, c_void_p, c_int, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
-    'renet_gemm_f32_split': (c_int, [c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p, c_int,
-                                     c_float, c_void_p, c_int, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
-    'renet_gemm_bf16': (c_int, [c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p, c_int,
-                                c_float, c_void_p, c_int, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    'renet_gemm_f32': (c_int, _GEMM_ARGS),
+    'renet_gemm_f32_split': (c_int, _GEMM_ARGS),
+    'renet_gemm_bf16': (c_int, _GEMM_ARGS),
     'renet_gemm_split_plan': (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
     'renet_maxabs_blocks': (c_int, [c_int, c_int, c_int]),
     'renet_maxabs_partials_multi': (c_int, [c_void_p, c_int, c_void_p]),
@@ -73,8 +80,7 @@ _SIGNATURES = {
                                   c_void_p, c_int, c_void_p]),
     'renet_bf16_bytes': (c_size_t, [c_int, c_int]),
     'renet_pack_bf16': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
-    'renet_gemm_bf16s': (c_int, [c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p, c_int,
-                                 c_float, c_void_p, c_int, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    'renet_gemm_bf16s': (c_int, _GEMM_ARGS),
     'renet_bf16_zero_padding': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     'renet_seq_assemble_fwd_bf16': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                             c_void_p, c_int, c_int, c_float, c_u64, c_u64, c_void_p, c_int, c_void_p,
@@ -118,21 +124,15 @@ _SIGNATURES = {
                                     c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     'renet_gru_bwd_multi': (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_size_t, c_void_p]),
-    'renet_gru_fwd_layouts': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                                      c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    'renet_gru_bwd_layouts': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                                      c_void_p, c_void_p, c_size_t, c_void_p]),
+    'renet_gru_fwd_layouts': (c_int, _GRU_FWD_LAYOUTS_ARGS),
+    'renet_gru_bwd_layouts': (c_int, _GRU_BWD_LAYOUTS_ARGS),
     'renet_gru_bound_parts': (c_int, [c_int]),
     'renet_gru_bwd_layouts_bounds': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                              c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    'renet_gru_fwd_layouts_f32': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                                           c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    'renet_gru_bwd_layouts_f32': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                                           c_void_p, c_void_p, c_size_t, c_void_p]),
-    'renet_gru_fwd_layouts_bf16': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                                           c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    'renet_gru_bwd_layouts_bf16': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                                           c_void_p, c_void_p, c_size_t, c_void_p]),
+    'renet_gru_fwd_layouts_f32': (c_int, _GRU_FWD_LAYOUTS_ARGS),
+    'renet_gru_bwd_layouts_f32': (c_int, _GRU_BWD_LAYOUTS_ARGS),
+    'renet_gru_fwd_layouts_bf16': (c_int, _GRU_FWD_LAYOUTS_ARGS),
+    'renet_gru_bwd_layouts_bf16': (c_int, _GRU_BWD_LAYOUTS_ARGS),
     'renet_concat3_fwd': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float,
                                   c_u64, c_void_p, c_void_p]),
     'renet_concat3_fwd_bounds': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float,
@@ -229,20 +229,17 @@ def _check(rc, what):
         raise RenetHipError('%s failed with code %d' % (what, rc))
 
 
-def _f32(t, name='tensor'):
+def _dev_ptr(dtype, default_name, t, name=None):
+    """Device address of the contiguous tensor t of `dtype` (None stays None)."""
     if t is None:
         return None
-    if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
-        raise RenetHipError('%s must be a contiguous float32 device tensor' % name)
+    if not (t.is_cuda and t.dtype == dtype and t.is_contiguous()):
+        raise RenetHipError('%s must be a contiguous %s device tensor' % (name or default_name, str(dtype)[6:]))
     return t.data_ptr()
 
 
-def _i32(t, name='index'):
-    if t is None:
-        return None
-    if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()):
-        raise RenetHipError('%s must be a contiguous int32 device tensor' % name)
-    return t.data_ptr()
+_f32 = functools.partial(_dev_ptr, torch.float32, 'tensor')        # _f32(t, name='tensor')
+_i32 = functools.partial(_dev_ptr, torch.int32, 'index')           # _i32(t, name='index')
 
 
 _raw_stream = getattr(torch._C, '_cuda_getCurrentRawStream', None)
@@ -297,6 +294,17 @@ class KernelTimer(object):
 
 _timer = None
 
+
+def _timed():
+    """Start of a timed library call: the start event, None while no timer is installed.  Every wrapper with a timer class
+    of its own brackets its call with _timed() / _timed_end()."""
+    return _timer.begin() if _timer is not None else None
+
+
+def _timed_end(t0, name, flops=0.0, nbytes=0.0, tag=None):
+    if t0 is not None:
+        _timer.end(name, t0, flops=flops, nbytes=nbytes, tag=tag)
+
 # wrappers without a timer of their own (the step's small kernels): set_timer(t, glue=True) times each of them as class
 # 'glue:<name>' so that bench.py's `kernel_only` covers EVERY C-ABI launch of a step, not only the named classes
 GLUE = ('softmax_ce_planes', 'gather_rows', 'segment_add', 'segment_add2', 'compose_table_items', 'rgcn_bwd_prep', 'colsum',
@@ -307,8 +315,6 @@ _glue_saved = {}
 
 
 def _timed_glue(name, fn):
-    import functools
-
     @functools.wraps(fn)
     def call(*a, **k):
         t = _timer
@@ -363,7 +369,7 @@ def rgcn_gather(x, row_ptr, col, etype, scale, weight, type_shift, transpose_w, 
                 relu, out, heavy_rows=None, heavy_thresh=0, src_limit=0, addend_rows=0, n_edges=None):
     """n_edges: edges actually walked by this launch (pruned launches), for the byte accounting only."""
     n, d = x.shape[0], x.shape[1]
-    t0 = _timer.begin() if _timer is not None else None
+    t0 = _timed()
     _check(lib().renet_rgcn_gather(_f32(x), d, _i32(row_ptr), _i32(col), _i32(etype), _f32(scale),
                                    _f32(weight), weight.shape[0], type_shift, int(transpose_w),
                                    _f32(addend), float(drop_p), int(seed), int(relu), _f32(out),
@@ -378,7 +384,7 @@ def rgcn_gather(x, row_ptr, col, etype, scale, weight, type_shift, transpose_w, 
         nbytes = e * (d * 4 + 8) + nn * (d * 4 + 8) + weight.numel() * 4 + (nn * d * 4 if addend is not None else 0)
         # launches over the full batch graph (layer 1 and its backward) and the pruned ones (last layer:
         # subject rows only, a few thousand short rows -- launch-latency bound) are different regimes
-        _timer.end('rgcn_gather' if n_edges is None else 'rgcn_gather_pruned', t0, nbytes=float(nbytes))
+        _timed_end(t0, 'rgcn_gather' if n_edges is None else 'rgcn_gather_pruned', nbytes=float(nbytes))
     return out
 
 
@@ -408,7 +414,7 @@ def rgcn_gather_items(x, g, weight, type_shift, transpose_w, addend, drop_p, see
         return rgcn_gather(x, g.row_ptr, g.col, g.etype, g.norm if use_norm else None, weight, type_shift,
                            transpose_w, addend, drop_p, seed, relu, out, heavy, g.heavy_thresh, src_limit,
                            addend_rows, n_edges=g.E_out if pruned else None)
-    t0 = _timer.begin() if _timer is not None else None
+    t0 = _timed()
     hv, nhv = (_i32(heavy), heavy.numel()) if heavy is not None else (None, 0)
     if w16 is not None:
         _check(lib().renet_rgcn_gather_items_bf16(
@@ -426,7 +432,7 @@ def rgcn_gather_items(x, g, weight, type_shift, transpose_w, addend, drop_p, see
         e = g.E_out if pruned else g.E
         name = 'rgcn_gather_%s_%s' % ('bwdh' if transpose_w else 'fwd', 'pruned' if pruned else 'full')
         wb = 2 if w16 is not None else 4
-        _timer.end(name, t0, nbytes=float(gather_bytes(e, n_rows, d, weight.numel(), addend is not None, 4, wb)),
+        _timed_end(t0, name, nbytes=float(gather_bytes(e, n_rows, d, weight.numel(), addend is not None, 4, wb)),
                    tag=float(gather_bytes(e, n_rows, d, weight.numel(), False, 4, wb)))       # tag: the strict bytes
     return out
 
@@ -464,7 +470,7 @@ def rgcn_gather_items_table(table, g, weight, type_shift, addend_table, drop_p, 
     n_rows = out.shape[0]
     it_src_t, it_type_t, col_t, _ = g.table_items()
     heavy = g.heavy_rows
-    t0 = _timer.begin() if _timer is not None else None
+    t0 = _timed()
     if table16 is not None and w16 is not None:
         _check(lib().renet_rgcn_gather_items_table_bf16(
             table16.p.data_ptr(), table16.p.shape[1], table.shape[0], d, _i32(it_src_t), _i32(it_type_t),
@@ -481,7 +487,7 @@ def rgcn_gather_items_table(table, g, weight, type_shift, addend_table, drop_p, 
             'rgcn_gather_items_table')
     if t0 is not None:          # SURVEY 8d's ALGORITHMIC bytes: one source row per edge, one output (+ addend) row per node
         eb = 2 if (table16 is not None and w16 is not None) else 4
-        _timer.end('rgcn_gather_fwd_full', t0,
+        _timed_end(t0, 'rgcn_gather_fwd_full',
                    nbytes=float(gather_bytes(g.E, n_rows, d, weight.numel(), addend_table is not None, eb, eb)),
                    tag=float(gather_bytes(g.E, n_rows, d, weight.numel(), False, eb, eb)))
     return out
@@ -489,16 +495,11 @@ def rgcn_gather_items_table(table, g, weight, type_shift, addend_table, drop_p, 
 
 def rgcn_bwd_prep(g_out, out, norm, relu, drop_p, seed, gn, g_loop):
     n, d = g_out.shape
+    args = (_f32(g_out), _f32(out), _f32(norm), int(relu), float(drop_p), int(seed), n, d, _f32(gn), _f32(g_loop))
     if _fused_bounds(g_loop):                    # g_loop's operand bound comes out of the kernel that writes it
-        nparts = lib().renet_bound_parts(n * (d // 4))
-        part = torch.empty(nparts, device=g_loop.device, dtype=torch.float32)
-        _check(lib().renet_rgcn_bwd_prep_bounds(_f32(g_out), _f32(out), _f32(norm), int(relu), float(drop_p),
-                                                int(seed), n, d, _f32(gn), _f32(g_loop), part.data_ptr(), _stream()),
-               'rgcn_bwd_prep_bounds')
-        _note_bound(g_loop, part, nparts)
+        _call_with_bounds('rgcn_bwd_prep_bounds', args, n * (d // 4), (g_loop,))
         return
-    _check(lib().renet_rgcn_bwd_prep(_f32(g_out), _f32(out), _f32(norm), int(relu), float(drop_p),
-                                     int(seed), n, d, _f32(gn), _f32(g_loop), _stream()), 'rgcn_bwd_prep')
+    _check(lib().renet_rgcn_bwd_prep(*args, _stream()), 'rgcn_bwd_prep')
 
 
 def rgcn_bwd_w(x, gn, e_src, e_dst, chunk_ptr, chunk_type, n_chunks, type_chunk_ptr, num_types, type_shift,
@@ -509,13 +510,13 @@ def rgcn_bwd_w(x, gn, e_src, e_dst, chunk_ptr, chunk_type, n_chunks, type_chunk_
     big = max(x.numel(), gn.numel()) * 4 >= (1 << 31) or os.environ.get('RENET_BWDW_64') == '1'
     nbytes = lib().renet_rgcn_bwd_w_workspace(n_chunks, d)
     ws = torch.empty(max(nbytes // 4, 1), device=x.device, dtype=torch.float32)
-    t0 = _timer.begin() if _timer is not None else None
+    t0 = _timed()
     fn = lib().renet_rgcn_bwd_w64 if big else lib().renet_rgcn_bwd_w
     _check(fn(_f32(x), _f32(gn), _i32(e_src), _i32(e_dst), _i32(chunk_ptr), _i32(chunk_type), n_chunks,
               _i32(type_chunk_ptr), num_types, type_shift, d, _f32(dW), float(beta), ws.data_ptr(), nbytes, _stream()),
            'rgcn_bwd_w')
-    if t0 is not None:      # SURVEY 8d backward-W: E * 2 rows + indices, dW written once
-        _timer.end('rgcn_bwd_w', t0, nbytes=float(e_src.numel() * (2 * d * 4 + 8) + dW.numel() * 4))
+    # SURVEY 8d backward-W: E * 2 rows + indices, dW written once
+    _timed_end(t0, 'rgcn_bwd_w', nbytes=float(e_src.numel() * (2 * d * 4 + 8) + dW.numel() * 4))
     return dW
 
 
@@ -529,7 +530,6 @@ def gemm_split_plan(ta, tb, m, n, k, lda=None, ldb=None, split_k=1, a_ptr=0, b_p
     """What renet_gemm_f32_split would launch for this problem (host logic only, no GPU needed): dict with `kernel`
     ('fused' | 'two_phase_128' | 'two_phase_256' | 'weight_resident'), `raw` (raw-buffer loader), `xcd_order` (0 = plain
     tile order, w = XCD-aware order with panels of <= w tiles), `grid`, `split_k`."""
-    import ctypes
     lda = (m if ta else k) if lda is None else lda
     ldb = (k if tb else n) if ldb is None else ldb
     out = (ctypes.c_int * 8)()
@@ -548,19 +548,47 @@ def auto_split_k(m, n, k):
     It reproduces the factors swept on MI355X (tools/gemm_sweep.py: dfeat 40 tiles -> 12 slices, dW_ih 35 -> 14,
     dW_loop 4 -> 128) and, unlike a pure fill heuristic, still splits a single-tile output (n_hidden = 100:
     100x100xK=46k would otherwise run 1440 k-tiles in ONE workgroup)."""
-    tiles = ((m + 127) // 128) * ((n + 127) // 128)
+    return _split_k_model(m, n, k, tile_m=128, slots=512, full=256, smax=128)
+
+
+def _split_k_model(m, n, k, tile_m, slots, full, smax):
+    """auto_split_k's cost model on a grid of tile_m x 128 tiles with `slots` workgroups per round: no split from `full` tiles
+    on, at most `smax` slices."""
+    tiles = ((m + tile_m - 1) // tile_m) * ((n + 127) // 128)
     ktiles = (k + 31) // 32
-    if tiles >= 256 or ktiles < 8:
+    if tiles >= full or ktiles < 8:
         return 1
-    smax = int(max(1, min(128, ktiles // 4)))
     per_slice = m * n * 2.7e-6
     best, best_t = 1, None
-    for s in range(1, smax + 1):
-        rounds = (tiles * s + 511) // 512
+    for s in range(1, max(1, min(smax, ktiles // 4)) + 1):
+        rounds = (tiles * s + slots - 1) // slots
         t = rounds * (ktiles / float(s) + 6.0) + (per_slice * s if s > 1 else 0.0)
         if best_t is None or t < best_t - 1e-9:
             best, best_t = s, t
     return best
+
+
+def _gemm_front(what, m, n, k, k2, out, beta, split_k, device, n_out=None, planes=False):
+    """What gemm, gemm_bf16s and gemm_planes do before their library call, for the [m, n] = [m, k] @ [k2, n] product whose
+    `out` has n_out (default n) columns; planes: gemm_planes' grid -> (out, split_k, split-K workspace or None, its bytes)."""
+    if k != k2:
+        raise RenetHipError('%s inner dimensions differ: %d vs %d' % (what, k, k2))
+    if out is None:
+        if beta != 0.0:
+            raise RenetHipError('beta != 0 needs an output tensor')
+        out = torch.empty(m, n if n_out is None else n_out, device=device, dtype=torch.float32)
+    if split_k is None:
+        split_k = (auto_split_k_planes if planes else auto_split_k)(m, n, k)
+    ws, ws_bytes = None, 0
+    if split_k > 1:
+        ws_bytes = lib().renet_gemm_workspace(m, n, split_k)
+        ws = torch.empty(ws_bytes // 4, device=device, dtype=torch.float32)
+    return out, split_k, ws, ws_bytes
+
+
+def _gemm_timed_end(t0, ta, tb, m, n, k, split_k):
+    if t0 is not None:
+        _timed_end(t0, 'gemm_f32', flops=2.0 * m * n * k, tag=(int(ta), int(tb), m, n, k, split_k))
 
 
 # 'bf16s'  : bf16 STORAGE: operands are (packed to) bf16 matrices in HBM, LDS-DMA staging, one bf16 MFMA product
@@ -634,57 +662,102 @@ def pack_bf16(x):
     r, c = x.shape
     rp, cp = (r + 255) & ~255, (c + 255) & ~255
     p = torch.empty(rp, cp, device=x.device, dtype=torch.bfloat16)
-    t0 = _timer.begin() if _timer is not None else None
+    t0 = _timed()
     _check(lib().renet_pack_bf16(x.data_ptr(), r, c, x.stride(0), p.data_ptr(), _stream()), 'pack_bf16')
-    if t0 is not None:
-        _timer.end('pack_bf16', t0, nbytes=float(r * c * 4 + rp * cp * 2))
+    _timed_end(t0, 'pack_bf16', nbytes=float(r * c * 4 + rp * cp * 2))
     return BF16Mat(p, r, c)
 
 
-# bf16 copies of WEIGHTS are cached between optimizer steps: parallel.HipAdam registers its parameters (stable
-# addresses inside the flat buffer) and bumps the epoch after every update; any other tensor is packed on every use.
-_weight_ptrs = {}              # data_ptr -> (rows, cols)
-_weight_cache = {}             # data_ptr -> (epoch, BF16Mat)
+class _StreamGuard(object):
+    """Orders consumers on OTHER streams behind the launch that filled a cached device buffer (ADVICE r3: the first
+    bound request after an optimizer step may come from ops._Side's side stream; a main-stream GEMM that then hits
+    the cache must not read the partial maxima before that launch has run).  Created right behind the producing
+    launch on the producing stream; wait() is free on that same stream."""
+    __slots__ = ('stream', 'event')
+
+    def __init__(self, device):
+        self.stream = torch.cuda.current_stream(device)
+        self.event = torch.cuda.Event()
+        self.event.record(self.stream)
+
+    def wait(self, device):
+        cur = torch.cuda.current_stream(device)
+        if cur != self.stream:
+            cur.wait_event(self.event)
+
+
+# What is derived from a WEIGHT is cached between optimizer steps: parallel.HipAdam registers its parameters (stable
+# addresses inside the flat buffer) and bumps the epoch after every update; any other tensor is packed / measured on every use.
+class _Weight(object):
+    """A registered weight: its shape, the tensor (weakly: its torch version counter is read) and the forms derived from it
+    -- the bf16 copy (BF16Mat), the planes (PlanesMat), the partial maxima ((part, n)) -- each None or one entry
+    (stamp, value, _StreamGuard or None) that holds while stamp == _weight_stamp(tensor)."""
+    __slots__ = ('shape', 'ref', 'bf16', 'planes', 'maxima')
+
+    def __init__(self):
+        self.bf16 = self.planes = self.maxima = None
+
+
+_weights = {}                  # data_ptr -> _Weight
 _weight_epoch = [0]
 
 
 def register_weights(tensors):
-    import weakref
     for t in tensors:
         if t.dim() == 2 and t.is_contiguous():
-            _weight_ptrs[t.data_ptr()] = tuple(t.shape)
-            _weight_objs[t.data_ptr()] = weakref.ref(t)
+            rec = _weights.setdefault(t.data_ptr(), _Weight())
+            rec.shape, rec.ref = tuple(t.shape), weakref.ref(t)
 
 
 def unregister_weights(tensors):
     for t in tensors:
-        _weight_ptrs.pop(t.data_ptr(), None)
-        _weight_cache.pop(t.data_ptr(), None)
-        _weight_planes.pop(t.data_ptr(), None)
-        _weight_max.pop(t.data_ptr(), None)
-        _weight_objs.pop(t.data_ptr(), None)
+        _weights.pop(t.data_ptr(), None)
 
 
 def weights_changed():
     _weight_epoch[0] += 1
 
 
+def _weight_stamp(t):
+    return (_weight_epoch[0], t._version)           # in-place torch writes (load_state_dict) bump _version
+
+
+def _registered(x, whole=False):
+    """The record of the registered weight that tensor x is or is a leading row / column block of (W_ih[:, :live]), else
+    None.  whole=True: only the weight itself counts."""
+    rec = _weights.get(x.data_ptr())
+    if rec is None or x.dim() != 2:
+        return None
+    if whole:
+        return rec if tuple(x.shape) == rec.shape and x.is_contiguous() else None
+    rows, cols = rec.shape
+    return rec if x.stride(1) == 1 and x.stride(0) == cols and x.shape[0] <= rows and x.shape[1] <= cols else None
+
+
+def _whole(x, rec):
+    """The registered matrix of which x is a leading block."""
+    return torch.as_strided(x, rec.shape, (rec.shape[1], 1))
+
+
+def _derived(rec, form, x, make, guarded=True):
+    """The value of rec's derived form `form` for weight (block) x as it is now: make() when there is none or the weight
+    changed since.  guarded: a consumer on another stream is ordered behind the launch that made it."""
+    ent, stamp = getattr(rec, form), _weight_stamp(x)
+    if ent is None or ent[0] != stamp:
+        ent = (stamp, make(), _StreamGuard(x.device) if guarded else None)
+        setattr(rec, form, ent)
+    if ent[2] is not None:
+        ent[2].wait(x.device)                       # (no-op on the stream that made it)
+    return ent[1]
+
+
 def _as_bf16(x):
     """Operand of gemm_bf16s for tensor / BF16Mat x -> (BF16Mat, rows, cols) of the LOGICAL matrix x."""
     if isinstance(x, BF16Mat):
         return x, x.R, x.C
-    ptr = x.data_ptr()
-    shp = _weight_ptrs.get(ptr)
-    if shp is not None and x.dim() == 2 and x.stride(1) == 1 and x.stride(0) == shp[1] and \
-            x.shape[0] <= shp[0] and x.shape[1] <= shp[1]:
-        # a registered weight, or a leading row / column block of it (W_ih[:, :live]): one cached copy serves both
-        ent = _weight_cache.get(ptr)
-        stamp = (_weight_epoch[0], x._version)      # in-place torch writes (load_state_dict) bump _version
-        if ent is None or ent[0] != stamp:
-            full = torch.as_strided(x, shp, (shp[1], 1))
-            ent = (stamp, pack_bf16(full))
-            _weight_cache[ptr] = ent
-        return ent[1], x.shape[0], x.shape[1]
+    rec = _registered(x)
+    if rec is not None:                             # one cached copy of the whole weight serves its leading blocks too
+        return _derived(rec, 'bf16', x, lambda: pack_bf16(_whole(x, rec)), guarded=False), x.shape[0], x.shape[1]
     m = pack_bf16(x)
     return m, m.R, m.C
 
@@ -742,36 +815,25 @@ def pack_planes(x, ones_col=False):
         raise RenetHipError('pack_planes needs a 2-D float32 device tensor with unit inner stride')
     r, c = x.shape
     m = planes_empty(r, c + (1 if ones_col else 0), x.device)
-    t0 = _timer.begin() if _timer is not None else None
+    t0 = _timed()
     _check(lib().renet_pack_planes(x.data_ptr(), r, c, x.stride(0), int(bool(ones_col)), m.p.data_ptr(), _stream()),
            'pack_planes')
-    if t0 is not None:
-        _timer.end('pack_planes', t0, nbytes=float(r * c * 4 + 3 * m.plane * 2))
+    _timed_end(t0, 'pack_planes', nbytes=float(r * c * 4 + 3 * m.plane * 2))
     return m
-
-
-_weight_planes = {}            # data_ptr -> ((epoch, version), PlanesMat) of a registered weight
 
 
 def weight_planes(w):
     """Planes of a weight matrix: a registered weight (parallel.HipAdam) is packed once per optimizer step -- or not at
     all when the optimizer kernel wrote them (note_weight_planes) -- anything else on every call."""
-    ptr = w.data_ptr()
-    shp = _weight_ptrs.get(ptr)
-    if shp is not None and tuple(w.shape) == tuple(shp) and w.is_contiguous():
-        stamp = (_weight_epoch[0], w._version)
-        ent = _weight_planes.get(ptr)
-        if ent is None or ent[0] != stamp:
-            ent = (stamp, pack_planes(w), _StreamGuard(w.device))
-            _weight_planes[ptr] = ent
-        ent[2].wait(w.device)
-        return ent[1]
-    return pack_planes(w)
+    rec = _registered(w, whole=True)
+    return _derived(rec, 'planes', w, lambda: pack_planes(w)) if rec is not None else pack_planes(w)
 
 
 def note_weight_planes(w, mat):
     """The optimizer kernel has just written `mat` = the planes of the UPDATED weight w (call after weights_changed())."""
-    _weight_planes[w.data_ptr()] = ((_weight_epoch[0], w._version), mat, _StreamGuard(w.device))
+    rec = _registered(w, whole=True)
+    if rec is not None:
+        rec.planes = (_weight_stamp(w), mat, _StreamGuard(w.device))
 
 
 def use_planes(weight, n_classes):
@@ -782,19 +844,7 @@ def use_planes(weight, n_classes):
 
 def auto_split_k_planes(m, n, k):
     """Split-K factor of gemm_planes (256 x 128 tiles, one workgroup per CU): auto_split_k's cost model on that grid."""
-    tiles = ((m + 255) // 256) * ((n + 127) // 128)
-    ktiles = (k + 31) // 32
-    if tiles >= 128 or ktiles < 8:
-        return 1
-    smax = int(max(1, min(64, ktiles // 4)))
-    per_slice = m * n * 2.7e-6
-    best, best_t = 1, None
-    for s_ in range(1, smax + 1):
-        rounds = (tiles * s_ + 255) // 256
-        t = rounds * (ktiles / float(s_) + 6.0) + (per_slice * s_ if s_ > 1 else 0.0)
-        if best_t is None or t < best_t - 1e-9:
-            best, best_t = s_, t
-    return best
+    return _split_k_model(m, n, k, tile_m=256, slots=256, full=128, smax=64)
 
 
 def gemm_planes(a, b, ta=False, tb=False, out=None, bias=None, alpha=1.0, alpha_dev=None, beta=0.0, col_out=None,
@@ -806,32 +856,19 @@ def gemm_planes(a, b, ta=False, tb=False, out=None, bias=None, alpha=1.0, alpha_
         raise RenetHipError('gemm_planes needs PlanesMat operands')
     m, k = (a.C, a.R) if ta else (a.R, a.C)
     n, k2 = (b.R, b.C) if tb else (b.C, b.R)
-    if k != k2:
-        raise RenetHipError('gemm_planes inner dimensions differ: %d vs %d' % (k, k2))
     n_main = n - 1 if col_out is not None else n
-    dev = a.p.device
-    if out is None:
-        if beta != 0.0:
-            raise RenetHipError('beta != 0 needs an output tensor')
-        out = torch.empty(m, n_main, device=dev, dtype=torch.float32)
+    out, split_k, ws, ws_bytes = _gemm_front('gemm_planes', m, n, k, k2, out, beta, split_k, a.p.device, n_out=n_main,
+                                             planes=True)
     if tuple(out.shape) != (m, n_main):
         raise RenetHipError('gemm_planes: output shape %r, expected %r' % (tuple(out.shape), (m, n_main)))
     if col_out is not None and (col_out.numel() != m or not col_out.is_contiguous()):
         raise RenetHipError('gemm_planes: col_out must be a contiguous vector of M floats')
-    if split_k is None:
-        split_k = auto_split_k_planes(m, n, k)
-    ws_ptr, ws_bytes = None, 0
-    if split_k > 1:
-        ws_bytes = lib().renet_gemm_workspace(m, n, split_k)
-        ws = torch.empty(ws_bytes // 4, device=dev, dtype=torch.float32)
-        ws_ptr = ws.data_ptr()
-    t0 = _timer.begin() if _timer is not None else None
+    t0 = _timed()
     _check(lib().renet_gemm_planes(int(ta), int(not tb), m, n, k, float(alpha), _f32(alpha_dev), a.p.data_ptr(),
                                    a.p.shape[2], a.plane, b.p.data_ptr(), b.p.shape[2], b.plane, float(beta),
-                                   out.data_ptr(), _ld(out), _f32(bias), _f32(col_out), split_k, ws_ptr, ws_bytes,
+                                   out.data_ptr(), _ld(out), _f32(bias), _f32(col_out), split_k, _f32(ws), ws_bytes,
                                    _stream()), 'gemm_planes')
-    if t0 is not None:
-        _timer.end('gemm_f32', t0, flops=2.0 * m * n_main * k, tag=(int(ta), int(tb), m, n_main, k, split_k))
+    _gemm_timed_end(t0, ta, tb, m, n_main, k, split_k)
     return out
 
 
@@ -879,50 +916,27 @@ def maxabs_partials(x):
     rows, cols = x.shape
     n = lib().renet_maxabs_blocks(rows, cols, _ld(x))
     part = torch.empty(n, device=x.device, dtype=torch.float32)
-    t0 = _timer.begin() if _timer is not None else None
+    t0 = _timed()
     _check(lib().renet_maxabs_partials(x.data_ptr(), rows, cols, _ld(x), part.data_ptr(), _stream()),
            'maxabs_partials')
-    if t0 is not None:
-        _timer.end('maxabs', t0, nbytes=float(rows * cols * 4))
+    _timed_end(t0, 'maxabs', nbytes=float(rows * cols * 4))
     return part, n
 
 
-_weight_max = {}               # data_ptr -> (stamp, part, n, guard) of a registered weight
-
-
-class _StreamGuard(object):
-    """Orders consumers on OTHER streams behind the launch that filled a cached device buffer (ADVICE r3: the first
-    bound request after an optimizer step may come from ops._Side's side stream; a main-stream GEMM that then hits
-    the cache must not read the partial maxima before that launch has run).  Created right behind the producing
-    launch on the producing stream; wait() is free on that same stream."""
-    __slots__ = ('stream', 'event')
-
-    def __init__(self, device):
-        self.stream = torch.cuda.current_stream(device)
-        self.event = torch.cuda.Event()
-        self.event.record(self.stream)
-
-    def wait(self, device):
-        cur = torch.cuda.current_stream(device)
-        if cur != self.stream:
-            cur.wait_event(self.event)
-
-
 _weight_jobs = {'key': None, 'table': None, 'parts': {}}     # one multi-array launch for all registered weights
-_weight_objs = {}              # data_ptr -> weakref of the registered weight (its torch version counter is read)
 
 
 def _measure_all_weights(device):
-    """-> {data_ptr: ((epoch, version), part, n)} for EVERY registered weight that is alive, contiguous, 16-byte aligned
-    and a multiple of 4 elements long, from one launch (renet_maxabs_partials_multi)."""
-    live = {p: r() for p, r in _weight_objs.items()}
-    ptrs = sorted(p for p, t in live.items() if t is not None and t.is_cuda and t.device == device and p in _weight_ptrs
+    """Measures the maxima of EVERY registered weight that is alive, contiguous, 16-byte aligned and a multiple of 4 elements
+    long with one launch (renet_maxabs_partials_multi)."""
+    live = {p: rec.ref() for p, rec in _weights.items()}
+    ptrs = sorted(p for p, t in live.items() if t is not None and t.is_cuda and t.device == device
                   and t.numel() % 4 == 0 and p % 16 == 0 and t.data_ptr() == p)
     key = (tuple(ptrs), str(device))
     if _weight_jobs['key'] != key:
         rows, parts = [], {}
         for p in ptrs:
-            shp = _weight_ptrs[p]
+            shp = _weights[p].shape
             nb = lib().renet_maxabs_blocks(shp[0], shp[1], shp[1])
             part = torch.empty(nb, device=device, dtype=torch.float32)
             parts[p] = (part, nb)
@@ -930,43 +944,35 @@ def _measure_all_weights(device):
         _weight_jobs.update(key=key, parts=parts,
                             table=torch.tensor(rows, dtype=torch.int64).to(device) if rows else None)
     if _weight_jobs['table'] is None:
-        return {}
-    t0 = _timer.begin() if _timer is not None else None
+        return
+    t0 = _timed()
     _check(lib().renet_maxabs_partials_multi(_weight_jobs['table'].data_ptr(), len(ptrs), _stream()),
            'maxabs_partials_multi')
     if t0 is not None:
-        _timer.end('maxabs', t0, nbytes=float(sum(_weight_ptrs[p][0] * _weight_ptrs[p][1] * 4 for p in ptrs)))
+        _timed_end(t0, 'maxabs', nbytes=float(sum(_weights[p].shape[0] * _weights[p].shape[1] * 4 for p in ptrs)))
     guard = _StreamGuard(device)
-    return {p: ((_weight_epoch[0], live[p]._version), part, nb, guard) for p, (part, nb) in _weight_jobs['parts'].items()}
+    for p, bound in _weight_jobs['parts'].items():
+        _weights[p].maxima = (_weight_stamp(live[p]), bound, guard)
 
 
 def prefetch_weight_bounds(device):
     """Measure every registered weight NOW, on the current stream (parallel.HipAdam.step calls this right behind the
     update, on the stream the step runs on): the f16x3 GEMMs of the next step then only ever hit the cache."""
-    if current_mode() == 'f16x3' and _weight_ptrs:
-        _weight_max.update(_measure_all_weights(device))
+    if current_mode() == 'f16x3' and _weights:
+        _measure_all_weights(device)
 
 
 def _weight_or_measured_max(x):
     """A registered weight's maxima are cached until the next optimizer step (a leading row / column block of the
     weight is bounded by the whole weight's); anything else is measured."""
-    ptr = x.data_ptr()
-    shp = _weight_ptrs.get(ptr)
-    if shp is not None and x.dim() == 2 and x.stride(1) == 1 and x.stride(0) == shp[1] and \
-            x.shape[0] <= shp[0] and x.shape[1] <= shp[1]:
-        stamp = (_weight_epoch[0], x._version)      # in-place torch writes (load_state_dict) bump _version
-        ent = _weight_max.get(ptr)
-        if ent is None or ent[0][0] != _weight_epoch[0]:
-            # first request after an optimizer step: every registered weight changed -- ONE launch measures them all
-            _weight_max.update(_measure_all_weights(x.device))
-            ent = _weight_max.get(ptr)
-        if ent is None or ent[0] != stamp:          # not coverable by the joint launch, or modified since: on its own
-            part, n = maxabs_partials(torch.as_strided(x, shp, (shp[1], 1)))
-            ent = (stamp, part, n, _StreamGuard(x.device))
-            _weight_max[ptr] = ent
-        ent[3].wait(x.device)                       # (no-op on the stream that measured)
-        return ent[1], ent[2]
-    return maxabs_partials(x)
+    rec = _registered(x)
+    if rec is None:
+        return maxabs_partials(x)
+    if rec.maxima is None or rec.maxima[0][0] != _weight_epoch[0]:
+        # first request after an optimizer step: every registered weight changed -- ONE launch measures them all
+        _measure_all_weights(x.device)
+    # (not coverable by the joint launch, or modified since: on its own)
+    return _derived(rec, 'maxima', x, lambda: maxabs_partials(_whole(x, rec)))
 
 
 def _f32op(x, bound=None):
@@ -1021,13 +1027,22 @@ def _note_bound(t, part, n):
     t._renet_bound = (part, n)
 
 
+def _call_with_bounds(entry, args, elems, outs):
+    """The `_bounds` variant of a producer kernel: renet_<entry>(*args, one block of partial maxima per tensor of `outs`,
+    stream), the blocks sized for `elems` units of work and noted on the tensors they bound."""
+    nparts = lib().renet_bound_parts(elems)
+    parts = torch.empty(len(outs), nparts, device=outs[0].device, dtype=torch.float32)
+    _check(getattr(lib(), 'renet_' + entry)(*args, *[p.data_ptr() for p in parts], _stream()), entry)
+    for t, p in zip(outs, parts):
+        _note_bound(t, p, nparts)
+
+
 _lazy_shells = {}          # (data_ptr, shape) of an uninitialised fp32 shell -> the BF16Mat it stands for
 
 
 def lazy_shell(mat, device):
     """fp32 tensor of mat's logical shape whose VALUES ARE NEVER WRITTEN: the autograd-visible stand-in of a tensor
     that exists only as a bf16 operand matrix (bf16-storage mode); operand() resolves it to `mat`."""
-    import weakref
     x = torch.empty(mat.R, mat.C, device=device, dtype=torch.float32)
     x._renet_bf16 = mat
     key = (x.data_ptr(), (mat.R, mat.C))
@@ -1083,25 +1098,12 @@ def gemm_bf16s(a, b, ta=False, tb=False, out=None, bias=None, alpha=1.0, beta=0.
     pb, br, bc = prep(b, 1 if tb else 0)
     m, k = (ac, ar) if ta else (ar, ac)
     n, k2 = (br, bc) if tb else (bc, br)
-    if k != k2:
-        raise RenetHipError('gemm inner dimensions differ: %d vs %d' % (k, k2))
-    if out is None:
-        if beta != 0.0:
-            raise RenetHipError('beta != 0 needs an output tensor')
-        out = torch.empty(m, n, device=pa.p.device, dtype=torch.float32)
-    if split_k is None:
-        split_k = auto_split_k(m, n, k)
-    ws_ptr, ws_bytes = None, 0
-    if split_k > 1:
-        ws_bytes = lib().renet_gemm_workspace(m, n, split_k)
-        ws = torch.empty(ws_bytes // 4, device=out.device, dtype=torch.float32)
-        ws_ptr = ws.data_ptr()
-    t0 = _timer.begin() if _timer is not None else None
+    out, split_k, ws, ws_bytes = _gemm_front('gemm', m, n, k, k2, out, beta, split_k, pa.p.device)
+    t0 = _timed()
     _check(lib().renet_gemm_bf16s(int(ta), int(not tb), m, n, k, float(alpha), pa.p.data_ptr(), pa.p.shape[1],
                                   pb.p.data_ptr(), pb.p.shape[1], float(beta), out.data_ptr(), _ld(out), _f32(bias),
-                                  split_k, ws_ptr, ws_bytes, _stream()), 'gemm_bf16s')
-    if t0 is not None:
-        _timer.end('gemm_f32', t0, flops=2.0 * m * n * k, tag=(int(ta), int(tb), m, n, k, split_k))
+                                  split_k, _f32(ws), ws_bytes, _stream()), 'gemm_bf16s')
+    _gemm_timed_end(t0, ta, tb, m, n, k, split_k)
     return out
 
 
@@ -1120,62 +1122,39 @@ def gemm(a, b, ta=False, tb=False, out=None, bias=None, alpha=1.0, beta=0.0, spl
         raise RenetHipError('gemm operands must be float32 device tensors')
     m, k = (a.shape[1], a.shape[0]) if ta else (a.shape[0], a.shape[1])
     k2, n = (b.shape[1], b.shape[0]) if tb else (b.shape[0], b.shape[1])
-    if k != k2:
-        raise RenetHipError('gemm inner dimensions differ: %d vs %d' % (k, k2))
-    if out is None:
-        out = torch.empty(m, n, device=a.device, dtype=torch.float32)
-        if beta != 0.0:
-            raise RenetHipError('beta != 0 needs an output tensor')
-    if split_k is None:
-        split_k = auto_split_k(m, n, k)
-    ws_ptr, ws_bytes = None, 0
-    if split_k > 1:
-        ws_bytes = lib().renet_gemm_workspace(m, n, split_k)
-        ws = torch.empty(ws_bytes // 4, device=a.device, dtype=torch.float32)
-        ws_ptr = ws.data_ptr()
+    out, split_k, ws, ws_bytes = _gemm_front('gemm', m, n, k, k2, out, beta, split_k, a.device)
     if md == 'f16x3' and _skinny_shape(ta, m, n, k, a, b, split_k):
         md = 'bf16x6'
     if md == 'f16x3':
         (pa, na), (pb, nb) = _f32op(opa).bound(), _f32op(opb).bound()     # (measured outside the GEMM's timer)
-    t0 = _timer.begin() if _timer is not None else None
+    t0 = _timed()
     if md == 'f16x3':
         _check(lib().renet_gemm_f32_h3(int(ta), int(tb), m, n, k, float(alpha), a.data_ptr(), _ld(a), b.data_ptr(),
-                                       _ld(b), float(beta), out.data_ptr(), _ld(out), _f32(bias), split_k, ws_ptr,
+                                       _ld(b), float(beta), out.data_ptr(), _ld(out), _f32(bias), split_k, _f32(ws),
                                        ws_bytes, pa.data_ptr(), na, pb.data_ptr(), nb, _stream()),
                'gemm_f32_h3')
     else:
         fn = lib().renet_gemm_f32_split if md == 'bf16x6' else lib().renet_gemm_bf16 if md == 'bf16' else \
             lib().renet_gemm_f32
         _check(fn(int(ta), int(tb), m, n, k, float(alpha), a.data_ptr(), _ld(a), b.data_ptr(),
-                  _ld(b), float(beta), out.data_ptr(), _ld(out), _f32(bias), split_k, ws_ptr,
+                  _ld(b), float(beta), out.data_ptr(), _ld(out), _f32(bias), split_k, _f32(ws),
                   ws_bytes, _stream()), 'gemm_f32')
-    if t0 is not None:
-        _timer.end('gemm_f32', t0, flops=2.0 * m * n * k, tag=(int(ta), int(tb), m, n, k, split_k))
+    _gemm_timed_end(t0, ta, tb, m, n, k, split_k)
     return out
 
 
 def colsum(x, out=None, beta=0.0):
     """out = beta * out + column sums of x (fp32 tensor or BF16Mat)."""
-    if isinstance(x, BF16Mat):
-        m, n = x.R, x.C
-        if out is None:
-            if beta != 0.0:
-                raise RenetHipError('beta != 0 needs an output tensor')
-            out = torch.empty(n, device=x.p.device, dtype=torch.float32)
-        nbytes = lib().renet_colsum_workspace(m, n)
-        ws = torch.empty(nbytes // 4, device=x.p.device, dtype=torch.float32) if nbytes else None
-        _check(lib().renet_colsum_bf16(x.p.data_ptr(), m, n, x.p.shape[1], _f32(out), float(beta),
-                                       ws.data_ptr() if nbytes else None, nbytes, _stream()), 'colsum_bf16')
-        return out
+    fn, what, t = (lib().renet_colsum_bf16, 'colsum_bf16', x.p) if isinstance(x, BF16Mat) else \
+        (lib().renet_colsum, 'colsum', x)
     m, n = x.shape
     if out is None:
         if beta != 0.0:
             raise RenetHipError('beta != 0 needs an output tensor')
-        out = torch.empty(n, device=x.device, dtype=torch.float32)
+        out = torch.empty(n, device=t.device, dtype=torch.float32)
     nbytes = lib().renet_colsum_workspace(m, n)
-    ws = torch.empty(nbytes // 4, device=x.device, dtype=torch.float32) if nbytes else None
-    _check(lib().renet_colsum(x.data_ptr(), m, n, _ld(x), _f32(out), float(beta), ws.data_ptr() if nbytes else None,
-                              nbytes, _stream()), 'colsum')
+    ws = torch.empty(nbytes // 4, device=t.device, dtype=torch.float32) if nbytes else None
+    _check(fn(t.data_ptr(), m, n, _ld(t), _f32(out), float(beta), _f32(ws), nbytes, _stream()), what)
     return out
 
 
@@ -1204,20 +1183,12 @@ def seq_assemble_fwd(h2, ent, rel, glob, subj_row, row_ent, row_rel, glob_row, d
     s, d = subj_row.numel(), h2.shape[1]
     x = torch.empty(s, 4 * d, device=h2.device, dtype=torch.float32)
     xr = torch.empty(s, 3 * d, device=h2.device, dtype=torch.float32)
+    args = (_f32(h2), _f32(ent), _f32(rel), _f32(glob), _i32(subj_row), _i32(row_ent), _i32(row_rel), _i32(glob_row), s, d,
+            float(drop_p), int(seed_x), int(seed_xr), _f32(x), _f32(xr))
     if _fused_bounds(x):                         # the operand bounds of X / Xr come out of the kernel that writes them
-        nparts = lib().renet_bound_parts(s * d)
-        parts = torch.empty(2, nparts, device=h2.device, dtype=torch.float32)
-        _check(lib().renet_seq_assemble_fwd_bounds(_f32(h2), _f32(ent), _f32(rel), _f32(glob), _i32(subj_row),
-                                                   _i32(row_ent), _i32(row_rel), _i32(glob_row), s, d, float(drop_p),
-                                                   int(seed_x), int(seed_xr), _f32(x), _f32(xr), parts[0].data_ptr(),
-                                                   parts[1].data_ptr(), _stream()), 'seq_assemble_fwd_bounds')
-        _note_bound(x, parts[0], nparts)
-        _note_bound(xr, parts[1], nparts)
-        return x, xr
-    _check(lib().renet_seq_assemble_fwd(_f32(h2), _f32(ent), _f32(rel), _f32(glob), _i32(subj_row),
-                                        _i32(row_ent), _i32(row_rel), _i32(glob_row), s, d, float(drop_p),
-                                        int(seed_x), int(seed_xr), _f32(x), _f32(xr), _stream()),
-           'seq_assemble_fwd')
+        _call_with_bounds('seq_assemble_fwd_bounds', args, s * d, (x, xr))
+    else:
+        _check(lib().renet_seq_assemble_fwd(*args, _stream()), 'seq_assemble_fwd')
     return x, xr
 
 
@@ -1294,14 +1265,11 @@ def _gru_call(n, step_offs, hdim, operands):
     return (bmax, ws, nbytes) + _offs(step_offs)
 
 
-@contextlib.contextmanager
-def _gru_timed(hdim, packed):
-    """The enclosed library calls as 'gru_recurrence': h_{t-1} @ W_hh^T (backward: d_gates @ W_hh) per step, 2 * 3H * H
-    flops per packed row of the tensors in `packed`."""
-    t0 = _timer.begin() if _timer is not None else None
-    yield
+def _gru_timed_end(t0, hdim, packed):
+    """The library calls since t0 = _timed() as 'gru_recurrence': h_{t-1} @ W_hh^T (backward: d_gates @ W_hh) per step,
+    2 * 3H * H flops per packed row of the tensors in `packed`."""
     if t0 is not None:
-        _timer.end('gru_recurrence', t0, flops=sum(2.0 * 3 * hdim * hdim * t.shape[0] for t in packed))
+        _timed_end(t0, 'gru_recurrence', flops=sum(2.0 * 3 * hdim * hdim * t.shape[0] for t in packed))
 
 
 def gru_fwd_multi(gis, step_off_host, hdim, w_hhs, b_hhs, out_rows=0):
@@ -1313,10 +1281,11 @@ def gru_fwd_multi(gis, step_off_host, hdim, w_hhs, b_hhs, out_rows=0):
     hs = [torch.empty(out_rows, hdim, device=dev, dtype=torch.float32) for _ in gis]
     svs = [torch.empty(g.shape[0], 5 * hdim, device=dev, dtype=torch.float32) for g in gis]
     _, ws, nbytes, _, _ = _gru_call(len(gis), [step_off_host], hdim, list(gis) + list(w_hhs) + list(b_hhs))
-    with _gru_timed(hdim, gis):
-        _check(lib().renet_gru_fwd_multi(len(gis), _ptrs(gis), ctypes.cast(step_off_host, c_void_p), L, hdim,
-                                         _ptrs(w_hhs), _ptrs(b_hhs), _ptrs(hs), out_rows, _ptrs(svs), ws.data_ptr(),
-                                         nbytes, _stream()), 'gru_fwd_multi')
+    t0 = _timed()
+    _check(lib().renet_gru_fwd_multi(len(gis), _ptrs(gis), ctypes.cast(step_off_host, c_void_p), L, hdim,
+                                     _ptrs(w_hhs), _ptrs(b_hhs), _ptrs(hs), out_rows, _ptrs(svs), ws.data_ptr(),
+                                     nbytes, _stream()), 'gru_fwd_multi')
+    _gru_timed_end(t0, hdim, gis)
     return hs, svs
 
 
@@ -1327,10 +1296,11 @@ def gru_bwd_multi(dh_lasts, step_off_host, hdim, w_hhs, saveds):
     d_gis = [torch.empty(s.shape[0], 3 * hdim, device=dev, dtype=torch.float32) for s in saveds]
     d_ghs = [torch.empty(s.shape[0], 3 * hdim, device=dev, dtype=torch.float32) for s in saveds]
     _, ws, nbytes, _, _ = _gru_call(n, [step_off_host], hdim, list(dh_lasts) + list(w_hhs) + list(saveds))
-    with _gru_timed(hdim, saveds):
-        _check(lib().renet_gru_bwd_multi(n, _ptrs(dh_lasts), ctypes.cast(step_off_host, c_void_p), L, hdim,
-                                         _ptrs(w_hhs), _ptrs(saveds), _ptrs(d_gis), _ptrs(d_ghs), ws.data_ptr(),
-                                         nbytes, _stream()), 'gru_bwd_multi')
+    t0 = _timed()
+    _check(lib().renet_gru_bwd_multi(n, _ptrs(dh_lasts), ctypes.cast(step_off_host, c_void_p), L, hdim,
+                                     _ptrs(w_hhs), _ptrs(saveds), _ptrs(d_gis), _ptrs(d_ghs), ws.data_ptr(),
+                                     nbytes, _stream()), 'gru_bwd_multi')
+    _gru_timed_end(t0, hdim, saveds)
     return d_gis, d_ghs
 
 
@@ -1345,9 +1315,10 @@ def gru_fwd_layouts(gis, step_offs, hdim, w_hhs, b_hhs, out_rows):
     svs = [torch.empty(g.shape[0], 5 * hdim, device=dev, dtype=torch.float32) for g in gis]
     _, ws, nbytes, so, ls = _gru_call(n, step_offs, hdim, list(gis) + list(w_hhs) + list(b_hhs))
     fn = getattr(lib(), 'renet_gru_fwd_layouts' + _GRU_SUFFIX.get(current_mode(), ''))
-    with _gru_timed(hdim, gis):
-        _check(fn(n, _ptrs(gis), so, ls, hdim, _ptrs(w_hhs), _ptrs(b_hhs), _ptrs(hs), (ctypes.c_int * n)(*rows),
-                  _ptrs(svs), ws.data_ptr(), nbytes, _stream()), 'gru_fwd_layouts')
+    t0 = _timed()
+    _check(fn(n, _ptrs(gis), so, ls, hdim, _ptrs(w_hhs), _ptrs(b_hhs), _ptrs(hs), (ctypes.c_int * n)(*rows),
+              _ptrs(svs), ws.data_ptr(), nbytes, _stream()), 'gru_fwd_layouts')
+    _gru_timed_end(t0, hdim, gis)
     return hs, svs
 
 
@@ -1371,25 +1342,27 @@ def gru_bwd_layouts(dh_lasts, step_offs, hdim, w_hhs, saveds, out_bf16=False):
     bmax, ws, nbytes, so, ls = _gru_call(n, step_offs, hdim, list(dh_lasts) + list(w_hhs) + list(saveds))
     head = (n, _ptrs(dh_lasts), so, ls, hdim, _ptrs(w_hhs), _ptrs(saveds))
     tail = (ws.data_ptr(), nbytes, _stream())
-    with _gru_timed(hdim, saveds):
-        if out_bf16:
-            _check(lib().renet_gru_bwd_layouts_bf16out(*head, _ptrs([m.p for m in d_gis]), _ptrs([m.p for m in d_ghs]),
-                                                       lds.pop(), *tail), 'gru_bwd_layouts_bf16out')
-            return d_gis, d_ghs
-        if _fused_bounds(d_gis[0]) and bmax > 0:
-            # the kernel that writes dGi also emits its operand bound (one max |dGi| per workgroup)
-            nparts = lib().renet_gru_bound_parts(int(bmax))
-            parts = torch.empty(n, nparts, device=dev, dtype=torch.float32)
-            rc = lib().renet_gru_bwd_layouts_bounds(*head, _ptrs(d_gis), _ptrs(d_ghs),
-                                                    _ptrs([parts[k] for k in range(n)]), *tail)
-            if rc == 0:
-                for k in range(n):
-                    _note_bound(d_gis[k], parts[k], nparts)
-                return d_gis, d_ghs
-            if rc != -2:                                     # RENET_ERR_UNSUPPORTED: another recurrence is selected
-                _check(rc, 'gru_bwd_layouts_bounds')
+    t0 = _timed()
+    rc = -2                                                  # RENET_ERR_UNSUPPORTED: not done by a special entry
+    if out_bf16:
+        rc = lib().renet_gru_bwd_layouts_bf16out(*head, _ptrs([m.p for m in d_gis]), _ptrs([m.p for m in d_ghs]),
+                                                 lds.pop(), *tail)
+        _check(rc, 'gru_bwd_layouts_bf16out')
+    elif _fused_bounds(d_gis[0]) and bmax > 0:
+        # the kernel that writes dGi also emits its operand bound (one max |dGi| per workgroup)
+        nparts = lib().renet_gru_bound_parts(int(bmax))
+        parts = torch.empty(n, nparts, device=dev, dtype=torch.float32)
+        rc = lib().renet_gru_bwd_layouts_bounds(*head, _ptrs(d_gis), _ptrs(d_ghs),
+                                                _ptrs([parts[k] for k in range(n)]), *tail)
+        if rc == 0:
+            for k in range(n):
+                _note_bound(d_gis[k], parts[k], nparts)
+        elif rc != -2:                                       # (-2: another recurrence is selected)
+            _check(rc, 'gru_bwd_layouts_bounds')
+    if rc == -2:
         fn = getattr(lib(), 'renet_gru_bwd_layouts' + _GRU_SUFFIX.get(current_mode(), ''))
         _check(fn(*head, _ptrs(d_gis), _ptrs(d_ghs), *tail), 'gru_bwd_layouts')
+    _gru_timed_end(t0, hdim, saveds)
     return d_gis, d_ghs
 
 
@@ -1397,15 +1370,11 @@ def concat3_fwd(a, ia, hmid, c, ic, drop_p, seed):
     b, d = hmid.shape
     parts = 3 if c is not None else 2
     feat = torch.empty(b, parts * d, device=hmid.device, dtype=torch.float32)
+    args = (_f32(a), _i32(ia), _f32(hmid), _f32(c), _i32(ic), b, d, float(drop_p), int(seed), _f32(feat))
     if _fused_bounds(feat):
-        nparts = lib().renet_bound_parts(b * parts * (d // 4))
-        part = torch.empty(nparts, device=hmid.device, dtype=torch.float32)
-        _check(lib().renet_concat3_fwd_bounds(_f32(a), _i32(ia), _f32(hmid), _f32(c), _i32(ic), b, d, float(drop_p),
-                                              int(seed), _f32(feat), part.data_ptr(), _stream()), 'concat3_fwd_bounds')
-        _note_bound(feat, part, nparts)
-        return feat
-    _check(lib().renet_concat3_fwd(_f32(a), _i32(ia), _f32(hmid), _f32(c), _i32(ic), b, d, float(drop_p),
-                                   int(seed), _f32(feat), _stream()), 'concat3_fwd')
+        _call_with_bounds('concat3_fwd_bounds', args, b * parts * (d // 4), (feat,))
+    else:
+        _check(lib().renet_concat3_fwd(*args, _stream()), 'concat3_fwd')
     return feat
 
 

@@ -273,3 +273,35 @@ def test_dual_head_function_equals_two_head_functions_over_emulated_kernels():
                 assert torch.allclose(g_new[n], g_ref[n], rtol=1e-5, atol=1e-7), n
     finally:
         undo()
+
+
+def test_gradient_helpers_accumulate_into_a_target_or_return_a_fresh_tensor():
+    """ops._gemm_grad / _colsum_grad / _segment_grad (kernels emulated in torch-CPU): with a target they return None and the
+    target holds old + result; without one they return a fresh tensor; the two agree bit for bit from a zero target."""
+    import cpu_abi_emulation
+    import ops
+    undo = cpu_abi_emulation.install()
+    try:
+        rng = np.random.RandomState(8)
+        f32 = lambda *shp: torch.from_numpy(rng.randn(*shp).astype(np.float32))       # noqa: E731
+        a, b, src = f32(7, 5), f32(7, 3), f32(9, 4)
+        idx = rng.randint(0, 6, 9)
+        h = G.SegPlan.host(idx)
+        plan = G.SegPlan()
+        plan.order, plan.seg_ptr, plan.target = (torch.from_numpy(np.ascontiguousarray(v)) for v in
+                                                 (h.order, h.seg_ptr, h.target))
+        plan.num_segments = h.num_segments
+        want_seg = torch.zeros(6, 4).index_add_(0, torch.from_numpy(idx).long(), src)
+        for call, shape, want in ((lambda tgt: ops._gemm_grad(a, b, tgt), (5, 3), a.t() @ b),
+                                  (lambda tgt: ops._colsum_grad(a, tgt), (5,), a.sum(dim=0)),
+                                  (lambda tgt: ops._segment_grad(src, plan, tgt, (6, 4)), (6, 4), want_seg)):
+            fresh = call(None)
+            assert tuple(fresh.shape) == shape and torch.allclose(fresh, want, rtol=1e-6, atol=1e-6)
+            zero = torch.zeros(shape)
+            assert call(zero) is None and torch.equal(zero, fresh)
+            old = f32(*shape)
+            tgt = old.clone()
+            assert call(tgt) is None
+            assert torch.allclose(tgt, old + want, rtol=1e-6, atol=1e-6) and not torch.equal(tgt, old)
+    finally:
+        undo()

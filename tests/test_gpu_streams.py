@@ -329,3 +329,74 @@ def test_bounds_from_the_producer_kernels_change_no_bit(dev, monkeypatch):
     for k in res[0][1]:
         assert torch.equal(res[0][1][k], res[1][1][k]), k
     assert res[0][2] <= res[1][2] - 5, (res[0][2], res[1][2])       # X, Xr, feat x2, g_loop no longer measured
+
+
+def test_registered_weight_life_cycle(dev, monkeypatch):
+    """What renet_hip derives from a REGISTERED weight -- the bf16 copy, the planes, the partial maxima -- is made once, again
+    after weights_changed() or an in-place torch write, served to leading column blocks that end on a 64-wide k stage, and
+    gone after unregister_weights(); every result equals, bit for bit, what an unregistered clone of the weight gives.
+    [257, 200] crosses one 256 padding boundary of the packed formats."""
+    import renet_hip as K
+    gen = torch.Generator().manual_seed(9)
+    w = (torch.randn(257, 200, generator=gen) * 0.1).to(dev)
+    xf = torch.randn(64, 200, generator=gen).to(dev)
+    x, x128, x100 = K.pack_bf16(xf), K.pack_bf16(xf[:, :128]), K.pack_bf16(xf[:, :100])       # contract over w's columns
+    a = K.F32Op(torch.randn(64, 257, generator=gen).to(dev), torch.full((1,), 8.0, device=dev), 1)      # over w's rows
+    calls = {}
+    for name in ('pack_bf16', 'pack_planes', 'maxabs_partials'):
+        def counted(*args, _name=name, _real=getattr(K, name), **kw):
+            calls[_name] = calls.get(_name, 0) + 1
+            return _real(*args, **kw)
+        monkeypatch.setattr(K, name, counted)
+
+    def launched():
+        return tuple(calls.get(k, 0) for k in ('pack_bf16', 'pack_planes', 'maxabs_partials'))
+
+    def forms(t):
+        """One request per derived form of t (the maxima twice: by an f16x3 GEMM, then by name) -> (the results, the
+        launches those requests made)."""
+        calls.clear()
+        y16 = K.gemm(x, t, tb=True, mode='bf16s')
+        planes = K.weight_planes(t)
+        y3 = K.gemm(a, t, mode='f16x3')
+        part, n = K.F32Op(t).bound()
+        return (y16, planes.p, (planes.R, planes.C), y3, float(part[:n].max())), launched()
+
+    def same(got, want):
+        return all(torch.equal(g, v) if torch.is_tensor(g) else g == v for g, v in zip(got, want))
+
+    K.register_weights([w])
+    try:
+        first, made = forms(w)
+        assert made == (1, 1, 0)                            # (the maxima: the joint launch over all registered weights)
+        assert first[4] == float(w.abs().max()) and same(first, forms(w.clone())[0])
+        again, made = forms(w)
+        assert made == (0, 0, 0) and same(again, first)
+        # the optimizer's kind of update: the values change under the tensor (no torch version bump), then the epoch moves
+        w.data.mul_(2.0)
+        K.weights_changed()
+        after, made = forms(w)
+        assert made == (1, 1, 0)
+        assert after[4] == float(w.abs().max()) and same(after, forms(w.clone())[0]) and not same(after, first)
+        assert forms(w)[1] == (0, 0, 0)
+        w.add_(0)                                           # an in-place torch write: version bump, same epoch
+        bumped, made = forms(w)
+        assert made == (1, 1, 1) and same(bumped, after)
+        assert forms(w)[1] == (0, 0, 0)
+        # leading column blocks as the contraction operand: [:, :128] ends on a 64-wide k stage and reads the cached copy of
+        # the whole matrix, [:, :100] does not and is packed afresh
+        calls.clear()
+        y128 = K.gemm(x128, w[:, :128], tb=True, mode='bf16s')
+        assert launched() == (0, 0, 0)
+        y100 = K.gemm(x100, w[:, :100], tb=True, mode='bf16s')
+        assert launched() == (1, 0, 0)
+        wc = w.clone()
+        assert torch.equal(y128, K.gemm(x128, wc[:, :128], tb=True, mode='bf16s'))
+        assert torch.equal(y100, K.gemm(x100, wc[:, :100], tb=True, mode='bf16s'))
+        K.unregister_weights([w])
+        for _ in range(2):                                  # an unregistered tensor: every request packs / measures
+            plain, made = forms(w)
+            assert made == (1, 1, 2) and same(plain, after)
+        assert [k for k, v in vars(K).items() if isinstance(v, dict) and w.data_ptr() in v] == []
+    finally:
+        K.unregister_weights([w])

@@ -544,6 +544,95 @@ def test_split_k_cost_model():
         assert 1 <= s <= max(1, ((k + 31) // 32))
 
 
+# (m, n, k) -> auto_split_k, auto_split_k_planes: the factors of the two cost models as they stood BEFORE they became one
+# parametrised model (recorded from that revision's functions).  The GEMMs of a training step at n_hidden 100 / 200 / 400
+# (batch 1024 per direction, 23033 entities, 16000 packed rows), the docstring's three swept shapes (40 tiles -> 12,
+# 35 -> 14, 4 -> 128), single-tile outputs, k-tile counts around 8, tile counts around the no-split thresholds
+# (255 / 256 tiles of 128 x 128, 127 / 128 tiles of 256 x 128).
+SPLIT_K_TABLE = [
+    ((2048, 23033, 300), 1, 1),
+    ((2048, 300, 23033), 10, 10),
+    ((23033, 300, 2048), 1, 1),
+    ((2048, 512, 200), 1, 1),
+    ((2048, 200, 512), 4, 4),
+    ((512, 200, 2048), 15, 15),
+    ((16000, 300, 400), 1, 1),
+    ((16000, 300, 300), 1, 1),
+    ((16000, 200, 300), 1, 1),
+    ((300, 400, 16000), 39, 32),
+    ((300, 300, 16000), 45, 42),
+    ((300, 100, 16000), 79, 64),
+    ((23033, 100, 100), 1, 1),
+    ((100, 100, 23033), 128, 64),
+    ((16000, 100, 100), 1, 1),
+    ((100, 100, 16000), 125, 64),
+    ((92000, 100, 100), 1, 1),
+    ((2048, 23033, 600), 1, 1),
+    ((2048, 600, 23033), 6, 6),
+    ((23033, 600, 2048), 1, 1),
+    ((2048, 512, 400), 2, 2),
+    ((2048, 400, 512), 3, 3),
+    ((512, 400, 2048), 11, 11),
+    ((16000, 600, 800), 1, 1),
+    ((16000, 600, 600), 1, 1),
+    ((16000, 400, 600), 1, 1),
+    ((600, 800, 16000), 14, 12),
+    ((600, 600, 16000), 20, 17),
+    ((600, 200, 16000), 39, 39),
+    ((23033, 200, 200), 1, 1),
+    ((200, 200, 23033), 82, 64),
+    ((16000, 200, 200), 1, 1),
+    ((200, 200, 16000), 68, 64),
+    ((92000, 200, 200), 1, 1),
+    ((2048, 23033, 1200), 1, 1),
+    ((2048, 1200, 23033), 3, 3),
+    ((23033, 1200, 2048), 1, 1),
+    ((2048, 512, 800), 3, 3),
+    ((2048, 800, 512), 1, 1),
+    ((512, 800, 2048), 8, 8),
+    ((16000, 1200, 1600), 1, 1),
+    ((16000, 1200, 1200), 1, 1),
+    ((16000, 800, 1200), 1, 1),
+    ((1200, 1600, 16000), 3, 3),
+    ((1200, 1200, 16000), 5, 5),
+    ((1200, 400, 16000), 12, 12),
+    ((23033, 400, 400), 1, 1),
+    ((400, 400, 23033), 32, 32),
+    ((16000, 400, 400), 1, 1),
+    ((400, 400, 16000), 32, 32),
+    ((92000, 400, 400), 1, 1),
+    ((1024, 600, 23033), 12, 12),
+    ((200, 200, 92000), 128, 64),
+    ((100, 100, 46000), 128, 64),
+    ((128, 128, 4096), 32, 32),
+    ((1, 1, 1048576), 128, 64),
+    ((256, 128, 8192), 54, 54),
+    ((128, 128, 224), 1, 1),
+    ((128, 128, 225), 2, 2),
+    ((600, 600, 255), 2, 2),
+    ((600, 600, 256), 2, 2),
+    ((600, 600, 31), 1, 1),
+    ((256, 128, 96), 1, 1),
+    ((1920, 2176, 4096), 2, 1),
+    ((2048, 2048, 4096), 1, 1),
+    ((256, 16256, 4096), 2, 2),
+    ((256, 16384, 4096), 1, 1),
+    ((16256, 128, 4096), 4, 4),
+    ((16384, 128, 4096), 4, 4),
+    ((32513, 128, 4096), 2, 1),
+    ((257, 200, 16000), 60, 60),
+    ((129, 129, 100000), 128, 64),
+]
+
+
+@pytest.mark.parametrize('shape,factor,factor_planes', SPLIT_K_TABLE,
+                         ids=lambda v: 'x'.join(map(str, v)) if isinstance(v, tuple) else None)
+def test_split_k_factors_are_the_recorded_ones(shape, factor, factor_planes):
+    import renet_hip as K
+    assert K.auto_split_k(*shape) == factor
+    assert K.auto_split_k_planes(*shape) == factor_planes
+
+
 def test_graph_store_cache_survives_address_reuse():
     """store_for() recognises a graph_dict by object identities; graphs that were freed and re-created at the same
     addresses (same-shaped dicts built in a loop) must not resurrect a stale store."""
