@@ -526,6 +526,24 @@ int renet_topk_positive(const float* x, size_t ldx, int n, int M, int k, float* 
                         void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Inference: the evaluation metric (model.py:365-381 raw, 391-418 filtered; the loss of 358-361).  One read of every row of
+ * scores [n, C] (row stride ld; never written) gives, for the gold column label[i] of row i,
+ *   greater[i]  = number of columns whose value is  > the gold value,
+ *   equal[i]    = number of columns whose value is == the gold value, the gold column included
+ *                 (the reference's rank with averaged ties is greater + (equal - 1) / 2 + 1),
+ *   row_loss[i] = logsumexp(scores[i, :]) - scores[i, label[i]]   (renet_softmax_ce without a gradient; NULL: not computed).
+ * filtered = 0: the values are the scores themselves; filt_ptr must be NULL.
+ * filtered = 1: the values are sigmoid(score) as torch.sigmoid rounds it in fp32 (1 / (1 + exp(-x)): distinct logits that
+ *   collapse onto one sigmoid value, 1.0 or 0 included, tie exactly as in the reference), and every column listed in
+ *   filt_col[filt_ptr[i] .. filt_ptr[i + 1]) other than label[i] counts with the value 0 instead of its own (filt_ptr NULL:
+ *   no lists).  A column may be listed at most once per row; listed columns outside [0, C) are ignored.
+ * label[i] is device data, so it cannot be checked here: a label outside [0, C) is clamped into the row by the kernel.
+ * RENET_ERR_BADARG for n < 0, C < 1, ld < C, a missing array, or lists with filtered = 0; n == 0 is a no-op. */
+int renet_rank_rows(const float* scores, int ld, int n, int C, const int32_t* label, const int32_t* filt_ptr,
+                    const int32_t* filt_col, int filtered, int32_t* greater, int32_t* equal, float* row_loss,
+                    void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * DEVICE batch-graph builder for the merged training batch (both directions of train.py:136-137 as one batch of 2B
  * sequences: graph.build_batch_both; replaces utils.py:209-244 + 115-131 + dgl.batch and this library's own HOST
  * builder for that case).  The dataset is resident in HBM (RenetStoreDev: quadruples, the per-role history index of

@@ -16,6 +16,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.nn.utils.rnn import PackedSequence
 
+import filter_index as FI
 import graph as G
 import ops
 import renet_hip as K
@@ -130,6 +131,11 @@ class RENet(nn.Module):
         # per timestamp (_lookahead_filter; opt-in, see its docstring)
         self.lookahead_eval = os.environ.get('RENET_LOOKAHEAD_EVAL', '0') == '1'
         self._la = self._la_at = None
+        # evaluate_filter_batch(): ranks and loss from the resident filter index + one rank kernel per direction
+        # (_device_ranks; opt-in: RENET_DEVICE_RANK=1; tools/run_reference_driver.py turns it on) instead of a host sort of
+        # all_triplets per call and torch passes over the score matrix
+        self.device_rank = os.environ.get('RENET_DEVICE_RANK', '0') == '1'
+        self._filter_index = None
         self.last_prune = None
         self.shadow_pick = None
         self._shadow = {}
@@ -1027,14 +1033,15 @@ def _host_quads(triplets):
     return tr.astype(np.int64).reshape(-1, 4)
 
 
-def _predict_batch(self, triplets, s_hist, o_hist, global_model):
+def _predict_batch(self, triplets, s_hist, o_hist, global_model, want_loss=True):
     """predict() for n test quadruples that share ONE timestamp, in one batch: row i of the result equals
     predict(triplets[i], (s_hist[0][i], s_hist[1][i]), (o_hist[0][i], o_hist[1][i]), global_model).
     The reference (and predict) build the batch graph of every quadruple separately, so the member graphs are kept
     separate per entity here (build_batch group=entity: same entity => same rolling history => same graphs)
     instead of being merged per timestamp as in training.  s_hist / o_hist: (list of the n given histories,
     list of their timestamp lists), i.e. slices of test.py's s_history_test / s_history_test_t.
-    Returns (loss[n], sub_pred[n, in_dim], ob_pred[n, in_dim])."""
+    Returns (loss[n], sub_pred[n, in_dim], ob_pred[n, in_dim]); want_loss=False: loss is None (the caller takes it from the
+    rank kernel, which reads the scores anyway)."""
     tr = _host_quads(triplets)
     n = len(tr)
     if n == 0 or np.any(tr[:, 3] != tr[0, 3]):
@@ -1066,7 +1073,9 @@ def _predict_batch(self, triplets, s_hist, o_hist, global_model):
         si, ri, oi = (torch.from_numpy(x).to(dev) for x in (s, r, o))
         ob_pred = _linear_eval(self.linear, torch.cat((self.ent_embeds[si], s_h, self.rel_embeds[ri]), dim=1))
         sub_pred = _linear_eval(self.linear, torch.cat((self.ent_embeds[oi], o_h, self.rel_embeds[R + ri]), dim=1))
-        loss = K.softmax_ce(ob_pred, oi.int(), 1.0, False) + K.softmax_ce(sub_pred, si.int(), 1.0, False)
+        loss = None
+        if want_loss:
+            loss = K.softmax_ce(ob_pred, oi.int(), 1.0, False) + K.softmax_ce(sub_pred, si.int(), 1.0, False)
     return loss, sub_pred, ob_pred
 
 
@@ -1107,6 +1116,8 @@ def _evaluate_filter_batch(self, triplets, s_hist, o_hist, global_model, all_tri
     (ranks[n, 2] = (rank_sub, rank_ob) per row, loss[n]), row i equal to
     evaluate_filter(triplets[i], (s_hist[0][i], s_hist[1][i]), (o_hist[0][i], o_hist[1][i]), ...)."""
     tr = _host_quads(triplets)
+    if self.device_rank:
+        return _device_ranks(self, tr, s_hist, o_hist, global_model, FI.filter_index_for(self, all_triplets))
     loss, sub_pred, ob_pred = self.predict_batch(tr, s_hist, o_hist, global_model)
     dev = ob_pred.device
     s, r, o = tr[:, 0], tr[:, 1], tr[:, 2]
@@ -1118,21 +1129,63 @@ def _evaluate_filter_batch(self, triplets, s_hist, o_hist, global_model, all_tri
     return np.stack((rank_sub, rank_ob), axis=1), loss
 
 
-def _evaluate_filter_stream(self, total_data, s_history, o_history, global_model, all_triplets, max_batch=4096):
-    """test.py:104-139 for a whole time-ordered test stream: groups consecutive quadruples by timestamp and
-    evaluates each group with evaluate_filter_batch (the per-timestamp state update of predict() runs once per
-    group, exactly as in the sequential loop).  s_history / o_history: (histories, timestamps) per quadruple,
-    as loaded by test.py.  Returns (ranks[len, 2], loss[len])."""
+def _device_ranks(self, tr, s_hist, o_hist, global_model, index):
+    """(ranks[n, 2] = (rank_sub, rank_ob), loss[n]) of the quadruples tr of ONE timestamp from one renet_rank_rows launch
+    per direction (csrc/rank.hip: counts and the cross-entropy from one read of the scores, which are not copied).
+    index: the FilterIndex of the known facts (filtered ranks, model.py:391-418), or None (raw ranks, model.py:365-381)."""
+    # with reference_shadowing the loss of a timestamp's first quadruple belongs to the shadowing entities while the ranks
+    # are those of its own (model.py:229-297): predict_batch computes that loss, the kernel only counts
+    own_loss = self.reference_shadowing
+    loss, sub_pred, ob_pred = self.predict_batch(tr, s_hist, o_hist, global_model, want_loss=own_loss)
+    dev = ob_pred.device
+    s, r, o = tr[:, 0], tr[:, 1], tr[:, 2]
+    label = torch.from_numpy(np.stack((s, o)).astype(np.int32)).to(dev)
+    counts = []
+    for side, pred, lab, keys in (('s', sub_pred, label[0], (o, r)), ('o', ob_pred, label[1], (s, r))):
+        ptr, col = index.lookup(side, np.stack(keys, axis=1), dev) if index is not None else (None, None)
+        cnt, ls = K.rank_rows(pred, lab, ptr, col, filtered=index is not None, want_loss=not own_loss)
+        counts.append(cnt)
+        if not own_loss:
+            loss = ls if loss is None else loss + ls
+    g, e = torch.stack(counts, dim=2).cpu().numpy().astype(np.float64)             # [2, n, 2] -> greater, equal [n, 2]
+    return g + (e - 1.0) / 2 + 1, loss
+
+
+def _evaluate_batch(self, triplets, s_hist, o_hist, global_model):
+    """evaluate() (model.py:365-381: the raw, unfiltered ranks) for the n quadruples of ONE timestamp: returns
+    (ranks[n, 2] = (rank_sub, rank_ob) per row, loss[n]), row i equal to
+    evaluate(triplets[i], (s_hist[0][i], s_hist[1][i]), (o_hist[0][i], o_hist[1][i]), global_model)."""
+    return _device_ranks(self, _host_quads(triplets), s_hist, o_hist, global_model, None)
+
+
+def _stream_groups(total_data, s_history, o_history, max_batch, evaluate):
+    """A time-ordered stream in groups of consecutive quadruples of one timestamp (at most max_batch each), every group
+    through evaluate(quadruples, s_hist, o_hist) -> (ranks[len, 2], loss[len])."""
     tr = _host_quads(total_data)
     ranks, losses = np.zeros((len(tr), 2)), np.zeros(len(tr), dtype=np.float32)
     cut = np.concatenate(([0], np.nonzero(np.diff(tr[:, 3]))[0] + 1, [len(tr)]))
     for a, b in zip(cut[:-1], cut[1:]):
         for c in range(a, b, max_batch):
             d = min(b, c + max_batch)
-            rk, ls = self.evaluate_filter_batch(tr[c:d], (s_history[0][c:d], s_history[1][c:d]),
-                                                (o_history[0][c:d], o_history[1][c:d]), global_model, all_triplets)
+            rk, ls = evaluate(tr[c:d], (s_history[0][c:d], s_history[1][c:d]), (o_history[0][c:d], o_history[1][c:d]))
             ranks[c:d], losses[c:d] = rk, ls.cpu().numpy()
     return ranks, losses
+
+
+def _evaluate_filter_stream(self, total_data, s_history, o_history, global_model, all_triplets, max_batch=4096):
+    """test.py:104-139 for a whole time-ordered test stream: groups consecutive quadruples by timestamp and
+    evaluates each group with evaluate_filter_batch (the per-timestamp state update of predict() runs once per
+    group, exactly as in the sequential loop).  s_history / o_history: (histories, timestamps) per quadruple,
+    as loaded by test.py.  Returns (ranks[len, 2], loss[len])."""
+    return _stream_groups(total_data, s_history, o_history, max_batch,
+                          lambda q, sh, oh: self.evaluate_filter_batch(q, sh, oh, global_model, all_triplets))
+
+
+def _evaluate_stream(self, total_data, s_history, o_history, global_model, max_batch=4096):
+    """test.py:104-139 with --raw for a whole time-ordered test stream: evaluate_filter_stream with the raw ranks of
+    evaluate() (evaluate_batch per group).  Returns (ranks[len, 2], loss[len])."""
+    return _stream_groups(total_data, s_history, o_history, max_batch,
+                          lambda q, sh, oh: self.evaluate_batch(q, sh, oh, global_model))
 
 
 RENet.init_history = _init_history
@@ -1154,3 +1207,5 @@ RENet._lookahead_filter = _lookahead_filter
 RENet.predict_batch = _moded(_predict_batch)
 RENet.evaluate_filter_batch = _moded(_evaluate_filter_batch)
 RENet.evaluate_filter_stream = _moded(_evaluate_filter_stream)
+RENet.evaluate_batch = _moded(_evaluate_batch)
+RENet.evaluate_stream = _moded(_evaluate_stream)

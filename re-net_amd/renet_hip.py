@@ -143,6 +143,8 @@ _SIGNATURES = {
     'renet_softmax_ce': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p,
                                  c_void_p]),
     'renet_joint_softmax': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    'renet_rank_rows': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                c_void_p, c_void_p]),
     'renet_topk_workspace': (c_size_t, [c_int]),
     'renet_topk_positive': (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
                                     c_void_p]),
@@ -1404,6 +1406,27 @@ def softmax_ce(logits, target, grad_scale, want_grad, row_loss=None):
                                   _f32(row_loss), logits.data_ptr() if want_grad else None, _stream()),
            'softmax_ce')
     return row_loss
+
+
+def rank_rows(scores, label, filt_ptr=None, filt_col=None, filtered=True, want_loss=True):
+    """renet_rank_rows on scores [n, C] (fp32, unit inner stride; not written) for the gold columns label [n] (int32):
+    -> (counts, row_loss): counts is int32 [2, n] = (greater, equal) -- the rank with averaged ties is
+    greater + (equal - 1) / 2 + 1 -- and row_loss [n] = logsumexp(row) - row[label] (None unless want_loss).
+    filtered: compare sigmoid(score) and give the columns of the CSR lists filt_ptr [n + 1] / filt_col (int32; every column at
+    most once per row) the value 0; filtered=False compares the scores themselves and takes no lists."""
+    if not (scores.is_cuda and scores.dtype == torch.float32 and scores.dim() == 2):
+        raise RenetHipError('rank_rows needs a 2-D float32 device tensor')
+    n, c = scores.shape
+    if label.numel() != n or (filt_ptr is not None and (filt_col is None or filt_ptr.numel() != n + 1)):
+        raise RenetHipError('rank_rows: shape mismatch')
+    counts = torch.empty(2, n, device=scores.device, dtype=torch.int32)
+    row_loss = torch.empty(n, device=scores.device, dtype=torch.float32) if want_loss else None
+    t0 = _timed()
+    _check(lib().renet_rank_rows(scores.data_ptr(), max(_ld(scores), c) if n == 1 else _ld(scores), n, c, _i32(label),
+                                 _i32(filt_ptr), _i32(filt_col), int(bool(filtered)), counts[0].data_ptr(),
+                                 counts[1].data_ptr(), _f32(row_loss), _stream()), 'rank_rows')
+    _timed_end(t0, 'rank_rows', nbytes=float(n * c * 4))
+    return counts, row_loss
 
 
 def joint_softmax(logits, num_rels, logits_r, prob_e):

@@ -106,6 +106,16 @@ def soft_cross_entropy(pred, soft_targets):
     return torch.mean(torch.sum(-soft_targets.to(logp.device).double() * logp, 1))
 
 
+def rank_metrics(ranks):
+    """test.py:141-160 on the [len, 2] (rank_sub, rank_ob) array of evaluate_filter_stream / evaluate_stream (any shape:
+    every rank counts once, as in the driver's concatenation) -> {'mrr', 'mr', 'hits@1', 'hits@3', 'hits@10'}."""
+    total_ranks = np.asarray(ranks, dtype=np.float64).reshape(-1)
+    out = {'mrr': float(np.mean(1.0 / total_ranks)), 'mr': float(np.mean(total_ranks))}
+    for hit in (1, 3, 10):
+        out['hits@%d' % hit] = float(np.mean(total_ranks <= hit))
+    return out
+
+
 def cuda(tensor):
     return tensor if tensor.is_cuda else tensor.cuda()
 

@@ -1,0 +1,127 @@
+#!/usr/bin/env python
+"""The last stage of the filtered evaluation -- scores to ranks and loss -- on a score matrix of evaluation size: the torch
+tail (model._known_pairs x 2, uploads, model._rank_rows x 2, softmax_ce x 2) against the device tail
+(filter_index.FilterIndex lookups + renet_rank_rows x 2), and evaluate_filter_stream with RENet.device_rank off and on.
+GPU only.
+
+    python tools/rank_bench.py tail [n] [C] [n_facts] [reps]        medians of `reps` alternating repetitions, JSON line
+    python tools/rank_bench.py stream [shape] [n_timestamps] [reps]
+"""
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, 're-net_amd'))
+sys.path.insert(0, os.path.join(ROOT, 'tools'))
+import filter_index as FI
+import model as M
+import renet_hip as K
+
+PEAK_HBM = 8.0e12                 # bytes/s, MI355X
+
+
+def _wall(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0, out
+
+
+def tail(n=4096, C=23033, n_facts=400000, reps=7):
+    dev = torch.device('cuda:0')
+    rng = np.random.RandomState(3)
+    num_rels = 256
+    facts = np.stack((rng.randint(0, C, n_facts), rng.randint(0, num_rels, n_facts), rng.randint(0, C, n_facts),
+                      rng.randint(0, 300, n_facts) * 24), axis=1).astype(np.int64)
+    facts = np.concatenate((facts, facts[: n_facts // 2] + np.array([0, 0, 0, 24])))     # repeated at another time
+    quads = facts[rng.choice(len(facts), n, replace=False)]
+    s, r, o = quads[:, 0], quads[:, 1], quads[:, 2]
+    g = torch.Generator().manual_seed(1)
+    ob_pred = (torch.randn(n, C, generator=g) * 4).to(dev)
+    sub_pred = (torch.randn(n, C, generator=g) * 4).to(dev)
+    total = torch.from_numpy(facts).to(dev)
+    t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+
+    def old_tail():
+        ro, co = M._known_pairs(total, (0, 1), 2, np.stack((s, r), axis=1))
+        rs, cs = M._known_pairs(total, (2, 1), 0, np.stack((o, r), axis=1))
+        rank_ob = M._rank_rows(ob_pred, t(o), t(ro), t(co))
+        rank_sub = M._rank_rows(sub_pred, t(s), t(rs), t(cs))
+        loss = K.softmax_ce(ob_pred, t(o).int(), 1.0, False) + K.softmax_ce(sub_pred, t(s).int(), 1.0, False)
+        return np.stack((rank_sub, rank_ob), axis=1), loss
+
+    t_build, index = _wall(lambda: FI.FilterIndex(total))
+
+    def new_tail():
+        label = torch.from_numpy(np.stack((s, o)).astype(np.int32)).to(dev)
+        counts, loss = [], None
+        for side, pred, lab, keys in (('s', sub_pred, label[0], (o, r)), ('o', ob_pred, label[1], (s, r))):
+            ptr, col = index.lookup(side, np.stack(keys, axis=1), dev)
+            cnt, ls = K.rank_rows(pred, lab, ptr, col, filtered=True)
+            counts.append(cnt)
+            loss = ls if loss is None else loss + ls
+        gr, eq = torch.stack(counts, dim=2).cpu().numpy().astype(np.float64)
+        return gr + (eq - 1.0) / 2 + 1, loss
+
+    (ra, la), (rb, lb) = old_tail(), new_tail()                 # warm-up of every shape, and the two tails must agree
+    same = bool(np.array_equal(ra, rb))
+    loss_diff = float((la - lb).abs().max())
+    told, tnew = [], []
+    for _ in range(reps):                                       # alternating: both sides see the same machine state
+        told.append(_wall(old_tail)[0])
+        tnew.append(_wall(new_tail)[0])
+    # the kernel alone (device events), filtered with lists and loss: one read of the matrix
+    ptr, col = index.lookup('o', np.stack((s, r), axis=1), dev)
+    lab = t(o).int()
+    ev = []
+    for _ in range(3 + reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        K.rank_rows(ob_pred, lab, ptr, col, filtered=True)
+        e1.record()
+        torch.cuda.synchronize()
+        ev.append(e0.elapsed_time(e1) * 1e-3)
+    t_k = float(np.median(ev[3:]))
+    nbytes = float(n) * C * 4
+    print(json.dumps({'n': n, 'C': C, 'facts': int(len(facts)), 'filter_nnz_per_side': int(ptr[-1]), 'reps': reps,
+                      'ranks_identical': same, 'loss_max_abs_diff': loss_diff,
+                      'old_tail_ms': [round(x * 1e3, 3) for x in sorted(told)], 'old_tail_median_ms': float(np.median(told)) * 1e3,
+                      'new_tail_ms': [round(x * 1e3, 3) for x in sorted(tnew)], 'new_tail_median_ms': float(np.median(tnew)) * 1e3,
+                      'index_build_once_ms': t_build * 1e3, 'kernel_median_ms': t_k * 1e3,
+                      'kernel_bytes_per_s': nbytes / t_k, 'kernel_share_of_hbm_peak': nbytes / t_k / PEAK_HBM}))
+
+
+def stream(shape='ICEWS18', n_t=3, reps=2):
+    import infer_bench
+    dev = torch.device('cuda:0')
+    times = {False: [], True: []}
+    ranks = {}
+    for rep in range(reps + 1):                                 # repetition 0 warms up both sides
+        for on in (False, True):
+            net, gnet, te, tes, teo, total = infer_bench.setup(shape, n_t, 200, dev)
+            net.device_rank = on
+            with torch.no_grad():
+                dt, (rk, _) = _wall(lambda: net.evaluate_filter_stream(te, tes, teo, gnet, total))
+            if rep:
+                times[on].append(dt)
+            ranks[on] = rk
+    n = len(ranks[True])
+    print(json.dumps({'shape': shape, 'timestamps': n_t, 'quadruples': n, 'reps': reps,
+                      'ranks_identical': bool(np.array_equal(ranks[False], ranks[True])),
+                      'off_s': [round(x, 4) for x in times[False]], 'on_s': [round(x, 4) for x in times[True]],
+                      'off_quadruples_per_s': n / float(np.median(times[False])),
+                      'on_quadruples_per_s': n / float(np.median(times[True]))}))
+
+
+if __name__ == '__main__':
+    a = sys.argv[1:]
+    if a and a[0] == 'stream':
+        stream(a[1] if len(a) > 1 else 'ICEWS18', int(a[2]) if len(a) > 2 else 3, int(a[3]) if len(a) > 3 else 2)
+    else:
+        tail(*[int(x) for x in a[1:5]])

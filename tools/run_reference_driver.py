@@ -29,6 +29,9 @@ def main():
     # test.py:104-139 / train.py:160-172 evaluate one quadruple per call and pass the whole stream as `all_triplets`:
     # RENet.lookahead_eval answers them from one batched evaluation per timestamp (RENET_LOOKAHEAD_EVAL=0: per call)
     os.environ.setdefault('RENET_LOOKAHEAD_EVAL', '1')
+    # ... and the ranks and loss of that evaluation come from the resident filter index and the rank kernel
+    # (RENet.device_rank; RENET_DEVICE_RANK=0: host sort of total_data per call + torch passes over the scores)
+    os.environ.setdefault('RENET_DEVICE_RANK', '1')
     sys.path.insert(0, os.path.join(ROOT, 're-net_amd'))
     sys.argv = [script] + sys.argv[2:]
     runpy.run_path(script, run_name='__main__')
