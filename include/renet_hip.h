@@ -623,6 +623,39 @@ int renet_build_full_graphs(const RenetFullStoreDev* store, const int32_t* tidx_
                             void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * DEVICE builder for GROUPED inference batches (graph.build_batch(..., group=...), RGCNAggregator.forward_grouped): ONE
+ * direction of B sequences, and sequences of different group ids get SEPARATE member graphs per timestamp -- a slot per
+ * (group, timestamp) pair, numbered group-major, then by time.  A batch has thousands of slots, so the node sets are not
+ * marked in a [slot][entity] table as in renet_build_batch_both: the 64-bit keys (slot << 32) | entity of every step's
+ * subject and history neighbours are radix sorted and numbered (subject keys first, in key order), and the induced edges
+ * come from a per-node walk through the store's subject index (graph.GraphStore.subject_index), membership by binary
+ * search in the sorted keys.  Per call (device int32, one upload): the batch's s, r, group and its FlatHistory laid out as
+ * first / count per sequence, step timestamps, neighbour ranges, neighbours.  idx_dev is the order of the sequences
+ * (device int32 [B]); NULL = the order of the arrays, so a caller uploads nothing besides them.  Fills the
+ * RenetBatchOut of renet_build_batch_both except rel_label / ent_label (may be NULL), with the row prefix [0, nA) of the
+ * subject rows -- bit for bit the arrays of the host builder (tests/test_gpu_grouped_builder.py).  Edge types are stored as
+ * type_s: the direction is the kernels' type_shift.  Same protocol: no host synchronisation, stages launch over capacities
+ * and guard on counts, RENET_BB_ERR_* in counts[RENET_BB_ERR].  B <= 4096, seq_len <= 32, 2 * num_rels <= 1024. */
+typedef struct {
+    const int32_t *s, *r, *group;              /* [B] subject, relation row, group id of every sequence               */
+    const int32_t *h_first, *h_count;          /* [B] first step and number of steps of every sequence                */
+    const int32_t* step_t;                     /* [n_steps] timestamp of every history step                           */
+    const int32_t* nbr_ptr;                    /* [n_steps + 1] neighbour range of every step                         */
+    const int32_t* nbr_o;                      /* [n_nbr] neighbour entities                                          */
+    const int32_t* times;                      /* [T] sorted timestamps of graph_dict                                 */
+    const int32_t* trip_ptr;                   /* [T + 1] fact range of every timestamp                               */
+    const int32_t *trip_s, *trip_r, *trip_o;   /* [n_facts]                                                           */
+    const int32_t* glob_times;                 /* [n_glob] sorted timestamps of the global-embedding table            */
+    const int32_t *by_subj, *subj_sorted;      /* [n_facts] facts sorted stably by (timestamp, subject); their subjects */
+    int n_steps, n_nbr, T, n_glob, n_facts, num_ent, num_rels;
+} RenetGroupedStoreDev;
+
+size_t renet_build_batch_grouped_workspace(const RenetGroupedStoreDev* store, int B, int cap_nodes, int cap_edges);
+int renet_build_batch_grouped(const RenetGroupedStoreDev* store, const int32_t* idx_dev, int B, int seq_len,
+                              int heavy_thresh, int group_budget, int chunk, const RenetBatchOut* out, void* workspace,
+                              size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * THE MERGED TRAINING STEP AS ONE LAUNCH LIST (round 6; csrc/step.cpp): one iteration of train.py:136-139 --
  *     loss = model(batch, ..., subject=True) + model(batch, ..., subject=False);  loss.backward()
  * on the merged batch of both directions (renet_build_batch_both / graph.build_batch_both) -- issued from C: the forward

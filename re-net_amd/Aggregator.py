@@ -100,6 +100,9 @@ class RGCNAggregator(nn.Module):
                                dropout=dropout)
         self.glob_table = GlobalEmbTable()
         self.last_batch = None
+        # forward_grouped builds its batch on the device (gpu_builder.GroupedDeviceBatch: the same arrays, bit for bit)
+        # instead of graph.build_batch + the upload of graph.DeviceGraph; opt-in: RENET_GROUPED_DEVICE_BUILDER=1
+        self.grouped_device_builder = os.environ.get('RENET_GROUPED_DEVICE_BUILDER', '0') == '1'
 
     # ------------------------------------------------------------------------------------------
     def build(self, s_hist, s, r, ent_embeds, graph_dict, global_emb, sort, group=None):
@@ -118,6 +121,24 @@ class RGCNAggregator(nn.Module):
         g.glob = table.mat
         return g
 
+    def build_grouped_device(self, fh, s, r, ent_embeds, graph_dict, global_emb, group):
+        """build(..., sort=True, group=group) on the DEVICE builder, or None where that front does not apply (the caller then
+        takes the host builder): tensors that are not on a HIP device, a batch beyond its limits, no history at all."""
+        import gpu_builder
+        if not ent_embeds.is_cuda or not 0 < len(fh) <= gpu_builder.MAX_GROUPED or fh.seq_ptr[-1] == 0 or \
+                self.seq_len > gpu_builder.MAXL or 2 * self.num_rels > 1024:
+            return None
+        table = self.glob_table.get(global_emb, self.h_dim, ent_embeds.device)
+        base = gpu_builder.graph_store_for(graph_dict, global_emb, self.num_nodes, self.num_rels, ent_embeds.device)
+        for _ in range(16):                                 # (a capacity grew: rebuild; first batches only)
+            if len(fh.step_t) + len(fh.nbr_o) >= 2 ** 30 or base.cap_nodes * 2 * self.num_rels >= 2 ** 31:
+                return None                                 # (beyond the front's 32-bit sort keys: RENET_ERR_UNSUPPORTED)
+            g = gpu_builder.GroupedDeviceBatch(gpu_builder.GroupedBatchStore(base, s, r, group, fh), self.seq_len)
+            if g.finalize():
+                g.glob = table.mat
+                return g
+        raise RuntimeError('device batch builder did not converge on its capacities')
+
     def encode(self, g, ent_embeds, rel_embeds, reverse, _lazy_bf16=False):
         """Device side: h0 gather, two RGCN layers, packed sequence assembly (Aggregator.py:136-165).
         _lazy_bf16 (PRIVATE: internal callers that hand X / Xr straight to ops.dual_gru / MultiGRUFn): in bf16-storage mode the
@@ -133,7 +154,13 @@ class RGCNAggregator(nn.Module):
         return ops.SeqAssembleFn.apply(h2, ent_embeds, rel_embeds, g.glob, g, p, sx, sxr, bool(_lazy_bf16))
 
     def _run(self, s_hist, s, r, ent_embeds, rel_embeds, graph_dict, global_emb, reverse, sort, group=None):
-        g = self.build(s_hist, s, r, ent_embeds, graph_dict, global_emb, sort, group)
+        g = None
+        if group is not None and sort and self.grouped_device_builder:
+            s_hist = s_hist if isinstance(s_hist, G.FlatHistory) else G.FlatHistory.from_lists(s_hist[0], s_hist[1])
+            g = self.build_grouped_device(s_hist, _host_ints(s), _host_ints(r), ent_embeds, graph_dict, global_emb,
+                                          _host_ints(group))
+        if g is None:
+            g = self.build(s_hist, s, r, ent_embeds, graph_dict, global_emb, sort, group)
         self.last_batch = g
         if g is None:
             return None, None

@@ -12,6 +12,9 @@
 // Second entry, renet_build_full_graphs: the global model's batches of FULL graphs (graph.build_full_graphs).  Its front
 // (fg_* kernels) only concatenates resident per-timestamp graphs; everything behind the edge list is build_tail, shared
 // with renet_build_batch_both.
+// Third entry, renet_build_batch_grouped: the grouped batches of batched inference (graph.build_batch(group=...)).  Its
+// front (gb_* kernels) numbers slots and nodes by sorting 64-bit keys and filters edges through the subject index; the
+// length sort, the steps, the edge expansion and build_tail are the ones of renet_build_batch_both.
 #include <cstring>
 #include "common.h"
 #include <rocprim/rocprim.hpp>
@@ -61,7 +64,9 @@ struct Store {
 // ---- stage A: length sort + per-sequence arrays (ONE workgroup) --------------------------------------------------
 // sequences q in [0, 2B): q < B = subject side of quadruple idx[q] (entity s, history role 0, relation row r),
 // q >= B = object side (entity o, role 1, relation row R + r).  Stable sort by descending history length.
-__global__ __launch_bounds__(1024) void bb_seq_kernel(Store st, const int32_t* __restrict__ idx, int B, int seq_len,
+// Q = 2B for the merged batch; Q = B: the subject side only (the grouped front: one direction per batch).  idx = nullptr:
+// the identity (sequence q is quadruple q of the store).
+__global__ __launch_bounds__(1024) void bb_seq_kernel(Store st, const int32_t* __restrict__ idx, int B, int Q, int seq_len,
                                                       int32_t* __restrict__ perm, int32_t* __restrict__ seq_first,
                                                       int32_t* __restrict__ seq_len_s, int32_t* __restrict__ seq_start,
                                                       int32_t* __restrict__ s_sorted, int32_t* __restrict__ r_sorted,
@@ -71,11 +76,10 @@ __global__ __launch_bounds__(1024) void bb_seq_kernel(Store st, const int32_t* _
     __shared__ int pos_of[BB_MAXQ];
     __shared__ int wsum[16];
     __shared__ int hist[BB_MAXL + 2];
-    const int Q = 2 * B;
     for (int q = threadIdx.x; q < BB_MAXQ; q += 1024) {
         int len = 0;
         if (q < Q) {
-            const int role = q >= B, qi = idx[q - role * B];
+            const int role = q >= B, qi = idx ? idx[q - role * B] : q - role * B;
             len = min(st.h_count[role][qi], seq_len);          // (the index already holds <= history_len snapshots)
         }
         lens[q] = q < Q ? len : -1;
@@ -100,7 +104,7 @@ __global__ __launch_bounds__(1024) void bb_seq_kernel(Store st, const int32_t* _
     // per sorted position
     for (int q = threadIdx.x; q < Q; q += 1024) {
         const int p = pos_of[q];
-        const int role = q >= B, qi = idx[q - role * B];
+        const int role = q >= B, qi = idx ? idx[q - role * B] : q - role * B;
         const int len = lens[q];
         perm[p] = q;
         seq_len_s[p] = len;
@@ -450,9 +454,11 @@ __global__ __launch_bounds__(256) void bb_expand_kernel(const int32_t* __restric
     }
 }
 
+// E2 = total of flag[0 .. *n_ptr) from its exclusive scan pos (flag = kept facts per entry: 0 / 1 per fact, or a count per node)
 __global__ void bb_set_e2_kernel(const int32_t* __restrict__ flag, const int32_t* __restrict__ pos,
-                                 int32_t* __restrict__ counts, int cap_facts, int cap_edges) {
-    const int F = min(counts[RENET_BB_FACTS], cap_facts);
+                                 int32_t* __restrict__ counts, const int32_t* __restrict__ n_ptr, int cap_facts,
+                                 int cap_edges) {
+    const int F = min(*n_ptr, cap_facts);
     int e2 = F > 0 ? pos[F - 1] + flag[F - 1] : 0;
     if (counts[RENET_BB_ERR] != 0) e2 = 0;                 // node overflow / bad timestamp: no edges (new_id is not valid)
     if (2 * e2 > cap_edges) { atomicOr(&counts[RENET_BB_ERR], RENET_BB_ERR_EDGES); e2 = 0; }
@@ -746,6 +752,197 @@ __global__ __launch_bounds__(256) void fg_edges_kernel(FullStore st, const int32
         if (h1[i]) atomicAdd(&tc[i], h1[i]);
 }
 
+// ================================================================================================================
+// GROUPED inference batches (graph.build_batch(..., group=...); RGCNAggregator.forward_grouped): one direction of B
+// sequences, a member graph (slot) per (group, timestamp) pair.  Thousands of slots: no [slot][entity] table (slot * num_ent
+// passes 2^31) -- slots and node sets are numbered by sorting 64-bit keys, membership is a binary search in the sorted keys,
+// and the induced edges walk the store's per-timestamp subject index from every node (graph._induced_edges(sparse=True)).
+// Stages A / B are bb_seq_kernel (Q = B) and bb_steps_kernel; everything behind the half edges is bb_expand_kernel +
+// build_tail, shared with renet_build_batch_both.
+struct GroupedStore {
+    const int32_t* group;
+    const int32_t* snap_ptr;
+    const int32_t* nbr_o;
+    const int32_t* trip_ptr;
+    const int32_t *trip_s, *trip_r, *trip_o;
+    const int32_t *by_subj, *subj_sorted;
+    int n_steps, n_nbr, n_facts;
+};
+
+constexpr uint64_t GB_NONE = ~0ull;                        // sentinel key: sorted behind every valid key
+
+__device__ __forceinline__ int lower_bound_u64(const uint64_t* a, int n, uint64_t v) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (a[mid] < v) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// S as the grouped stages see it: 0 after a bad timestamp (bb_steps_kernel then left step arrays unwritten)
+__device__ __forceinline__ int gb_steps(const int32_t* counts) {
+    return (counts[RENET_BB_ERR] & (RENET_BB_ERR_TIME | RENET_BB_ERR_GLOB)) ? 0 : counts[RENET_BB_S];
+}
+
+// row of node (slot, entity) in the batch, -1 if it is not a node: ukey = the N sorted unique keys, uid their rows
+__device__ __forceinline__ int gb_row_of(const uint64_t* ukey, const int32_t* uid, int N, uint64_t key) {
+    const int u = lower_bound_u64(ukey, N, key);
+    return (u < N && ukey[u] == key) ? uid[u] : -1;
+}
+
+// ---- grouped stage C: slots.  Key of step k = (group << 32) | timestamp index; thread per (sorted sequence i, step j) ----
+__global__ __launch_bounds__(256) void gb_slot_keys_kernel(GroupedStore gs, const int32_t* __restrict__ counts,
+                                                           const int32_t* __restrict__ perm,
+                                                           const int32_t* __restrict__ seq_len_s,
+                                                           const int32_t* __restrict__ seq_start,
+                                                           const int32_t* __restrict__ step_dense,
+                                                           uint64_t* __restrict__ gkey) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    const int i = t / BB_MAXL, j = t - i * BB_MAXL;
+    if (gb_steps(counts) == 0 || i >= counts[RENET_BB_NNZ] || j >= seq_len_s[i]) return;
+    const int k = seq_start[i] + j;
+    gkey[k] = ((uint64_t)(uint32_t)gs.group[perm[i]] << 32) | (uint32_t)step_dense[k];
+}
+
+// first-of-run flags of a sorted key array (sentinels are no keys); shift = 1 drops the neighbour bit of the node keys.
+// fb (node keys only): the run has no subject key, i.e. its first key carries the neighbour bit.
+__global__ __launch_bounds__(256) void gb_run_flags_kernel(const uint64_t* __restrict__ skey, int cap, int shift,
+                                                           int32_t* __restrict__ fa, int32_t* __restrict__ fb) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cap) return;
+    const uint64_t k = skey[i];
+    const bool first = k != GB_NONE && (i == 0 || (k >> shift) != (skey[i - 1] >> shift));
+    const bool nbr = shift && (k & 1);
+    fa[i] = first && !nbr;
+    if (fb) fb[i] = first && nbr;
+}
+
+__global__ __launch_bounds__(256) void gb_slots_kernel(const uint64_t* __restrict__ skey, int cap,
+                                                       const int32_t* __restrict__ flag, const int32_t* __restrict__ pos,
+                                                       uint64_t* __restrict__ slot_key, int32_t* __restrict__ slot_ti,
+                                                       int32_t* __restrict__ counts) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cap) return;
+    if (flag[i]) { slot_key[pos[i]] = skey[i]; slot_ti[pos[i]] = (int32_t)(uint32_t)skey[i]; }
+    if (i == cap - 1) counts[RENET_BB_TB] = pos[i] + flag[i];
+}
+
+// ---- grouped stage D: node keys ((slot << 32 | entity) << 1) | neighbour bit.  One WAVE per step: lane 0 the subject (at
+// the step's own position), the lanes the neighbours (behind the steps, at the neighbour's position): no scan, every key
+// has a place of its own and the unused places keep the sentinel.
+__global__ __launch_bounds__(256) void gb_node_keys_kernel(GroupedStore gs, const int32_t* __restrict__ counts,
+                                                           const int32_t* __restrict__ step_snap,
+                                                           const int32_t* __restrict__ step_packed,
+                                                           const int32_t* __restrict__ row_ent,
+                                                           const uint64_t* __restrict__ gkey,
+                                                           const uint64_t* __restrict__ slot_key,
+                                                           int32_t* __restrict__ slot_k, uint64_t* __restrict__ nkey) {
+    const int k = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (k >= gb_steps(counts)) return;
+    const int lane = threadIdx.x & 63;
+    const int snap = step_snap[k] & 0x3FFFFFFF;
+    if (snap >= gs.n_steps) return;
+    const uint64_t slot = (uint64_t)lower_bound_u64(slot_key, counts[RENET_BB_TB], gkey[k]);
+    if (lane == 0) {
+        slot_k[k] = (int)slot;
+        nkey[snap] = ((slot << 32) | (uint32_t)row_ent[step_packed[k]]) << 1;
+    }
+    const int b = gs.snap_ptr[snap], e = min(gs.snap_ptr[snap + 1], gs.n_nbr);
+    for (int n = b + lane; n < e; n += 64) nkey[(size_t)gs.n_steps + n] = (((slot << 32) | (uint32_t)gs.nbr_o[n]) << 1) | 1;
+}
+
+// ---- grouped stage E: numbering: subject keys first (in key order), then the others (in key order) ------------------
+__global__ void gb_node_count_kernel(const int32_t* __restrict__ fa, const int32_t* __restrict__ pa,
+                                     const int32_t* __restrict__ fb, const int32_t* __restrict__ pb, int cap, int cap_nodes,
+                                     int32_t* __restrict__ counts) {
+    const int nA = pa[cap - 1] + fa[cap - 1], nB = pb[cap - 1] + fb[cap - 1];
+    const bool over = (long long)nA + nB > cap_nodes;
+    if (over) atomicOr(&counts[RENET_BB_ERR], RENET_BB_ERR_NODES);  // every later stage then sees an EMPTY graph (no OOB access)
+    counts[RENET_BB_NA] = over ? 0 : nA;
+    counts[RENET_BB_N] = over ? 0 : nA + nB;
+}
+
+__global__ __launch_bounds__(256) void gb_number_kernel(const uint64_t* __restrict__ skey, int cap,
+                                                        const int32_t* __restrict__ fa, const int32_t* __restrict__ pa,
+                                                        const int32_t* __restrict__ fb, const int32_t* __restrict__ pb,
+                                                        const int32_t* __restrict__ counts, uint64_t* __restrict__ ukey,
+                                                        int32_t* __restrict__ uid, int32_t* __restrict__ node_ent,
+                                                        int32_t* __restrict__ node_slot) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cap || !(fa[i] | fb[i])) return;
+    const int N = counts[RENET_BB_N], nA = counts[RENET_BB_NA];
+    const int u = pa[i] + pb[i], id = fa[i] ? pa[i] : nA + pb[i];
+    if (u >= N || id >= N) return;                          // (N = 0 after an overflow)
+    const uint64_t key = skey[i] >> 1;
+    ukey[u] = key;
+    uid[u] = id;
+    node_ent[id] = (int32_t)(uint32_t)key;
+    node_slot[id] = (int32_t)(key >> 32);
+}
+
+// subject row of every step, in packed order
+__global__ __launch_bounds__(256) void gb_subj_row_kernel(const int32_t* __restrict__ counts,
+                                                          const int32_t* __restrict__ step_packed,
+                                                          const int32_t* __restrict__ row_ent,
+                                                          const int32_t* __restrict__ slot_k,
+                                                          const uint64_t* __restrict__ ukey, const int32_t* __restrict__ uid,
+                                                          int32_t* __restrict__ subj_row) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    const int N = counts[RENET_BB_N];
+    if (k >= gb_steps(counts) || N == 0) return;
+    const int p = step_packed[k];
+    subj_row[p] = max(gb_row_of(ukey, uid, N, ((uint64_t)slot_k[k] << 32) | (uint32_t)row_ent[p]), 0);
+}
+
+// ---- grouped stage F: induced edges, sparse.  Thread per node (slot, e): the facts of the slot's timestamp with subject e
+// (a range of the subject index) whose object is a node of the slot.  emit = 0: counts them; emit = 1: writes their keys
+// (slot << 32) | fact behind the node's scanned offset.  Sorting those keys restores the host's order: slot-major, and
+// inside a slot the store's fact order.
+__global__ __launch_bounds__(256) void gb_node_facts_kernel(GroupedStore gs, const int32_t* __restrict__ counts, int cap_nodes,
+                                                            const uint64_t* __restrict__ ukey,
+                                                            const int32_t* __restrict__ slot_ti, int emit,
+                                                            int32_t* __restrict__ ecnt, const int32_t* __restrict__ epos,
+                                                            uint64_t* __restrict__ fkey) {
+    const int u = blockIdx.x * blockDim.x + threadIdx.x;
+    if (u >= cap_nodes) return;
+    const int N = counts[RENET_BB_N];
+    int c = 0;
+    if (u < N && (!emit || counts[RENET_BB_E2] > 0)) {
+        const uint64_t key = ukey[u], slot = key >> 32;
+        const int ent = (int)(uint32_t)key, ti = slot_ti[slot];
+        const int b = gs.trip_ptr[ti], e = min(gs.trip_ptr[ti + 1], gs.n_facts);
+        const int lim = emit ? counts[RENET_BB_E2] : 0, at = emit ? epos[u] : 0;
+        for (int q = b + lower_bound_i32(gs.subj_sorted + b, e - b, ent); q < e && gs.subj_sorted[q] == ent; ++q) {
+            const int j = gs.by_subj[q];
+            if ((unsigned)j >= (unsigned)gs.n_facts) continue;      // (the index is range-checked on the host; never index past it)
+            const uint64_t ko = (slot << 32) | (uint32_t)gs.trip_o[j];
+            const int v = lower_bound_u64(ukey, N, ko);
+            if (v >= N || ukey[v] != ko) continue;
+            if (emit && at + c < lim) fkey[at + c] = (slot << 32) | (uint32_t)j;
+            ++c;
+        }
+    }
+    if (!emit) ecnt[u] = c;
+}
+
+// the half edges of the sorted fact keys: local subject row -> local object row, type r (type_s: the direction is the
+// kernels' type_shift)
+__global__ __launch_bounds__(256) void gb_half_edges_kernel(GroupedStore gs, const int32_t* __restrict__ counts,
+                                                            const uint64_t* __restrict__ fkey_sorted,
+                                                            const uint64_t* __restrict__ ukey, const int32_t* __restrict__ uid,
+                                                            int32_t* __restrict__ half_src, int32_t* __restrict__ half_dst,
+                                                            int32_t* __restrict__ half_et) {
+    const int m = blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= counts[RENET_BB_E2]) return;
+    const int N = counts[RENET_BB_N];
+    const uint64_t k = fkey_sorted[m], slot = k >> 32;
+    const int j = (int)(uint32_t)k;
+    half_src[m] = max(gb_row_of(ukey, uid, N, (slot << 32) | (uint32_t)gs.trip_s[j]), 0);
+    half_dst[m] = max(gb_row_of(ukey, uid, N, (slot << 32) | (uint32_t)gs.trip_o[j]), 0);
+    half_et[m] = gs.trip_r[j];
+}
+
 inline int bits_for(uint64_t v) { int b = 1; while (b < 63 && (1ull << b) <= v) ++b; return b; }
 
 #define BB_HIP(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return (int)e__; } while (0)
@@ -837,7 +1034,7 @@ struct TailBufs {
         pkey = cv.take<uint32_t>(max(cap_nodes, cap_steps));
         pflag = cv.take<int32_t>(max(cap_nodes, cap_steps) + 2);
         ppos = cv.take<int32_t>(max(cap_nodes, cap_steps) + 2);
-        tmp_bytes = rocprim_temp_bytes(cap_nodes, cap_edges, cap_facts);
+        tmp_bytes = rocprim_temp_bytes(cap_nodes, max(cap_edges, cap_steps), cap_facts);     // (plan 1 sorts cap_steps rows)
         tmp = cv.take<char>(tmp_bytes);
         return tmp != nullptr && cv.ok;
     }
@@ -904,11 +1101,77 @@ struct FullBufs : TailBufs {
     }
 };
 
+// scratch of the grouped front (renet_build_batch_grouped) + the tail
+struct GroupedBufs : TailBufs {
+    int32_t* seq_first;
+    int32_t* seq_len_s;
+    int32_t* seq_start;
+    int32_t* rel_label;            // (bb_seq_kernel writes labels; a grouped batch has none)
+    int32_t* ent_label;
+    int32_t* step_snap;
+    int32_t* step_dense;           // timestamp index of every step
+    int32_t* step_packed;
+    int32_t* slot_used;
+    uint64_t* gkey;                // [cap_steps] slot key of every step
+    uint64_t* slot_key;            // [cap_steps] the Tb unique slot keys, sorted
+    int32_t* slot_ti;
+    int32_t* slot_k;               // [cap_steps] slot of every step
+    uint64_t* nkey;                // [cap_keys] node keys, a place per step and per neighbour
+    uint64_t* skey;                // [max(cap_keys, cap_steps, cap_edges / 2)] sorted keys of the sort at hand
+    uint64_t* ukey;                // [cap_keys] the N unique node keys, sorted
+    int32_t* uid;                  // [cap_keys] their rows
+    int32_t* fa;                   // [cap_scan] flags / counts and their scans
+    int32_t* pa;
+    int32_t* fb;
+    int32_t* pb;
+    uint64_t* fkey;                // [cap_edges / 2] keys of the kept facts
+    int32_t* half_src;
+    int32_t* half_dst;
+    int32_t* half_et;
+    void* tmp64;                   // rocPRIM scratch of the 64-bit key sorts
+    size_t tmp64_bytes;
+    static int cap_keys(const RenetGroupedStoreDev* sd) { return max(sd->n_steps, 0) + max(sd->n_nbr, 0) + 1; }
+    bool carve(Carver& cv, const RenetGroupedStoreDev* sd, int B, int cap_nodes, int cap_edges) {
+        const int cap_steps = B * BB_MAXL, ck = cap_keys(sd), ce2 = max(cap_edges / 2, 1);
+        const int cap_sort = max(max(ck, cap_steps), ce2), cap_scan = max(max(ck, cap_steps), cap_nodes) + 2;
+        seq_first = cv.take<int32_t>(BB_MAXQ);
+        seq_len_s = cv.take<int32_t>(BB_MAXQ);
+        seq_start = cv.take<int32_t>(BB_MAXQ);
+        rel_label = cv.take<int32_t>(BB_MAXQ);
+        ent_label = cv.take<int32_t>(BB_MAXQ);
+        step_snap = cv.take<int32_t>(cap_steps);
+        step_dense = cv.take<int32_t>(cap_steps);
+        step_packed = cv.take<int32_t>(cap_steps);
+        slot_used = cv.take<int32_t>(2 * sd->T + 2);
+        gkey = cv.take<uint64_t>(cap_steps);
+        slot_key = cv.take<uint64_t>(cap_steps);
+        slot_ti = cv.take<int32_t>(cap_steps);
+        slot_k = cv.take<int32_t>(cap_steps);
+        nkey = cv.take<uint64_t>(ck);
+        skey = cv.take<uint64_t>(cap_sort);
+        ukey = cv.take<uint64_t>(ck);
+        uid = cv.take<int32_t>(ck);
+        fa = cv.take<int32_t>(cap_scan);
+        pa = cv.take<int32_t>(cap_scan);
+        fb = cv.take<int32_t>(cap_scan);
+        pb = cv.take<int32_t>(cap_scan);
+        fkey = cv.take<uint64_t>(ce2);
+        half_src = cv.take<int32_t>(ce2);
+        half_dst = cv.take<int32_t>(ce2);
+        half_et = cv.take<int32_t>(ce2);
+        size_t t = 0;
+        (void)rocprim::radix_sort_keys(nullptr, t, (uint64_t*)nullptr, (uint64_t*)nullptr, (size_t)cap_sort, 0, 64);
+        tmp64_bytes = (t + 255) & ~(size_t)255;
+        tmp64 = cv.take<char>(tmp64_bytes);
+        return carve_tail(cv, cap_nodes, cap_edges, cap_steps, cap_scan, true) && tmp64 != nullptr;
+    }
+};
+
 // ---- the shared tail: stages F (sorts, rows, chunks), G (item stream, wave groups) and H (the first n_plans plans) over an
 // edge list that a front has left in bf.src / dst / et with its keys, bf.deg and the histograms.  pruned = false: the
 // batch has no row prefix (nA = N): the *2 lists, n_chunks2 and n_groups_out's own scan are not computed.
 int build_tail(const TailBufs& bf, const RenetBatchOut* out, int cap_nodes, int cap_edges, int cap_steps, int num_ent, int T2,
-               int key_bits, int heavy_thr, int group_budget, int chunk, int n_plans, int B, bool pruned, hipStream_t st) {
+               int key_bits, int heavy_thr, int group_budget, int chunk, int n_plans, int n_seq, bool pruned, hipStream_t st) {
     int32_t* counts = out->counts;
     int32_t* err = counts + RENET_BB_ERR;
     const int cap_chunks = cap_edges / chunk + T2 + 1;
@@ -958,12 +1221,12 @@ int build_tail(const TailBufs& bf, const RenetBatchOut* out, int cap_nodes, int 
                  bf.first_pos, pruned ? bf.first_out_pos : bf.first_pos, pruned ? bf.first_out : bf.first_flag, bf.item_start,
                  bf.item_cnt, out->grp_ptr);
     RENET_LAUNCH_CHECK();
-    // segmented-add plans: 0 node_ent (N rows), 1 subj_row (S rows), 2 s_sorted (2B), 3 r_sorted (2B)
+    // segmented-add plans: 0 node_ent (N rows), 1 subj_row (S rows), 2 s_sorted, 3 r_sorted (n_seq rows: every sequence)
     for (int pl = 0; pl < n_plans; ++pl) {
         const int32_t* idx = pl == 0 ? out->node_ent : pl == 1 ? out->subj_row : pl == 2 ? out->s_sorted : out->r_sorted;
         const int32_t* n_ptr = pl == 0 ? counts + RENET_BB_N : pl == 1 ? counts + RENET_BB_S : nullptr;
-        const int n_fixed = 2 * B;
-        const int cap = pl == 0 ? cap_nodes : pl == 1 ? cap_steps : 2 * B;
+        const int n_fixed = n_seq;
+        const int cap = pl == 0 ? cap_nodes : pl == 1 ? cap_steps : n_seq;
         const uint64_t bound = pl == 0 ? (uint64_t)num_ent : pl == 1 ? (uint64_t)cap_nodes
                                : pl == 2 ? (uint64_t)num_ent : (uint64_t)T2;
         const int kb = bits_for(bound);
@@ -1031,7 +1294,7 @@ int renet_build_batch_both(const RenetStoreDev* sd, const int32_t* idx_dev, int 
     BB_HIP(hipMemsetAsync(bf.deg, 0, (size_t)(cap_nodes + 2) * sizeof(int32_t), st));
     BB_HIP(hipMemsetAsync(bf.tc, 0, 2 * 1024 * sizeof(int32_t), st));      // bf.tc and bf.tc2 are adjacent 4 KB blocks
 
-    RENET_LAUNCH(bb_seq_kernel, dim3(1), dim3(1024), 0, st, S, idx_dev, B, seq_len, out->perm, bf.seq_first, bf.seq_len_s,
+    RENET_LAUNCH(bb_seq_kernel, dim3(1), dim3(1024), 0, st, S, idx_dev, B, 2 * B, seq_len, out->perm, bf.seq_first, bf.seq_len_s,
                  bf.seq_start, out->s_sorted, out->r_sorted, out->rel_label, out->ent_label, out->step_off, counts);
     RENET_LAUNCH_CHECK();
     RENET_LAUNCH(bb_steps_kernel, dim3((2 * B * BB_MAXL + 255) / 256), dim3(256), 0, st, S, B, out->perm, bf.seq_first,
@@ -1061,10 +1324,131 @@ int renet_build_batch_both(const RenetStoreDev* sd, const int32_t* idx_dev, int 
     RENET_LAUNCH_CHECK();
     size_t tb = bf.tmp_bytes;
     BB_HIP(rocprim::exclusive_scan(bf.tmp, tb, bf.flag, bf.pos, 0, (size_t)cap_facts, rocprim::plus<int>(), st));
-    RENET_LAUNCH(bb_set_e2_kernel, dim3(1), dim3(1), 0, st, bf.flag, bf.pos, counts, cap_facts, cap_edges);
+    RENET_LAUNCH(bb_set_e2_kernel, dim3(1), dim3(1), 0, st, bf.flag, bf.pos, counts, counts + RENET_BB_FACTS, cap_facts, cap_edges);
     RENET_LAUNCH_CHECK();
     RENET_LAUNCH(bb_edges_kernel, dim3((cap_facts + 255) / 256), dim3(256), 0, st, S, counts, bf.fact_off, bf.slot_ti,
                  bf.slot_group, bf.flag, bf.pos, bf.fslot, bf.new_id, cap_facts, cap_edges, bf.half_src, bf.half_dst, bf.half_et, err);
+    RENET_LAUNCH_CHECK();
+    RENET_LAUNCH(bb_expand_kernel, dim3(min((cap_edges + 255) / 256, 1024)), dim3(256), 0, st, counts, sd->num_rels, cap_edges,
+                 key_bits, bf.half_src, bf.half_dst, bf.half_et, bf.src, bf.dst, bf.et, bf.key_dt, bf.key_t, bf.key_t2, bf.iota, bf.deg, bf.tc, bf.tc2);
+    RENET_LAUNCH_CHECK();
+    const int rc = build_tail(bf, out, cap_nodes, cap_edges, cap_steps, sd->num_ent, T2, key_bits, heavy_thr, group_budget, chunk,
+                              4, 2 * B, true, st);
+    if (rc != RENET_OK) return rc;
+    RENET_LAUNCH(bb_finish_kernel, dim3(1), dim3(64), 0, st, out->row_ptr, out->step_off, counts);
+    RENET_LAUNCH_CHECK();
+    return RENET_OK;
+}
+
+size_t renet_build_batch_grouped_workspace(const RenetGroupedStoreDev* sd, int B, int cap_nodes, int cap_edges) {
+    if (!sd || B <= 0 || B > BB_MAXQ || cap_nodes <= 0 || cap_edges < 2 || sd->T <= 0 || sd->n_steps < 0 || sd->n_nbr < 0) return 0;
+    Carver dry{reinterpret_cast<char*>(256), ~(size_t)0 >> 2};          // never dereferenced
+    GroupedBufs b;
+    b.carve(dry, sd, B, cap_nodes, cap_edges & ~1);
+    return dry.used + 256;
+}
+
+int renet_build_batch_grouped(const RenetGroupedStoreDev* sd, const int32_t* idx_dev, int B, int seq_len, int heavy_thr,
+                              int group_budget, int chunk, const RenetBatchOut* out, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+    if (!sd || !out || B <= 0 || B > BB_MAXQ || seq_len <= 0 || seq_len > BB_MAXL || sd->n_steps < 0 || sd->n_nbr < 0 ||
+        sd->n_facts < 0 || out->cap_nodes <= 0 || out->cap_edges < 2)
+        return RENET_ERR_BADARG;
+    if (2 * sd->num_rels > 1024 || sd->num_rels <= 0 || sd->T <= 0 || group_budget + heavy_thr + 1 > 64 || chunk <= 0 ||
+        (long long)sd->n_steps + sd->n_nbr >= (1ll << 30))
+        return RENET_ERR_UNSUPPORTED;
+    if (workspace_bytes < renet_build_batch_grouped_workspace(sd, B, out->cap_nodes, out->cap_edges)) return RENET_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    // the batch's own arrays as the one-role history index that bb_seq_kernel / bb_steps_kernel read
+    Store S;
+    S.q_s = sd->s; S.q_r = sd->r; S.q_o = sd->s;
+    for (int r = 0; r < 2; ++r) {
+        S.h_first[r] = sd->h_first; S.h_count[r] = sd->h_count; S.snap_t[r] = sd->step_t;
+        S.snap_ptr[r] = sd->nbr_ptr; S.nbr_o[r] = sd->nbr_o;
+    }
+    S.times = sd->times; S.trip_ptr = sd->trip_ptr; S.trip_s = sd->trip_s; S.trip_r = sd->trip_r; S.trip_o = sd->trip_o;
+    S.glob_times = sd->glob_times; S.T = sd->T; S.n_glob = sd->n_glob; S.num_ent = sd->num_ent; S.num_rels = sd->num_rels;
+    GroupedStore GS;
+    GS.group = sd->group; GS.snap_ptr = sd->nbr_ptr; GS.nbr_o = sd->nbr_o; GS.trip_ptr = sd->trip_ptr;
+    GS.trip_s = sd->trip_s; GS.trip_r = sd->trip_r; GS.trip_o = sd->trip_o; GS.by_subj = sd->by_subj;
+    GS.subj_sorted = sd->subj_sorted; GS.n_steps = sd->n_steps; GS.n_nbr = sd->n_nbr; GS.n_facts = sd->n_facts;
+    const int cap_nodes = out->cap_nodes, cap_edges = out->cap_edges & ~1, ce2 = cap_edges / 2;
+    const int cap_steps = B * BB_MAXL, ck = GroupedBufs::cap_keys(sd);
+    const int T2 = 2 * sd->num_rels;
+    if ((uint64_t)cap_nodes * T2 >= (1ull << 31)) return RENET_ERR_UNSUPPORTED;
+    const int key_bits = bits_for((uint64_t)cap_nodes * T2);
+    // sorted bits of the node / fact keys: a slot is < cap_steps < 2^slot_bits - 1, so the sentinel's ones still sort last
+    const int slot_bits = bits_for((uint64_t)cap_steps);
+
+    Carver cv{reinterpret_cast<char*>(workspace), workspace_bytes};
+    GroupedBufs bf;
+    if (!bf.carve(cv, sd, B, cap_nodes, cap_edges)) return RENET_ERR_WORKSPACE;
+    int32_t* counts = out->counts;
+    int32_t* err = counts + RENET_BB_ERR;
+
+    BB_HIP(hipMemsetAsync(counts, 0, RENET_BB_NCOUNTS * sizeof(int32_t), st));
+    BB_HIP(hipMemsetAsync(bf.gkey, 0xFF, (size_t)cap_steps * sizeof(uint64_t), st));           // GB_NONE
+    BB_HIP(hipMemsetAsync(bf.nkey, 0xFF, (size_t)ck * sizeof(uint64_t), st));
+    BB_HIP(hipMemsetAsync(bf.fkey, 0xFF, (size_t)ce2 * sizeof(uint64_t), st));
+    BB_HIP(hipMemsetAsync(bf.deg, 0, (size_t)(cap_nodes + 2) * sizeof(int32_t), st));
+    BB_HIP(hipMemsetAsync(bf.tc, 0, 2 * 1024 * sizeof(int32_t), st));      // bf.tc and bf.tc2 are adjacent 4 KB blocks
+
+    // A, B: length sort and steps, subject side only (Q = B: every sequence has role 0)
+    RENET_LAUNCH(bb_seq_kernel, dim3(1), dim3(1024), 0, st, S, idx_dev, B, B, seq_len, out->perm, bf.seq_first, bf.seq_len_s,
+                 bf.seq_start, out->s_sorted, out->r_sorted, bf.rel_label, bf.ent_label, out->step_off, counts);
+    RENET_LAUNCH_CHECK();
+    RENET_LAUNCH(bb_steps_kernel, dim3((cap_steps + 255) / 256), dim3(256), 0, st, S, B, out->perm, bf.seq_first,
+                 bf.seq_len_s, bf.seq_start, out->s_sorted, out->r_sorted, out->step_off, counts, bf.step_snap, bf.step_dense,
+                 bf.step_packed, bf.slot_used, out->row_seq, out->row_ent, out->row_rel, out->glob_row, err);
+    RENET_LAUNCH_CHECK();
+    // C: slots = sorted unique (group, timestamp index) keys
+    RENET_LAUNCH(gb_slot_keys_kernel, dim3((cap_steps + 255) / 256), dim3(256), 0, st, GS, counts, out->perm, bf.seq_len_s,
+                 bf.seq_start, bf.step_dense, bf.gkey);
+    RENET_LAUNCH_CHECK();
+    size_t tb = bf.tmp64_bytes;
+    BB_HIP(rocprim::radix_sort_keys(bf.tmp64, tb, bf.gkey, bf.skey, (size_t)cap_steps, 0, 64, st));
+    RENET_LAUNCH(gb_run_flags_kernel, dim3((cap_steps + 255) / 256), dim3(256), 0, st, bf.skey, cap_steps, 0, bf.fa, (int32_t*)nullptr);
+    RENET_LAUNCH_CHECK();
+    tb = bf.tmp_bytes;
+    BB_HIP(rocprim::exclusive_scan(bf.tmp, tb, bf.fa, bf.pa, 0, (size_t)cap_steps, rocprim::plus<int>(), st));
+    RENET_LAUNCH(gb_slots_kernel, dim3((cap_steps + 255) / 256), dim3(256), 0, st, bf.skey, cap_steps, bf.fa, bf.pa, bf.slot_key,
+                 bf.slot_ti, counts);
+    RENET_LAUNCH_CHECK();
+    // D, E: node sets = sorted unique (slot, entity) keys, subject rows numbered first
+    RENET_LAUNCH(gb_node_keys_kernel, dim3((cap_steps + 3) / 4), dim3(256), 0, st, GS, counts, bf.step_snap, bf.step_packed,
+                 out->row_ent, bf.gkey, bf.slot_key, bf.slot_k, bf.nkey);
+    RENET_LAUNCH_CHECK();
+    tb = bf.tmp64_bytes;
+    BB_HIP(rocprim::radix_sort_keys(bf.tmp64, tb, bf.nkey, bf.skey, (size_t)ck, 0, 33 + slot_bits, st));
+    RENET_LAUNCH(gb_run_flags_kernel, dim3((ck + 255) / 256), dim3(256), 0, st, bf.skey, ck, 1, bf.fa, bf.fb);
+    RENET_LAUNCH_CHECK();
+    tb = bf.tmp_bytes;
+    BB_HIP(rocprim::exclusive_scan(bf.tmp, tb, bf.fa, bf.pa, 0, (size_t)ck, rocprim::plus<int>(), st));
+    tb = bf.tmp_bytes;
+    BB_HIP(rocprim::exclusive_scan(bf.tmp, tb, bf.fb, bf.pb, 0, (size_t)ck, rocprim::plus<int>(), st));
+    RENET_LAUNCH(gb_node_count_kernel, dim3(1), dim3(1), 0, st, bf.fa, bf.pa, bf.fb, bf.pb, ck, cap_nodes, counts);
+    RENET_LAUNCH_CHECK();
+    RENET_LAUNCH(gb_number_kernel, dim3((ck + 255) / 256), dim3(256), 0, st, bf.skey, ck, bf.fa, bf.pa, bf.fb, bf.pb, counts,
+                 bf.ukey, bf.uid, out->node_ent, out->node_slot);
+    RENET_LAUNCH_CHECK();
+    RENET_LAUNCH(gb_subj_row_kernel, dim3((cap_steps + 255) / 256), dim3(256), 0, st, counts, bf.step_packed, out->row_ent,
+                 bf.slot_k, bf.ukey, bf.uid, out->subj_row);
+    RENET_LAUNCH_CHECK();
+    // F: induced edges through the subject index: count per node, scan, emit fact keys, sort back to (slot, fact) order
+    RENET_LAUNCH(gb_node_facts_kernel, dim3((cap_nodes + 255) / 256), dim3(256), 0, st, GS, counts, cap_nodes, bf.ukey, bf.slot_ti,
+                 0, bf.fa, bf.pa, bf.fkey);
+    RENET_LAUNCH_CHECK();
+    tb = bf.tmp_bytes;
+    BB_HIP(rocprim::exclusive_scan(bf.tmp, tb, bf.fa, bf.pa, 0, (size_t)cap_nodes, rocprim::plus<int>(), st));
+    RENET_LAUNCH(bb_set_e2_kernel, dim3(1), dim3(1), 0, st, bf.fa, bf.pa, counts, counts + RENET_BB_N, cap_nodes, cap_edges);
+    RENET_LAUNCH_CHECK();
+    RENET_LAUNCH(gb_node_facts_kernel, dim3((cap_nodes + 255) / 256), dim3(256), 0, st, GS, counts, cap_nodes, bf.ukey, bf.slot_ti,
+                 1, bf.fa, bf.pa, bf.fkey);
+    RENET_LAUNCH_CHECK();
+    tb = bf.tmp64_bytes;
+    BB_HIP(rocprim::radix_sort_keys(bf.tmp64, tb, bf.fkey, bf.skey, (size_t)ce2, 0, 32 + slot_bits, st));
+    RENET_LAUNCH(gb_half_edges_kernel, dim3((ce2 + 255) / 256), dim3(256), 0, st, GS, counts, bf.skey, bf.ukey, bf.uid,
+                 bf.half_src, bf.half_dst, bf.half_et);
     RENET_LAUNCH_CHECK();
     RENET_LAUNCH(bb_expand_kernel, dim3(min((cap_edges + 255) / 256, 1024)), dim3(256), 0, st, counts, sd->num_rels, cap_edges,
                  key_bits, bf.half_src, bf.half_dst, bf.half_et, bf.src, bf.dst, bf.et, bf.key_dt, bf.key_t, bf.key_t2, bf.iota, bf.deg, bf.tc, bf.tc2);

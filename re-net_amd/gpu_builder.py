@@ -13,10 +13,14 @@ The global model's full-graph batches (graph.build_full_graphs; Aggregator.py:44
 full graphs of a list of timestamps (csrc/builder.hip: renet_build_full_graphs, the same tail kernels behind a three-kernel
 front), again bit-identical to the host builder (tests/test_gpu_full_graph_builder.py).
 
+Grouped inference batches (graph.build_batch(group=...), RGCNAggregator.forward_grouped) are the third front:
+`GroupedBatchStore` uploads one call's s / r / group / FlatHistory, `GroupedDeviceBatch` is the batch of ONE direction with
+a member graph per (group, timestamp) (renet_build_batch_grouped), bit-identical again (tests/test_gpu_grouped_builder.py).
+
 Layout of this file: the ctypes mirrors of the structs and count slots of include/renet_hip.h (tests/test_host_cpu.py holds
 them to the header); `_Store`, the base of the resident stores, and the per-graph_dict cache `_cached_store`; `_launch`,
 the one place that lays out, allocates and calls a builder front; `_PendingBatch`, the life cycle of a batch from the
-launch to finalize(), of which `DeviceBatch` and `FullGraphBatch` are a front plus the fields each adds."""
+launch to finalize(), of which `DeviceBatch`, `GroupedDeviceBatch` and `FullGraphBatch` are a front plus the fields each adds."""
 import ctypes
 import weakref
 
@@ -55,6 +59,12 @@ class _FullStoreDev(ctypes.Structure):
     _fields_ = [('node_ptr', _P), ('node_ent_all', _P), ('trip_ptr', _P), ('trip_ls', _P), ('trip_r', _P), ('trip_lo', _P),
                 ('T', ctypes.c_int), ('n_nodes', ctypes.c_int), ('n_facts', ctypes.c_int), ('num_ent', ctypes.c_int),
                 ('num_rels', ctypes.c_int)]
+
+
+class _GroupedStoreDev(ctypes.Structure):
+    _fields_ = [(n, _P) for n in ('s', 'r', 'group', 'h_first', 'h_count', 'step_t', 'nbr_ptr', 'nbr_o', 'times', 'trip_ptr',
+                                  'trip_s', 'trip_r', 'trip_o', 'glob_times', 'by_subj', 'subj_sorted')] + \
+               [(n, ctypes.c_int) for n in ('n_steps', 'n_nbr', 'T', 'n_glob', 'n_facts', 'num_ent', 'num_rels')]
 
 
 def _bind():
@@ -114,6 +124,16 @@ class GraphDeviceStore(_Store):
         # capacities: grown on demand (an overflow is reported in the counts and the batch rebuilt)
         self.cap_nodes, self.cap_edges = 1 << 17, 1 << 19
         self.c = None                         # (a ListBatchStore fills a struct per batch)
+        self._store = store
+
+    def subject_index(self):
+        """Device (by_subj, subj_sorted) of graph.GraphStore.subject_index(), uploaded on first use: the grouped front walks
+        the facts of a node through it."""
+        if 'by_subj' not in self.t:
+            by_subj, subj_sorted = self._store.subject_index()
+            _check_int32('fact indices', by_subj)
+            self.t.update(by_subj=_i32(by_subj, self.device), subj_sorted=_i32(subj_sorted, self.device))
+        return self.t['by_subj'], self.t['subj_sorted']
 
 
 class DeviceStore(GraphDeviceStore):
@@ -221,6 +241,58 @@ class ListBatchStore(object):
         self.base._give_pinned(buf)
 
 
+MAX_GROUPED = 4096           # sequences per grouped batch (one workgroup sorts their lengths)
+
+
+class GroupedBatchStore(ListBatchStore):
+    """What GroupedDeviceBatch needs of a store, for ONE grouped batch of one direction: its s, r, group and FlatHistory
+    (first / count per sequence, step timestamps, neighbour pointers, neighbours) uploaded in ONE int32 copy, on top of the
+    resident GraphDeviceStore and its subject index.  The ranges the host builder checks are checked here: the kernels
+    index with these ids."""
+
+    def __init__(self, base, s, r, group, fh, stream=None):
+        self.base = base
+        self.device, self.num_ent, self.num_rels = base.device, base.num_ent, base.num_rels
+        s, r, group = (np.asarray(a, dtype=np.int64).reshape(-1) for a in (s, r, group))
+        B = len(s)
+        if len(fh) != B or len(r) != B or len(group) != B:
+            raise ValueError('histories, subjects, relations and groups differ in length')
+        if base._store.max_ent >= self.num_ent or base._store.max_rel >= self.num_rels:
+            raise ValueError('graph_dict holds entity id %d / relation id %d but num_ent = %d, num_rels = %d'
+                             % (base._store.max_ent, base._store.max_rel, self.num_ent, self.num_rels))
+        parts = [s, r, group, fh.seq_ptr[:-1], np.diff(fh.seq_ptr), fh.step_t, fh.nbr_ptr, fh.nbr_o]
+        _check_int32('ids / timestamps', *parts)
+        if B and (s.max() >= self.num_ent or r.max() >= self.num_rels):
+            raise ValueError('batch subject / relation id out of range')
+        if len(fh.nbr_o) and fh.nbr_o.max() >= self.num_ent:
+            raise ValueError('history neighbour id out of range')
+        if len(fh.nbr_ptr) != len(fh.step_t) + 1 or fh.seq_ptr[-1] != len(fh.step_t) or fh.nbr_ptr[-1] != len(fh.nbr_o):
+            raise ValueError('inconsistent FlatHistory')
+        offs, tot = [], 0
+        for a in parts:
+            offs.append(tot)
+            tot += (len(a) + 15) & ~15                       # 64-byte aligned slices
+        flat = np.zeros(tot + 16, dtype=np.int32)
+        for a, o in zip(parts, offs):
+            flat[o:o + len(a)] = a
+        st = stream if stream is not None else torch.cuda.current_stream()
+        with torch.cuda.stream(st):
+            self._buf = torch.from_numpy(flat).to(self.device, non_blocking=True)
+            by_subj, subj_sorted = base.subject_index()
+        sd = _GroupedStoreDev()
+        for n, o in zip(('s', 'r', 'group', 'h_first', 'h_count', 'step_t', 'nbr_ptr', 'nbr_o'), offs):
+            setattr(sd, n, self._buf.data_ptr() + 4 * o)
+        for n in ('times', 'trip_ptr', 'trip_s', 'trip_r', 'trip_o', 'glob_times'):
+            setattr(sd, n, base.t[n].data_ptr())
+        sd.by_subj, sd.subj_sorted = by_subj.data_ptr(), subj_sorted.data_ptr()
+        sd.n_steps, sd.n_nbr = len(fh.step_t), len(fh.nbr_o)
+        sd.T, sd.n_glob, sd.n_facts = base.T, base.n_glob, base.n_facts
+        sd.num_ent, sd.num_rels = self.num_ent, self.num_rels
+        self.c = sd
+        self.n_quads = B
+        self.longest = int(np.diff(fh.seq_ptr).max()) if B else 0
+
+
 class _Host(object):
     """Host-side view of a DeviceBatch (what graph._HostView offers for a host-built batch)."""
 
@@ -238,8 +310,9 @@ class _Host(object):
         return self._perm
 
 
-# the two fronts of csrc/builder.hip: (workspace size, build) of the C ABI
+# the fronts of csrc/builder.hip: (workspace size, build) of the C ABI
 _FRONT_BOTH = ('renet_build_batch_workspace', 'renet_build_batch_both')
+_FRONT_GROUPED = ('renet_build_batch_grouped_workspace', 'renet_build_batch_grouped')
 _FRONT_FULL = ('renet_build_full_graphs_workspace', 'renet_build_full_graphs')
 
 
@@ -274,7 +347,7 @@ def _launch(front, store, idx_dev, n, lead, own, cn, ce, stream):
     for f in ('plan_order', 'plan_seg', 'plan_target'):
         setattr(out, f, (_P * 4)(*[v[f + str(k)].data_ptr() if f + str(k) in v else None for k in range(4)]))
     out.cap_nodes, out.cap_edges = cn, ce
-    rc = getattr(L, front[1])(ctypes.addressof(store.c), idx_dev.data_ptr(), n, *lead, G.HEAVY, G.GROUP_ITEMS, G.CHUNK,
+    rc = getattr(L, front[1])(ctypes.addressof(store.c), idx_dev.data_ptr() if idx_dev is not None else None, n, *lead, G.HEAVY, G.GROUP_ITEMS, G.CHUNK,
                               ctypes.addressof(out), ws.data_ptr(), nbytes, stream.cuda_stream)
     if rc != 0:
         raise K.RenetHipError('%s failed with code %d' % (front[1], rc))
@@ -291,9 +364,12 @@ class _PendingBatch(G.BatchGraph):
         G.BatchGraph.__init__(self)
         self.store = store
         st = stream if stream is not None else torch.cuda.current_stream()
-        with torch.cuda.stream(st):
-            idx_dev = torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int32)).to(store.device, non_blocking=True)
-        self._v, self._norm, self._keep = _launch(front, store, idx_dev, len(idx), lead, own, cn, ce, st)
+        idx_dev = None                               # (idx = None: the front takes the store's own order, nothing to upload)
+        if idx is not None:
+            with torch.cuda.stream(st):
+                idx_dev = torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int32)).to(store.device, non_blocking=True)
+        n = len(idx) if idx is not None else store.n_quads
+        self._v, self._norm, self._keep = _launch(front, store, idx_dev, n, lead, own, cn, ce, st)
         self._counts_host = store._take_pinned()     # owned by this batch until finalize() / release
         self._stream = st
         with torch.cuda.stream(st):
@@ -367,6 +443,8 @@ class DeviceBatch(_PendingBatch):
     """A merged batch built on the device from the quadruple indices `idx` of `store`.  After finalize() it carries the
     attributes of graph.BatchGraph, graph and sequence part, with the row prefix [0, nA) of the subject rows."""
 
+    _LABELS = ('rel_label', 'ent_label')
+
     def __init__(self, store, idx, seq_len, stream=None):
         self.n_quads = int(len(idx))
         self.B = B2 = 2 * self.n_quads              # sequences of the merged batch (graph.HostBatch.B)
@@ -405,12 +483,37 @@ class DeviceBatch(_PendingBatch):
         self.e_src2, self.e_dst2 = v['e_src2'][:self.E_out], v['e_dst2'][:self.E_out]
         for n in ('subj_row', 'row_seq', 'row_ent', 'row_rel', 'glob_row'):
             setattr(self, n, v[n][:S])
-        for n in ('s_sorted', 'r_sorted', 'rel_label', 'ent_label'):
+        for n in ('s_sorted', 'r_sorted') + self._LABELS:
             setattr(self, n, v[n])
         self.step_off = v['step_off'][:self.L + 1]
         self.plan_subj_row, self.plan_s, self.plan_r = self._plan(1, S, c), self._plan(2, self.B, c), self._plan(3, self.B, c)
         # the few host-side values the model still needs (packing of the GRU launches, reporting)
         self.host = _Host(self, c)
+
+
+class GroupedDeviceBatch(DeviceBatch):
+    """The grouped batch of ONE direction (graph.build_batch(..., sort=True, group=...)) built on the device from a
+    GroupedBatchStore: B sequences, a member graph per (group, timestamp).  After finalize() it carries what a DeviceBatch
+    carries (it shares _accept and _own_part), without rel_label / ent_label; `host.perm` and `host.batch_sizes` are what
+    forward_grouped's callers read."""
+    _LABELS = ()
+
+    def __init__(self, store, seq_len, stream=None):
+        self.n_quads = self.B = B = int(store.n_quads)
+        if not 0 < B <= MAX_GROUPED or not 0 < int(seq_len) <= MAXL:
+            raise ValueError('a grouped device batch has 1 .. %d sequences of at most %d steps' % (MAX_GROUPED, MAXL))
+        if store.longest > int(seq_len):
+            raise ValueError('history longer than seq_len (%d > %d)' % (store.longest, int(seq_len)))
+        cn, ce = store.cap_nodes, store.cap_edges
+        cs = B * MAXL
+        T2 = 2 * store.num_rels
+        cc = ce // G.CHUNK + T2 + 2
+        own = dict(node_slot=cn, e_src2=ce, e_dst2=ce, chunk_ptr2=cc + 1, chunk_type2=cc, type_chunk_ptr2=T2 + 1,
+                   subj_row=cs, row_seq=cs, row_ent=cs, row_rel=cs, glob_row=cs, s_sorted=B, r_sorted=B, perm=B,
+                   step_off=MAXL + 1, plan_order1=cs, plan_seg1=cs + 1, plan_target1=cs,
+                   plan_order2=B, plan_seg2=B + 1, plan_target2=B, plan_order3=B, plan_seg3=B + 1, plan_target3=B)
+        # (idx = None: the sequences in the order of the store's arrays -- the store's upload is the only one)
+        _PendingBatch.__init__(self, _FRONT_GROUPED, store, None, (int(seq_len),), own, cn, ce, stream)
 
 
 # ---- full-graph batches of the global model (csrc/builder.hip: renet_build_full_graphs) -----------------------------------

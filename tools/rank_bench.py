@@ -6,6 +6,8 @@ GPU only.
 
     python tools/rank_bench.py tail [n] [C] [n_facts] [reps]        medians of `reps` alternating repetitions, JSON line
     python tools/rank_bench.py stream [shape] [n_timestamps] [reps]
+    python tools/rank_bench.py grouped [shape] [n_timestamps] [reps]   evaluate_filter_stream (device_rank on) with
+                                                                     RGCNAggregator.grouped_device_builder off and on
 """
 import json
 import os
@@ -119,9 +121,78 @@ def stream(shape='ICEWS18', n_t=3, reps=2):
                       'on_quadruples_per_s': n / float(np.median(times[True]))}))
 
 
+def grouped(shape='ICEWS18', n_t=3, reps=2):
+    """evaluate_filter_stream with the grouped batches from the host builder (off) and the device builder (on), device_rank
+    on in both: alternating repetitions after a warm-up of each, then ONE profiled pass per side that synchronises around
+    every forward_grouped stage -- builder (graph.build_batch + upload / GroupedDeviceBatch to finalize) and encoder (host
+    timer and device events) per call; `rest` is what remains of the pass (score GEMMs, ranks, the host loop)."""
+    import infer_bench
+    dev = torch.device('cuda:0')
+    times = {False: [], True: []}
+    ranks, split = {}, {}
+
+    def one(on, profile=False):
+        net, gnet, te, tes, teo, total = infer_bench.setup(shape, n_t, 200, dev)
+        net.device_rank = True
+        agg = net.aggregator
+        agg.grouped_device_builder = on
+        rec = {'build': [], 'encode': [], 'encode_dev': [], 'rows': []}
+        if profile:
+            build, build_dev, encode = agg.build, agg.build_grouped_device, agg.encode
+
+            def timed(fn, key):
+                def run(*a, **k):
+                    dt, out = _wall(lambda: fn(*a, **k))
+                    if out is not None or key != 'build_dev':
+                        rec['build'].append(dt)
+                    return out
+                return run
+
+            def enc(g, *a, **k):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                e0.record()
+                out = encode(g, *a, **k)
+                e1.record()
+                torch.cuda.synchronize()
+                rec['encode'].append(time.perf_counter() - t0)
+                rec['encode_dev'].append(e0.elapsed_time(e1) * 1e-3)
+                rec['rows'].append(int(g.S))
+                return out
+            agg.build, agg.build_grouped_device, agg.encode = timed(build, 'build'), timed(build_dev, 'build_dev'), enc
+        with torch.no_grad():
+            dt, (rk, _) = _wall(lambda: net.evaluate_filter_stream(te, tes, teo, gnet, total))
+        return dt, rk, rec
+
+    for rep_ in range(reps + 1):                                # repetition 0 warms up both sides
+        for on in (False, True):
+            dt, rk, _ = one(on)
+            if rep_:
+                times[on].append(dt)
+            ranks[on] = rk
+    for on in (False, True):
+        dt, _, rec = one(on, profile=True)
+        ms = lambda xs: round(float(np.median(xs)) * 1e3, 3) if xs else None
+        split[on] = {'groups': len(rec['encode']), 'pass_s': round(dt, 4), 'build_ms_median': ms(rec['build']),
+                     'build_ms_sum': round(sum(rec['build']) * 1e3, 2), 'encode_ms_median': ms(rec['encode']),
+                     'encode_device_ms_median': ms(rec['encode_dev']), 'encode_ms_sum': round(sum(rec['encode']) * 1e3, 2),
+                     'rest_ms_sum': round((dt - sum(rec['build']) - sum(rec['encode'])) * 1e3, 2),
+                     'steps_median': int(np.median(rec['rows'])) if rec['rows'] else 0}
+    n = len(ranks[True])
+    print(json.dumps({'shape': shape, 'timestamps': n_t, 'quadruples': n, 'reps': reps,
+                      'ranks_identical': bool(np.array_equal(ranks[False], ranks[True])),
+                      'off_s': [round(x, 4) for x in times[False]], 'on_s': [round(x, 4) for x in times[True]],
+                      'off_quadruples_per_s': n / float(np.median(times[False])),
+                      'on_quadruples_per_s': n / float(np.median(times[True])),
+                      'split_off': split[False], 'split_on': split[True]}))
+
+
 if __name__ == '__main__':
     a = sys.argv[1:]
-    if a and a[0] == 'stream':
+    if a and a[0] == 'grouped':
+        grouped(a[1] if len(a) > 1 else 'ICEWS18', int(a[2]) if len(a) > 2 else 3, int(a[3]) if len(a) > 3 else 2)
+    elif a and a[0] == 'stream':
         stream(a[1] if len(a) > 1 else 'ICEWS18', int(a[2]) if len(a) > 2 else 3, int(a[3]) if len(a) > 3 else 2)
     else:
         tail(*[int(x) for x in a[1:5]])
