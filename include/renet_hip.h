@@ -14,8 +14,9 @@
  *   - `stream` is a hipStream_t passed as void* (torch.cuda.current_stream().cuda_stream); every
  *     call only enqueues work on it and never synchronises;
  *   - fp32 row-major contiguous matrices, int32 indices;
- *   - D (n_hidden) must be 100, 200 or 400 (the reference hard-codes num_bases = 100, model.py:36,
- *     so the relation blocks are 1x1, 2x2, 4x4); other values return RENET_ERR_UNSUPPORTED;
+ *   - D (n_hidden) must be 100, 200, 300 or 400 (the reference hard-codes num_bases = 100, model.py:36,
+ *     so the relation blocks are 1x1, 2x2, 3x3, 4x4); other values return RENET_ERR_UNSUPPORTED, and so
+ *     do the bf16-storage entries (renet_rgcn_gather_items*_bf16, renet_gru_*_layouts_bf16*) at D = 300;
  *   - return value: 0 = ok, <0 = argument error (below), >0 = hipError_t from the launch.
  */
 #ifndef RENET_HIP_H

@@ -11,6 +11,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 import ops
+import renet_hip as K
 
 _RELU_FUNCS = (F.relu, torch.relu, torch.nn.functional.relu)
 
@@ -38,8 +39,10 @@ class RGCNBlockLayer(RGCNLayer):
     def __init__(self, in_feat, out_feat, num_rels, num_bases, bias=None, activation=None,
                  self_loop=False, dropout=0.0):
         super().__init__(in_feat, out_feat, bias, activation, self_loop=self_loop, dropout=dropout)
-        if in_feat != out_feat or num_bases != 100 or in_feat not in (100, 200, 400):
-            raise ValueError('kernels are built for num_bases=100 and n_hidden in {100, 200, 400}')
+        if in_feat != out_feat or num_bases != 100 or in_feat not in (100, 200, 300, 400):
+            raise ValueError('kernels are built for num_bases=100 and n_hidden in {100, 200, 300, 400}')
+        if in_feat == 300 and K.current_mode() == 'bf16s':
+            raise ValueError('bf16 storage mode has no n_hidden = 300 kernels (3x3 relation blocks are fp32 only)')
         self.num_rels = num_rels
         self.num_bases = num_bases
         self.out_feat = out_feat

@@ -47,7 +47,8 @@ static inline int renet_gemm_tile_order() {
     return v;
 }
 
-static inline bool renet_dim_ok(int D) { return D == 100 || D == 200 || D == 400; }
+// n_hidden the kernels are built for: relation blocks of 1x1, 2x2, 3x3, 4x4 (num_bases = 100)
+static inline bool renet_dim_ok(int D) { return D == 100 || D == 200 || D == 300 || D == 400; }
 
 // ---- counter-based dropout ------------------------------------------------------------------
 // One splitmix64 draw per group of 4 consecutive elements (every dropout site works on float4

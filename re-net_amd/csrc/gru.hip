@@ -146,7 +146,7 @@ int gru_fwd_impl(int npl, int n, const float* const* Gi, const int32_t* const* s
     const int e0 = make_layouts(n, step_off, L, out_rows, true, ly, B_of);
     if (e0 != RENET_OK) return e0;
     if (max_rows(ly) == 0) return RENET_OK;
-    if (H != 100 && H != 200 && H != 400) return RENET_ERR_UNSUPPORTED;
+    if (!renet_dim_ok(H) || (npl == 1 && H == 300)) return RENET_ERR_UNSUPPORTED;   // (no bf16 storage mode at 300)
     hipStream_t st = (hipStream_t)stream;
     if (npl == 0 || (use_f32() && npl == 3)) {
         FwdProbs ps;
@@ -190,7 +190,7 @@ int gru_bwd_impl(int npl, int n, const float* const* dh_last, const int32_t* con
     const int e0 = make_layouts(n, step_off, L, nullptr, false, ly, B_of);
     if (e0 != RENET_OK) return e0;
     if (max_rows(ly) == 0) return RENET_OK;
-    if (H != 100 && H != 200 && H != 400) return RENET_ERR_UNSUPPORTED;
+    if (!renet_dim_ok(H) || (npl == 1 && H == 300)) return RENET_ERR_UNSUPPORTED;   // (no bf16 storage mode at 300)
     hipStream_t st = (hipStream_t)stream;
     const bool f32 = npl == 0 || (use_f32() && npl == 3);
     const bool steps = npl == 3 && !f32 && !use_persistent();

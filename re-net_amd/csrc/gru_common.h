@@ -11,7 +11,7 @@
 // ---- the families' launchers (library-internal) ----------------------------------------------------------------------
 // The argument packs are kernel parameter types of the anonymous namespace, and a function whose signature names such a
 // type cannot be defined in another translation unit: packs, layouts and step states cross as const void* (read back
-// with as<T>).  H is 100, 200 or 400 (the front has answered RENET_ERR_UNSUPPORTED for anything else).
+// with as<T>).  H is 100, 200, 300 or 400 (the front has answered RENET_ERR_UNSUPPORTED for anything else).
 #define RENET_GRU_HIDDEN __attribute__((visibility("hidden")))
 // gru_f32.hip: the exact-fp32 recurrences (probs: FwdProbs / BwdProbs), and W_hh [rows, cols] -> W_hh^T
 RENET_GRU_HIDDEN int renet_gru_f32_fwd(int H, const void* probs, int np, const void* layouts, hipStream_t st);
@@ -138,12 +138,13 @@ __device__ __forceinline__ f32x4 mfma_p(const bf16x8 (&a)[NPL], const bf16x8 (&b
 // ---- host helpers of the launchers ------------------------------------------------------------------------------------
 template <class T>
 const T& as(const void* p) { return *static_cast<const T*>(p); }
-// the run-time H as a template argument: f(std::integral_constant<int, H>{}) for the three supported widths
+// the run-time H as a template argument: f(std::integral_constant<int, H>{}) for the supported widths
 template <class F>
 int with_h(int H, F&& f) {
     switch (H) {
         case 100: return f(std::integral_constant<int, 100>{});
         case 200: return f(std::integral_constant<int, 200>{});
+        case 300: return f(std::integral_constant<int, 300>{});
         case 400: return f(std::integral_constant<int, 400>{});
         default: return RENET_ERR_UNSUPPORTED;
     }

@@ -15,6 +15,49 @@ namespace {
 constexpr int kWaves = 4;           // waves per workgroup
 constexpr int kThreads = 64 * kWaves;
 
+// Floats of a feature row that one lane owns per chunk.  SI = 1, 2, 4: a float4 (the relation blocks tile it).  SI = 3
+// (D = 300): a 3x3 block does not tile a float4, so a lane owns exactly ONE block -- 3 features as a 12-byte load
+// (dwordx3), its 9 block entries as three more -- 100 lanes in two chunks, the same lane / chunk geometry as D = 400.
+// A chunk travels as a float4 whose .w is the constant 0 (no register).
+template <int SI> constexpr int vw_of() { return SI == 3 ? 3 : 4; }
+struct f32x3_mem { float x, y, z; };                    // 4-byte aligned: global_load / store_dwordx3
+
+template <int VW>
+__device__ __forceinline__ float4 ld_chunk(const float* base, size_t ch) {
+    if constexpr (VW == 4) return reinterpret_cast<const float4*>(base)[ch];
+    else {
+        const f32x3_mem v = reinterpret_cast<const f32x3_mem*>(base)[ch];
+        return make_float4(v.x, v.y, v.z, 0.f);
+    }
+}
+template <int VW>
+__device__ __forceinline__ void st_chunk(float* base, size_t ch, float4 o) {
+    if constexpr (VW == 4) reinterpret_cast<float4*>(base)[ch] = o;
+    else {
+        f32x3_mem v; v.x = o.x; v.y = o.y; v.z = o.z;
+        reinterpret_cast<f32x3_mem*>(base)[ch] = v;
+    }
+}
+// dropout multipliers of chunk ch of row `row`.  The mask is defined on the float4 groups of the [rows, D] tensor
+// (renet_drop4: group row * D/4 + f/4, element f % 4); a 3-float chunk straddles at most two of them.
+template <int VW, int D>
+__device__ __forceinline__ float4 drop_chunk(const DropCfg& d, uint64_t row, int ch) {
+    if constexpr (VW == 4) return renet_drop4(d, row * (D / 4) + ch);
+    else {
+        if (d.thresh == 0) return make_float4(1.f, 1.f, 1.f, 1.f);
+        const int f0 = 3 * ch, k0 = f0 & 3;
+        const uint64_t g0 = row * (D / 4) + (f0 >> 2);
+        const float4 a = renet_drop4(d, g0), b = renet_drop4(d, g0 + 1);       // (b unused when k0 <= 1)
+        const float m[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+        float4 r;
+        r.x = k0 == 0 ? m[0] : k0 == 1 ? m[1] : k0 == 2 ? m[2] : m[3];
+        r.y = k0 == 0 ? m[1] : k0 == 1 ? m[2] : k0 == 2 ? m[3] : m[4];
+        r.z = k0 == 0 ? m[2] : k0 == 1 ? m[3] : k0 == 2 ? m[4] : m[5];
+        r.w = 0.f;
+        return r;
+    }
+}
+
 template <int SI, bool TR>
 __device__ __forceinline__ void blockmul(const float4 x, const float4* __restrict__ w, float4& acc) {
     if constexpr (SI == 1) {
@@ -35,6 +78,17 @@ __device__ __forceinline__ void blockmul(const float4 x, const float4* __restric
             acc.y = fmaf(x.x, a.z, fmaf(x.y, a.w, acc.y));
             acc.z = fmaf(x.z, b.x, fmaf(x.w, b.y, acc.z));
             acc.w = fmaf(x.z, b.z, fmaf(x.w, b.w, acc.w));
+        }
+    } else if constexpr (SI == 3) {
+        const float4 r0 = w[0], r1 = w[1], r2 = w[2];              // rows i = 0..2 of the 3x3 block (xyz; w = 0)
+        if constexpr (!TR) {
+            acc.x = fmaf(x.x, r0.x, fmaf(x.y, r1.x, fmaf(x.z, r2.x, acc.x)));
+            acc.y = fmaf(x.x, r0.y, fmaf(x.y, r1.y, fmaf(x.z, r2.y, acc.y)));
+            acc.z = fmaf(x.x, r0.z, fmaf(x.y, r1.z, fmaf(x.z, r2.z, acc.z)));
+        } else {
+            acc.x = fmaf(x.x, r0.x, fmaf(x.y, r0.y, fmaf(x.z, r0.z, acc.x)));
+            acc.y = fmaf(x.x, r1.x, fmaf(x.y, r1.y, fmaf(x.z, r1.z, acc.y)));
+            acc.z = fmaf(x.x, r2.x, fmaf(x.y, r2.y, fmaf(x.z, r2.z, acc.z)));
         }
     } else {
         const float4 r0 = w[0], r1 = w[1], r2 = w[2], r3 = w[3];   // rows i = 0..3 of the 4x4 block
@@ -72,18 +126,20 @@ struct GatherArgs {
     DropCfg drop;
 };
 
-template <int CH>
+template <int SI>
 __device__ __forceinline__ void gather_epilogue(const GatherArgs& a, int v, int ch, float4 o, float sc) {
+    constexpr int VW = vw_of<SI>(), D = 100 * SI, CH = D / VW;
     o = f4_scale(o, sc);
     if (a.addend && v < a.addend_rows) {
-        float4 ad = reinterpret_cast<const float4*>(a.addend)[(size_t)v * CH + ch];
-        ad = f4_mul(ad, renet_drop4(a.drop, (uint64_t)v * CH + ch));
+        float4 ad = ld_chunk<VW>(a.addend, (size_t)v * CH + ch);
+        if constexpr (VW == 4) ad = f4_mul(ad, renet_drop4(a.drop, (uint64_t)v * CH + ch));
+        else ad = f4_mul(ad, drop_chunk<VW, D>(a.drop, (uint64_t)v, ch));
         o = f4_add(o, ad);
     }
     if (a.relu) {
         o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f);
     }
-    reinterpret_cast<float4*>(a.out)[(size_t)v * CH + ch] = o;
+    st_chunk<VW>(a.out, (size_t)v * CH + ch, o);
 }
 
 // SI = D/100 (relation block size); NCH = float4 chunks per lane = ceil(D/4/64); UNR = edges whose
@@ -105,8 +161,9 @@ __device__ __forceinline__ void gather_heavy_row(const GatherArgs& a, int v);
 template <int SI, int NCH, int UNR, bool TR>
 __global__ __launch_bounds__(kThreads) void rgcn_gather_kernel(GatherArgs a) {
     constexpr int D = 100 * SI;
-    constexpr int CH = D / 4;               // float4 chunks per feature row
-    constexpr int WCH = SI;                 // float4 weight loads per chunk
+    constexpr int VW = vw_of<SI>();         // floats per chunk
+    constexpr int CH = D / VW;              // chunks per feature row
+    constexpr int WCH = SI;                 // weight loads per chunk
     constexpr int WROW4 = D * SI / 4;       // float4 per relation weight row
     constexpr int R = 8;                    // rows per group
     const int lane = threadIdx.x & 63;
@@ -123,7 +180,7 @@ __global__ __launch_bounds__(kThreads) void rgcn_gather_kernel(GatherArgs a) {
     const int gpb = (ngroups + nb - 1) / nb;
     const int g0 = vb * gpb;
     const int g1 = min(ngroups, g0 + gpb);
-    const float4* __restrict__ x4 = reinterpret_cast<const float4*>(a.x);
+    const float4* __restrict__ x4 = reinterpret_cast<const float4*>(a.x);       // (the float4 widths read through these)
     const float4* __restrict__ w4 = reinterpret_cast<const float4*>(a.W);
 
     for (int grp = g0 + wave; grp < g1; grp += kWaves) {
@@ -147,7 +204,7 @@ __global__ __launch_bounds__(kThreads) void rgcn_gather_kernel(GatherArgs a) {
                 const float sc = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_sc), r));
 #pragma unroll
                 for (int c = 0; c < NCH; ++c)
-                    if (lane + 64 * c < CH) gather_epilogue<CH>(a, v0 + r, lane + 64 * c, acc[c], sc);
+                    if (lane + 64 * c < CH) gather_epilogue<SI>(a, v0 + r, lane + 64 * c, acc[c], sc);
             }
 #pragma unroll
             for (int c = 0; c < NCH; ++c) acc[c] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -181,15 +238,29 @@ __global__ __launch_bounds__(kThreads) void rgcn_gather_kernel(GatherArgs a) {
                 if (k0 + u < cnt && __builtin_amdgcn_readlane(my_col, k0 + u) < a.src_limit) {
                     const int src = __builtin_amdgcn_readlane(my_col, k0 + u);   // wave-uniform -> SGPR base
                     const int t = __builtin_amdgcn_readlane(my_t, k0 + u);
-                    const float4* xr = x4 + (size_t)src * CH;
-                    const float4* wr = w4 + (size_t)t * WROW4;
+                    if constexpr (VW == 4) {
+                        const float4* xr = x4 + (size_t)src * CH;
+                        const float4* wr = w4 + (size_t)t * WROW4;
 #pragma unroll
-                    for (int c = 0; c < NCH; ++c) {
-                        const int ch = lane + 64 * c;
-                        if (ch < CH) {
-                            xv[u][c] = xr[ch];
+                        for (int c = 0; c < NCH; ++c) {
+                            const int ch = lane + 64 * c;
+                            if (ch < CH) {
+                                xv[u][c] = xr[ch];
 #pragma unroll
-                            for (int q = 0; q < WCH; ++q) wv[u][c][q] = wr[ch * WCH + q];
+                                for (int q = 0; q < WCH; ++q) wv[u][c][q] = wr[ch * WCH + q];
+                            }
+                        }
+                    } else {
+                        const float* xr = a.x + (size_t)src * D;
+                        const float* wr = a.W + (size_t)t * (D * SI);
+#pragma unroll
+                        for (int c = 0; c < NCH; ++c) {
+                            const int ch = lane + 64 * c;
+                            if (ch < CH) {
+                                xv[u][c] = ld_chunk<VW>(xr, ch);
+#pragma unroll
+                                for (int q = 0; q < WCH; ++q) wv[u][c][q] = ld_chunk<VW>(wr, ch * WCH + q);
+                            }
                         }
                     }
                 }
@@ -219,7 +290,8 @@ __global__ __launch_bounds__(kThreads) void rgcn_gather_kernel(GatherArgs a) {
 template <int SI, int NCH, int UNR, bool TR>
 __device__ __forceinline__ void gather_heavy_row(const GatherArgs& a, int v) {
     constexpr int D = 100 * SI;
-    constexpr int CH = D / 4;
+    constexpr int VW = vw_of<SI>();
+    constexpr int CH = D / VW;
     constexpr int WCH = SI;
     constexpr int WROW4 = D * SI / 4;
     __shared__ float4 red[kWaves][CH];
@@ -244,9 +316,16 @@ __device__ __forceinline__ void gather_heavy_row(const GatherArgs& a, int v) {
                 for (int c = 0; c < NCH; ++c) {
                     const int ch = lane + 64 * c;
                     if (ch < CH) {
-                        xv[u][c] = x4[(size_t)src * CH + ch];
+                        if constexpr (VW == 4) {
+                            xv[u][c] = x4[(size_t)src * CH + ch];
 #pragma unroll
-                        for (int q = 0; q < WCH; ++q) wv[u][c][q] = w4[(size_t)t * WROW4 + ch * WCH + q];
+                            for (int q = 0; q < WCH; ++q) wv[u][c][q] = w4[(size_t)t * WROW4 + ch * WCH + q];
+                        } else {
+                            xv[u][c] = ld_chunk<VW>(a.x, (size_t)src * CH + ch);
+#pragma unroll
+                            for (int q = 0; q < WCH; ++q)
+                                wv[u][c][q] = ld_chunk<VW>(a.W, (size_t)t * (CH * WCH) + ch * WCH + q);
+                        }
                     }
                 }
             }
@@ -273,7 +352,7 @@ __device__ __forceinline__ void gather_heavy_row(const GatherArgs& a, int v) {
                 float4 s = red[0][ch];
 #pragma unroll
                 for (int w = 1; w < kWaves; ++w) s = f4_add(s, red[w][ch]);
-                gather_epilogue<CH>(a, v, ch, s, sc);
+                gather_epilogue<SI>(a, v, ch, s, sc);
             }
         }
     }
@@ -352,6 +431,26 @@ __device__ __forceinline__ void buf_store4(__amdgpu_buffer_rsrc_t r, uint32_t vo
     __builtin_amdgcn_raw_buffer_store_b128(v, r, (int)voff, 0, 0);
 }
 
+// chunk-width (VW floats) forms of the loads / the store: 16-byte, or 12-byte (dwordx3) with .w = 0
+typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
+template <int VW>
+__device__ __forceinline__ float4 buf_loadvs(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff) {
+    if constexpr (VW == 4) return buf_load4s(r, voff, soff);
+    else {
+        const u32x3 v = __builtin_amdgcn_raw_buffer_load_b96(r, (int)voff, (int)soff, 0);
+        return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), 0.f);
+    }
+}
+template <int VW>
+__device__ __forceinline__ void buf_storev(__amdgpu_buffer_rsrc_t r, uint32_t voff, float4 o) {
+    if constexpr (VW == 4) buf_store4(r, voff, o);
+    else {
+        u32x3 v;
+        v.x = __float_as_uint(o.x); v.y = __float_as_uint(o.y); v.z = __float_as_uint(o.z);
+        __builtin_amdgcn_raw_buffer_store_b96(v, r, (int)voff, 0, 0);
+    }
+}
+
 // bf16 STORAGE of the gather operands (BASELINE config 5; MX = 1: relation blocks bf16, MX = 2: source rows too):
 // 8-byte loads of 4 bf16 per lane instead of 16-byte loads of 4 floats, widened to fp32 in registers (exact), fp32
 // accumulation and fp32 addend / output as before.  At D = 400 the 6.4 KB relation block per edge is the stream that
@@ -363,12 +462,14 @@ __device__ __forceinline__ float4 buf_load4s_bf16(__amdgpu_buffer_rsrc_t r, uint
     const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(r, (int)voff, (int)soff, 0);
     return make_float4(bf_lo(v.x), bf_hi(v.x), bf_lo(v.y), bf_hi(v.y));
 }
-// the WCH float4 of one lane's relation-block slice: fp32 (16 WCH bytes at wo) or bf16 (8 WCH bytes at wo)
+// the WCH float4 of one lane's relation-block slice: fp32 (16 WCH bytes at wo; 12 WCH at SI = 3) or bf16 (8 WCH bytes at wo)
 template <int WCH, bool B16>
 __device__ __forceinline__ void load_wblock(__amdgpu_buffer_rsrc_t rw, uint32_t wo, uint32_t ws, float4 (&w)[WCH]) {
+    static_assert(!(B16 && WCH == 3), "no bf16 storage of 3x3 relation blocks");
     if constexpr (!B16) {
+        constexpr int VW = vw_of<WCH>();
 #pragma unroll
-        for (int q = 0; q < WCH; ++q) w[q] = buf_load4s(rw, wo + 16u * q, ws);
+        for (int q = 0; q < WCH; ++q) w[q] = buf_loadvs<VW>(rw, wo + (4u * VW) * q, ws);
     } else if constexpr (WCH == 1) {
         w[0] = buf_load4s_bf16(rw, wo, ws);
     } else {
@@ -390,17 +491,17 @@ constexpr int kItemFlushMap = -3;
 template <int SI, int NCH, bool TR>
 __device__ __forceinline__ void row_epilogue(const GatherArgs& g, int row, bool has_ad, float sc, int lane,
                                              const float4 (&acc)[NCH], const float4 (&ad)[NCH]) {
-    constexpr int CH = 100 * SI / 4;
-    const __amdgpu_buffer_rsrc_t ro = make_rsrc(g.out + (size_t)row * (CH * 4), CH * 16);
+    constexpr int D = 100 * SI, VW = vw_of<SI>();
+    const __amdgpu_buffer_rsrc_t ro = make_rsrc(g.out + (size_t)row * D, D * 4);
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
         const int ch = lane + 64 * c;
         float4 o = f4_scale(acc[c], sc);
-        if (has_ad) o = f4_add(o, f4_mul(ad[c], renet_drop4(g.drop, (uint64_t)row * CH + ch)));
+        if (has_ad) o = f4_add(o, f4_mul(ad[c], drop_chunk<VW, D>(g.drop, (uint64_t)row, ch)));
         if (g.relu) {
             o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f);
         }
-        buf_store4(ro, (uint32_t)ch * 16u, o);               // lanes past the row: out of range => dropped
+        buf_storev<VW>(ro, (uint32_t)ch * (4u * VW), o);     // lanes past the row: out of range => dropped
     }
 }
 
@@ -413,7 +514,9 @@ template <int SI, int NCH, int UNR, bool TR, int MX, bool COMPACT = false>
 __device__ __forceinline__ void gather_item_group(const ItemArgs& a, int grp) {
     constexpr bool XB = MX == 2, WB = MX >= 1;
     constexpr int D = 100 * SI;
-    constexpr int CH = D / 4;
+    constexpr int VW = vw_of<SI>();
+    constexpr uint32_t CB = 4u * VW;                     // bytes of one fp32 chunk
+    constexpr int CH = D / VW;
     constexpr int WCH = SI;
     constexpr uint32_t ROWB = D * 4;                     // bytes of one fp32 feature row (addend, output)
     const uint32_t XROWB = a.g.x_rowb;                   // bytes of one row of x (fp32: ROWB; bf16: 2 * its row stride)
@@ -437,9 +540,9 @@ __device__ __forceinline__ void gather_item_group(const ItemArgs& a, int grp) {
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
         const uint32_t ch = (uint32_t)(lane + 64 * c);
-        xoff[c] = ch < (uint32_t)CH ? ch * (XB ? 8u : 16u) : kOob;
-        aoff[c] = ch < (uint32_t)CH ? ch * 16u : kOob;                 // the addend is always fp32
-        woff[c] = ch < (uint32_t)CH ? ch * ((WB ? 8u : 16u) * WCH) : kOob;
+        xoff[c] = ch < (uint32_t)CH ? ch * (XB ? 8u : CB) : kOob;
+        aoff[c] = ch < (uint32_t)CH ? ch * CB : kOob;                  // the addend is always fp32
+        woff[c] = ch < (uint32_t)CH ? ch * ((WB ? 8u : CB) * WCH) : kOob;
     }
     float4 acc[NCH];
 #pragma unroll
@@ -486,7 +589,7 @@ __device__ __forceinline__ void gather_item_group(const ItemArgs& a, int grp) {
                 const uint32_t wo = edge ? woff[c] : kOob;
                 if constexpr (!XB) {
                     const uint32_t xo = (edge || flush_ad) ? xoff[c] : kOob;
-                    xv[u][c] = flush_ad ? buf_load4s(rad, xo, xs) : buf_load4s(rx, xo, xs);
+                    xv[u][c] = flush_ad ? buf_loadvs<VW>(rad, xo, xs) : buf_loadvs<VW>(rx, xo, xs);
                 } else {
                     // bf16 source rows and fp32 addend rows differ in load width: two unconditional loads, the one that
                     // does not apply gets the out-of-range offset (no memory access); exactly one of them is non-zero
@@ -522,7 +625,9 @@ template <int SI, int NCH, int UNR, bool TR, int WAVES, int MX, bool COMPACT = f
 __device__ __forceinline__ void gather_hub_row(const GatherArgs& a, int v) {
     constexpr bool XB = MX == 2, WB = MX >= 1;
     constexpr int D = 100 * SI;
-    constexpr int CH = D / 4;
+    constexpr int VW = vw_of<SI>();
+    constexpr uint32_t CB = 4u * VW;
+    constexpr int CH = D / VW;
     constexpr int WCH = SI;
     constexpr uint32_t ROWB = D * 4;
     const uint32_t XROWB = a.x_rowb, WROWB = a.w_rowb;
@@ -541,10 +646,10 @@ __device__ __forceinline__ void gather_hub_row(const GatherArgs& a, int v) {
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
         const uint32_t ch = (uint32_t)(lane + 64 * c);
-        xoff[c] = ch < (uint32_t)CH ? ch * (XB ? 8u : 16u) : kOob;
-        woff[c] = ch < (uint32_t)CH ? ch * ((WB ? 8u : 16u) * WCH) : kOob;
+        xoff[c] = ch < (uint32_t)CH ? ch * (XB ? 8u : CB) : kOob;
+        woff[c] = ch < (uint32_t)CH ? ch * ((WB ? 8u : CB) * WCH) : kOob;
         acc[c] = make_float4(0.f, 0.f, 0.f, 0.f);
-        adv[c] = buf_load4s(rad, (has_ad && wave == 0 && ch < (uint32_t)CH) ? ch * 16u : kOob,
+        adv[c] = buf_loadvs<VW>(rad, (has_ad && wave == 0 && ch < (uint32_t)CH) ? ch * CB : kOob,
                             has_ad ? (uint32_t)adrow * ROWB : 0u);
     }
     for (int base = e0; base < e1; base += 64) {
@@ -585,7 +690,7 @@ __device__ __forceinline__ void gather_hub_row(const GatherArgs& a, int v) {
 #pragma unroll
                 for (int c = 0; c < NCH; ++c) {
                     if constexpr (XB) xv[u][c] = buf_load4s_bf16(rx, ok ? xoff[c] : kOob, xs);
-                    else xv[u][c] = buf_load4s(rx, ok ? xoff[c] : kOob, xs);
+                    else xv[u][c] = buf_loadvs<VW>(rx, ok ? xoff[c] : kOob, xs);
                     load_wblock<WCH, WB>(rw, ok ? woff[c] : kOob, ws, wv[u][c]);
                 }
             }
@@ -653,7 +758,8 @@ int launch_gather_items(const ItemArgs& a, bool tr, bool pruned, hipStream_t st)
     return RENET_OK;
 }
 
-// edges in flight per wave (tuning knob, read once): RENET_GATHER_UNR in {2, 3, 4, 6, 8}; 0 / unset = default
+// edges in flight per wave (tuning knob, read once): RENET_GATHER_UNR in {2, 3, 4, 6, 8}; 0 / unset, or a value the
+// width has no instantiation for (gather_items_impl: 6 and 8 exist at D = 100 / 200 only) = that width's default
 int gather_unr() {
     static const int v = renet_env_int("RENET_GATHER_UNR", 0, 0, 8);
     return v;
@@ -715,6 +821,9 @@ __global__ __launch_bounds__(256) void rgcn_bwd_prep_kernel(const float4* __rest
 // chunk -- the group's first chunk or the first chunk of a type -- and the reduce kernel below reads only those slots
 // (the hottest relation of a Zipf batch owns > 1000 chunks: 8x fewer dependent rounds on its critical path).
 // BIG: x / gmat of 2 GiB and more (renet_rgcn_bwd_w64) -- 64-bit global addressing instead of the 32-bit buffer offsets.
+// SI = 3: lane = one 3x3 block (3-float chunks of x and gmat, see vw_of): 9 products per edge, kept as three xyz rows;
+// the block's 9 entries are consecutive floats of the relation row, which is 225 float4 -- LDS and the partial rows are
+// written per float; the 64 lanes of a run's first wave then add the run's rows and store them, one float4 each.
 constexpr int kBwdWGroup = 8;
 template <int SI, int NCH, bool BIG = false>
 __global__ __launch_bounds__(kBwdWGroup * 64) void rgcn_bwd_w_partial_kernel(
@@ -722,10 +831,11 @@ __global__ __launch_bounds__(kBwdWGroup * 64) void rgcn_bwd_w_partial_kernel(
     const int32_t* __restrict__ e_dst, const int32_t* __restrict__ chunk_ptr, const int32_t* __restrict__ chunk_type,
     int n_chunks, float4* __restrict__ partial) {
     constexpr int D = 100 * SI;
-    constexpr int CH = D / 4;
+    constexpr int VW = vw_of<SI>();
+    constexpr int CH = D / VW;
     constexpr int WROW4 = D * SI / 4;
     constexpr uint32_t ROWB = D * 4;
-    constexpr int UNR = (SI == 4) ? 2 : 8;              // edges with both row loads in flight together
+    constexpr int UNR = (SI == 4) ? 2 : (SI == 3) ? 4 : 8;   // edges with both row loads in flight together
     __shared__ float4 red[kBwdWGroup][WROW4];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -736,7 +846,7 @@ __global__ __launch_bounds__(kBwdWGroup * 64) void rgcn_bwd_w_partial_kernel(
     const __amdgpu_buffer_rsrc_t rg = make_rsrc(gmat, kBufSpan);
     uint32_t off[NCH];
 #pragma unroll
-    for (int q = 0; q < NCH; ++q) off[q] = (uint32_t)(lane + 64 * q) < (uint32_t)CH ? (uint32_t)(lane + 64 * q) * 16u : kOob;
+    for (int q = 0; q < NCH; ++q) off[q] = (uint32_t)(lane + 64 * q) < (uint32_t)CH ? (uint32_t)(lane + 64 * q) * (4u * VW) : kOob;
     float4 acc[NCH][SI];
 #pragma unroll
     for (int q = 0; q < NCH; ++q)
@@ -765,11 +875,16 @@ __global__ __launch_bounds__(kBwdWGroup * 64) void rgcn_bwd_w_partial_kernel(
                         const size_t sr = (size_t)__builtin_amdgcn_readlane(my_s, kk) * CH + ch;
                         const size_t dr = (size_t)__builtin_amdgcn_readlane(my_d, kk) * CH + ch;
                         const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-                        xv[u][q] = on ? reinterpret_cast<const float4*>(x)[sr] : z;
-                        gv[u][q] = on ? reinterpret_cast<const float4*>(gmat)[dr] : z;
+                        if constexpr (VW == 4) {
+                            xv[u][q] = on ? reinterpret_cast<const float4*>(x)[sr] : z;
+                            gv[u][q] = on ? reinterpret_cast<const float4*>(gmat)[dr] : z;
+                        } else {
+                            xv[u][q] = on ? ld_chunk<VW>(x, sr) : z;
+                            gv[u][q] = on ? ld_chunk<VW>(gmat, dr) : z;
+                        }
                     } else {
-                        xv[u][q] = buf_load4s(rx, ok ? off[q] : kOob, so);
-                        gv[u][q] = buf_load4s(rg, ok ? off[q] : kOob, dof);
+                        xv[u][q] = buf_loadvs<VW>(rx, ok ? off[q] : kOob, so);
+                        gv[u][q] = buf_loadvs<VW>(rg, ok ? off[q] : kOob, dof);
                     }
                 }
             }
@@ -792,6 +907,15 @@ __global__ __launch_bounds__(kBwdWGroup * 64) void rgcn_bwd_w_partial_kernel(
                         acc[q][1].y = fmaf(xv[u][q].z, gv[u][q].w, acc[q][1].y);
                         acc[q][1].z = fmaf(xv[u][q].w, gv[u][q].z, acc[q][1].z);
                         acc[q][1].w = fmaf(xv[u][q].w, gv[u][q].w, acc[q][1].w);
+                    } else if constexpr (SI == 3) {
+                        // dW[i][j] = x_i g_j of this lane's block: acc[q][i] = row i (xyz)
+                        const float xs[3] = {xv[u][q].x, xv[u][q].y, xv[u][q].z};
+#pragma unroll
+                        for (int i = 0; i < 3; ++i) {
+                            acc[q][i].x = fmaf(xs[i], gv[u][q].x, acc[q][i].x);
+                            acc[q][i].y = fmaf(xs[i], gv[u][q].y, acc[q][i].y);
+                            acc[q][i].z = fmaf(xs[i], gv[u][q].z, acc[q][i].z);
+                        }
                     } else {
                         const float xs[4] = {xv[u][q].x, xv[u][q].y, xv[u][q].z, xv[u][q].w};
 #pragma unroll
@@ -810,8 +934,14 @@ __global__ __launch_bounds__(kBwdWGroup * 64) void rgcn_bwd_w_partial_kernel(
     for (int q = 0; q < NCH; ++q) {
         const int ch = lane + 64 * q;
         if (ch < CH) {
+            if constexpr (SI == 3) {
+                float* rf = reinterpret_cast<float*>(red[wave]) + ch * 9;    // (stride 9 floats: conflict-free)
 #pragma unroll
-            for (int i = 0; i < SI; ++i) red[wave][ch * SI + i] = acc[q][i];
+                for (int i = 0; i < 3; ++i) { rf[3 * i] = acc[q][i].x; rf[3 * i + 1] = acc[q][i].y; rf[3 * i + 2] = acc[q][i].z; }
+            } else {
+#pragma unroll
+                for (int i = 0; i < SI; ++i) red[wave][ch * SI + i] = acc[q][i];
+            }
         }
     }
     __syncthreads();
@@ -820,6 +950,14 @@ __global__ __launch_bounds__(kBwdWGroup * 64) void rgcn_bwd_w_partial_kernel(
     if (wave != 0 && chunk_type[c - 1] == ty) return;         // not the first chunk of its run
     int run = 1;                                              // chunks of this run inside the group
     while (wave + run < kBwdWGroup && c + run < n_chunks && chunk_type[c + run] == ty) ++run;
+    if constexpr (SI == 3) {
+        for (int k = lane; k < WROW4; k += 64) {
+            float4 r = red[wave][k];
+            for (int w = 1; w < run; ++w) r = f4_add(r, red[wave + w][k]);
+            partial[(size_t)c * WROW4 + k] = r;
+        }
+        return;
+    }
 #pragma unroll
     for (int q = 0; q < NCH; ++q) {
         const int ch = lane + 64 * q;
@@ -1066,6 +1204,7 @@ int renet_rgcn_gather(const float* x, int D, const int32_t* row_ptr, const int32
     switch (D) {
         case 100: return launch_gather<1, 1, 4>(a, transpose_w != 0, st);
         case 200: return launch_gather<2, 1, 4>(a, transpose_w != 0, st);
+        case 300: return launch_gather<3, 2, 2>(a, transpose_w != 0, st);
         default: return launch_gather<4, 2, 2>(a, transpose_w != 0, st);
     }
 }
@@ -1100,6 +1239,7 @@ static int gather_items_impl(int mx, int x_ld, int w_ld, const float* x, int x_r
     a.g.x_rowb = mx == 2 ? (uint32_t)x_ld * 2u : (uint32_t)D * 4u;
     a.g.w_rowb = mx >= 1 ? (uint32_t)w_ld * 2u : (uint32_t)D * (D / 100) * 4u;
     if (mx < 0 || mx > 2 || (mx >= 1 && w_ld < D * (D / 100)) || (mx == 2 && x_ld < D)) return RENET_ERR_BADARG;
+    if (mx != 0 && D == 300) return RENET_ERR_UNSUPPORTED;      // no bf16 storage of 3x3 blocks (the arms below: 400)
     if (mx == 1) {
         switch (D) {
             case 100: return launch_gather_items<1, 1, 6, 1>(a, tr, pr, st);
@@ -1126,6 +1266,10 @@ static int gather_items_impl(int mx, int x_ld, int w_ld, const float* x, int x_r
             if (unr == 6) return launch_gather_items<2, 1, 6>(a, tr, pr, st);
             if (unr == 8) return launch_gather_items<2, 1, 8>(a, tr, pr, st);
             return launch_gather_items<2, 1, 3>(a, tr, pr, st);      // 60 VGPRs: 8 waves per SIMD
+        case 300:                                                    // 100 lanes x one 3x3 block (vw_of)
+            if (unr == 3) return launch_gather_items<3, 2, 3>(a, tr, pr, st);
+            if (unr == 4) return launch_gather_items<3, 2, 4>(a, tr, pr, st);
+            return launch_gather_items<3, 2, 2>(a, tr, pr, st);      // 87-91 VGPRs: 5 waves per SIMD
         default:
             if (unr == 3) return launch_gather_items<4, 2, 3>(a, tr, pr, st);
             if (unr == 4) return launch_gather_items<4, 2, 4>(a, tr, pr, st);
@@ -1242,6 +1386,12 @@ static int bwd_w_impl(bool big, const float* x, const float* gn, const int32_t* 
                 if (big) RENET_LAUNCH((rgcn_bwd_w_partial_kernel<1, 1, true>), grid, dim3(kBwdWGroup * 64), 0, st, x4, g4,
                                             e_src, e_dst, chunk_ptr, chunk_type, n_chunks, p4);
                 else RENET_LAUNCH((rgcn_bwd_w_partial_kernel<1, 1>), grid, dim3(kBwdWGroup * 64), 0, st, x4, g4,
+                                   e_src, e_dst, chunk_ptr, chunk_type, n_chunks, p4);
+                break;
+            case 300:
+                if (big) RENET_LAUNCH((rgcn_bwd_w_partial_kernel<3, 2, true>), grid, dim3(kBwdWGroup * 64), 0, st, x4, g4,
+                                            e_src, e_dst, chunk_ptr, chunk_type, n_chunks, p4);
+                else RENET_LAUNCH((rgcn_bwd_w_partial_kernel<3, 2>), grid, dim3(kBwdWGroup * 64), 0, st, x4, g4,
                                    e_src, e_dst, chunk_ptr, chunk_type, n_chunks, p4);
                 break;
             case 200:

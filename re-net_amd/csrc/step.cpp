@@ -165,7 +165,7 @@ Lay layout(const RenetStepModel& m, const RenetStepBatch& b) {
 
 bool args_ok(const RenetStepModel* m, const RenetStepBatch* b) {
     if (!m || !b) return false;
-    if (!(m->D == 100 || m->D == 200 || m->D == 400) || m->num_ent < 1 || m->T < 2 || m->C2 < 1) return false;
+    if (!(m->D == 100 || m->D == 200 || m->D == 300 || m->D == 400) || m->num_ent < 1 || m->T < 2 || m->C2 < 1) return false;
     if (b->N < 1 || b->nA < 1 || b->nA > b->N || b->S < 1 || b->B < 1 || b->L < 1 || !b->step_off_host) return false;
     // 32-bit buffer offsets of the item kernels / table layer (the Python path falls back to other kernels beyond this)
     const size_t big = (size_t)std::max(b->N, m->num_ent) * m->D * 4;
