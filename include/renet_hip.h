@@ -483,6 +483,42 @@ int renet_segment_pool_bwd(const float* dout, const int32_t* seg_ptr, const int3
                            int D, int is_max, int N, float* dh, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Neighbour pooling of the mean / attentive history encoders (Aggregator.py:239-361: MeanAggregator, AttnAggregator;
+ * replaces the sparse.mm + division of :264-267, the per-sequence loops of :276-278 / :322-340 and
+ * pack_padded_sequence).  A SEGMENT is the neighbour list of one time step of one sequence:
+ *   nbr[seg_ptr[u] .. seg_ptr[u + 1])  entity ids (rows of E [N_ent, D]); repeats allowed, never empty
+ *   seg_s[u], seg_r[u]                 the sequence's subject entity / relation (row of R [N_rel, D])
+ *   seg_q[u]                           the sequence's row in q
+ *   out_row[u]                         the segment's row in the packed (time-major) output
+ * attn == 0:  out[out_row[u]] = [ mean_j E[nbr_j] | E[s] ]                                    (row stride 2D)
+ * attn != 0:  a_j = v . tanh(P[nbr_j] + q[seg_q[u]]),  w = softmax_j(a)                         (Aggregator.py:333-337)
+ *             out[out_row[u]] = [ sum_j w_j E[nbr_j] | E[s] | R[r] ]                          (row stride 3D)
+ *             with P [N_ent, D] = E W_o^T and q = W_s E[s] + W_r R[r] + b computed by the caller (renet_gemm_*);
+ *             stats[u] = (max_j a_j, log sum_j exp(a_j - max)), w[k] = the softmax weight of neighbour k.
+ * seg_ptr is read on the device; seg_ptr_host is the same array in HOST memory, checked here: a segment of length 0
+ * returns RENET_ERR_BADARG.  One wave per segment, an online softmax (running maximum, rescaled only when it moves);
+ * segments longer than 256 neighbours are split over the waves of a workgroup and merged in wave order.  No atomics:
+ * the result is a function of the inputs alone.
+ * Backward (dOut: the gradient of the packed rows, out: the forward result), per neighbour k of segment u, with
+ * g = dOut[out_row[u], 0:D]:
+ *   attn == 0:  cE[k] = g / n_u
+ *   attn != 0:  da = w_k (g . E[nbr_k] - g . out[out_row[u], 0:D]),  t = tanh(P[nbr_k] + q)
+ *               cE[k] = w_k g,  cP[k] = da v (1 - t^2),  dq_rows[u] = sum_k cP[k],  dv_rows[u] = sum_k da t
+ *   ds_rows[u] / dr_rows[u] = the E[s] / R[r] column blocks of dOut[out_row[u]] (dr_rows: attn only).
+ * The caller sums cE / cP per destination entity (renet_segment_add2 over a plan of nbr), dq_rows / ds_rows / dr_rows
+ * per sequence (renet_segment_add) and dv_rows over all segments (renet_colsum); arguments a mode does not use may be
+ * NULL.  fp32 only; every float pointer 16-byte aligned. */
+int renet_nbr_pool_fwd(const float* E, const float* R, const float* P, const float* q, const float* v,
+                       const int32_t* nbr, const int32_t* seg_ptr, const int32_t* seg_ptr_host, const int32_t* seg_s,
+                       const int32_t* seg_r, const int32_t* seg_q, const int32_t* out_row, int S, int D, int attn,
+                       float* out, float* stats, float* w, void* stream);
+int renet_nbr_pool_bwd(const float* dOut, const float* out, const float* E, const float* P, const float* q,
+                       const float* v, const float* w, const int32_t* nbr, const int32_t* seg_ptr,
+                       const int32_t* seg_ptr_host, const int32_t* seg_q, const int32_t* out_row, int S, int D, int attn,
+                       float* cE, float* cP, float* dq_rows, float* dv_rows, float* ds_rows, float* dr_rows,
+                       void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Fused clip_grad_norm_ + Adam (+ weight decay) + zero_grad over flat buffers (train.py:140-142).
  * p, g, m, v: n floats each (16-byte aligned); `step` is the 1-based step count (bias correction);
  * max_norm <= 0 disables clipping; grad_norm_out (optional device float) receives the pre-clip norm.

@@ -1,7 +1,8 @@
 """Neighbourhood aggregators with the reference's class names and call signatures
 (reference Aggregator.py:9-237), rebuilt on the DGL-free batch builder (graph.py) and the HIP
-kernels.  Mean/Attn aggregators of the reference are dead code there (model.py:36 always builds
-RGCNAggregator) and are not provided.
+kernels.  MeanAggregator / AttnAggregator (Aggregator.py:239-361; the paper's ablation encoders -- model.py:36 always
+builds RGCNAggregator, and so does RENet here) need no graph: their neighbour id lists go through graph.NeighbourBatch
+and the fused pooling kernels (csrc/nbr_pool.hip).
 
 What differs from the reference internally (results are the same):
   * the batch graph is built by a few vectorised numpy passes instead of ~T_b DGL subgraph calls;
@@ -278,3 +279,82 @@ class RGCNAggregator_global(nn.Module):
             pos += 1
         win = times[max(0, pos - self.seq_len):pos]
         return self.pooled(win, ent_embeds, graph_dict, reverse)
+
+
+class _NeighbourAggregator(nn.Module):
+    """What MeanAggregator and AttnAggregator share: the host batch of the neighbour id lists, the packed result with
+    its dropout (Aggregator.py:281 / 342: the reference drops on the padded tensor before packing -- elementwise the same
+    distribution), and predict() as a one-sequence batch."""
+
+    def __init__(self, h_dim, dropout, seq_len):
+        super().__init__()
+        self.h_dim = h_dim
+        self.drop_p = float(dropout or 0.0)
+        self.dropout = nn.Dropout(dropout)       # kept for attribute compatibility; the mask is ops.DropoutFn's
+        self.seq_len = seq_len
+        self.last_batch = None
+
+    def build(self, s_hist, s, r, ent_embeds, seq_len):
+        """-> graph.DeviceNeighbourBatch, or None when every history is empty."""
+        hb = G.NeighbourBatch(_host_ints(s), _host_ints(r), s_hist, seq_len=seq_len)
+        return hb.to(ent_embeds.device) if hb.nseq else None
+
+    def pooled(self, nb, ent_embeds, rel_embeds):
+        raise NotImplementedError
+
+    def forward(self, s_hist, s, r, ent_embeds, rel_embeds):
+        """-> PackedSequence of the length-sorted non-empty sequences (`last_batch.host.perm` is the order), or None when
+        every history is empty."""
+        nb = self.last_batch = self.build(s_hist, s, r, ent_embeds, self.seq_len)
+        if nb is None:
+            return None
+        x = self.pooled(nb, ent_embeds, rel_embeds)
+        if self.training and self.drop_p > 0:
+            x = ops.DropoutFn.apply(x, self.drop_p, ops.next_seed())
+        return PackedSequence(x, torch.from_numpy(nb.host.batch_sizes.astype(np.int64)))
+
+    def predict(self, s_history, s, r, ent_embeds, rel_embeds):
+        """One sequence: s_history = list of 1-D id arrays -> one row per time step (no dropout, no length limit)."""
+        if len(s_history) == 0:
+            return self._empty(ent_embeds)
+        nb = self.build([list(s_history)], _host_ints(s)[:1], _host_ints(r)[:1], ent_embeds, None)
+        return self.pooled(nb, ent_embeds, rel_embeds)
+
+
+class MeanAggregator(_NeighbourAggregator):
+    """Aggregator.py:239-297: packed rows [ mean_j ent[nbr_j] | ent[s] ] (gcn=True: relu(gcn_layer(mean)) first)."""
+
+    def __init__(self, h_dim, dropout, seq_len=10, gcn=False):
+        super().__init__(h_dim, dropout, seq_len)
+        self.gcn = gcn
+        if gcn:
+            self.gcn_layer = nn.Linear(h_dim, h_dim)
+
+    def _empty(self, ent_embeds):
+        return ent_embeds.new_zeros(0, 2 * self.h_dim)
+
+    def pooled(self, nb, ent_embeds, rel_embeds):
+        x = ops.NbrPoolFn.apply(ent_embeds, None, None, None, None, nb)
+        if self.gcn:                                                              # Aggregator.py:269-271
+            h = self.h_dim
+            m = F.relu(ops.LinearFn.apply(x[:, :h], self.gcn_layer.weight, self.gcn_layer.bias))
+            x = torch.cat((m, x[:, h:]), dim=1)
+        return x
+
+
+class AttnAggregator(_NeighbourAggregator):
+    """Aggregator.py:306-361: packed rows [ sum_j w_j ent[nbr_j] | ent[s] | rel[r] ] with
+    w = softmax_j( tanh(attn_s([ent[nbr_j] | ent[s] | rel[r]])) @ v_s )."""
+
+    def __init__(self, h_dim, dropout, seq_len=10):
+        super().__init__(h_dim, dropout, seq_len)
+        self.attn_s = nn.Linear(3 * h_dim, h_dim)
+        self.v_s = nn.Parameter(torch.Tensor(h_dim, 1))
+        nn.init.xavier_uniform_(self.v_s, gain=nn.init.calculate_gain('relu'))
+
+    def _empty(self, ent_embeds):
+        return ent_embeds.new_zeros(0, 3 * self.h_dim)
+
+    def pooled(self, nb, ent_embeds, rel_embeds):
+        p, q = ops.NbrAttnProjFn.apply(ent_embeds, rel_embeds, self.attn_s.weight, self.attn_s.bias, nb)
+        return ops.NbrPoolFn.apply(ent_embeds, rel_embeds, p, q, self.v_s, nb)

@@ -256,6 +256,12 @@ def ragged_arange(starts, counts):
     return base + np.arange(total, dtype=np.int64)
 
 
+def length_order(lens):
+    """The permutation that sorts sequences by history length, descending, ties in their given order (stable): what
+    build_batch(sort=True) and NeighbourBatch order their sequences by."""
+    return np.argsort(-np.asarray(lens, dtype=np.int64), kind='stable')
+
+
 class FlatHistory(object):
     """Histories of a list of sequences in flat arrays: sequence i owns steps
     [seq_ptr[i], seq_ptr[i+1]); step k has timestamp step_t[k] and neighbour objects
@@ -348,6 +354,114 @@ class SegPlan(object):
             p.seg_ptr = np.zeros(1, np.int32)
         p.num_segments = int(len(p.target))
         return p
+
+
+class NeighbourBatch(object):
+    """Host batch of the mean / attentive encoders (Aggregator.MeanAggregator, AttnAggregator; restates
+    utils.py:186-207 get_sorted_s_r_embed + the packing of Aggregator.py:273-285): no graph, only the neighbour id lists.
+
+    hist: the reference's layout for these classes -- hist[i] = list (one entry per time step) of 1-D id arrays -- or a
+    FlatHistory (seq_ptr, nbr_ptr, nbr_o; step_t is not read).  Sequences are sorted by history length, descending
+    (length_order, the routine of build_batch(sort=True)); empty sequences are dropped.  One SEGMENT is one time step of
+    one kept sequence; segments are sequence-major (the order of the reference's len_s / flattened ids).
+    int32 arrays: perm [B], batch_sizes [L], seg_ptr [S + 1], nbr [nnz], seg_s / seg_r / seg_q / out_row [S] (seg_q: the
+    segment's position in the sorted batch, out_row: its row in the packed time-major layout), s_sorted / r_sorted [nseq].
+    SegPlans: plan_nbr (neighbour rows per entity), plan_seq (segments per sequence); plan_s / plan_r (kept sequences per
+    subject entity / relation).  to(device) uploads the index arrays (one copy) for renet_nbr_pool_fwd / bwd."""
+    INT_FIELDS = ('nbr', 'seg_ptr', 'seg_s', 'seg_r', 'seg_q', 'out_row', 's_sorted', 'r_sorted')
+    PLANS = ('plan_nbr', 'plan_seq', 'plan_s', 'plan_r')
+
+    def __init__(self, s, r, hist, seq_len=None):
+        from gpu_builder import _check_int32
+        s = np.asarray(s, dtype=np.int64).reshape(-1)
+        r = np.asarray(r, dtype=np.int64).reshape(-1)
+        seq_ptr, nbr_ptr, nbr_o = self._flat(hist)
+        if len(seq_ptr) - 1 != len(s) or len(r) != len(s):
+            raise ValueError('one history per (s, r) pair expected')
+        lens_all = np.diff(seq_ptr)
+        perm = length_order(lens_all)
+        nseq = int(np.count_nonzero(lens_all))
+        ln = lens_all[perm][:nseq]
+        self.B, self.nseq, self.lens = len(s), nseq, ln
+        self.L = int(ln[0]) if nseq else 0
+        if seq_len is not None and self.L > seq_len:
+            raise ValueError('history longer than seq_len (%d > %d)' % (self.L, seq_len))
+        self.S = S = int(ln.sum())
+        step_seq = np.repeat(np.arange(nseq, dtype=np.int64), ln)
+        step_idx = ragged_arange(seq_ptr[perm[:nseq]], ln)
+        step_j = np.arange(S, dtype=np.int64) - np.repeat(np.cumsum(ln) - ln, ln)
+        cnt = nbr_ptr[step_idx + 1] - nbr_ptr[step_idx]
+        if S and cnt.min() < 1:
+            raise ValueError('a history step without neighbours')
+        nbr = nbr_o[ragged_arange(nbr_ptr[step_idx], cnt)]
+        self.nnz = int(len(nbr))
+        bs = (ln[None, :] > np.arange(self.L)[:, None]).sum(axis=1) if self.L else np.zeros(0, np.int64)
+        off = np.concatenate(([0], np.cumsum(bs))).astype(np.int64)
+        s_sorted, r_sorted = s[perm], r[perm]
+        _check_int32('neighbour / subject / relation ids', nbr, s, r, limit=2 ** 31 - 1)
+        _check_int32('batch sizes', np.asarray([self.nnz, S, len(s)]))
+        self.max_ent = int(max(nbr.max() if self.nnz else -1, s.max() if len(s) else -1))
+        self.max_rel = int(r.max()) if len(r) else -1
+        self.perm = perm.astype(np.int32)
+        self.batch_sizes = bs.astype(np.int32)
+        self.seg_ptr = np.concatenate(([0], np.cumsum(cnt))).astype(np.int32)
+        self.nbr = nbr.astype(np.int32)
+        self.seg_s = s_sorted[step_seq].astype(np.int32)
+        self.seg_r = r_sorted[step_seq].astype(np.int32)
+        self.seg_q = step_seq.astype(np.int32)
+        self.out_row = (off[step_j] + step_seq).astype(np.int32)
+        self.s_sorted, self.r_sorted = s_sorted[:nseq].astype(np.int32), r_sorted[:nseq].astype(np.int32)
+        self.plan_nbr = SegPlan.host(self.nbr)
+        self.plan_seq = SegPlan.host(self.seg_q)
+        self.plan_s = SegPlan.host(self.s_sorted)
+        self.plan_r = SegPlan.host(self.r_sorted)
+
+    @staticmethod
+    def _flat(hist):
+        """-> (seq_ptr, nbr_ptr, nbr_o) as int64 arrays."""
+        if isinstance(hist, FlatHistory):
+            return hist.seq_ptr, hist.nbr_ptr, hist.nbr_o
+        lens = np.fromiter(map(len, hist), dtype=np.int64, count=len(hist))
+        steps = [np.asarray(a, dtype=np.int64).reshape(-1) for a in _chain.from_iterable(hist)]
+        cnt = np.fromiter(map(len, steps), dtype=np.int64, count=len(steps))
+        nbr_o = np.concatenate(steps) if steps else np.zeros(0, np.int64)
+        return np.concatenate(([0], np.cumsum(lens))), np.concatenate(([0], np.cumsum(cnt))), nbr_o
+
+    def to(self, device):
+        """-> DeviceNeighbourBatch: the same fields as device int32 views of ONE upload (plans included)."""
+        return DeviceNeighbourBatch(self, device)
+
+
+class DeviceNeighbourBatch(object):
+    """A NeighbourBatch on the device: INT_FIELDS and the four plans as int32 device views; `host` keeps the numpy
+    side (perm, batch_sizes, sizes) and seg_ptr_host is the host copy of seg_ptr the kernels' entry checks read."""
+
+    def __init__(self, hb, device):
+        parts, names = [], []
+        for f in hb.INT_FIELDS:
+            names.append(f)
+            parts.append(getattr(hb, f))
+        for pn in hb.PLANS:
+            p = getattr(hb, pn)
+            for f in ('order', 'seg_ptr', 'target'):
+                names.append(pn + '.' + f)
+                parts.append(getattr(p, f))
+        sizes = [len(a) for a in parts]
+        offs = np.concatenate(([0], np.cumsum(sizes)))
+        dev = h2d(np.concatenate(parts).astype(np.int32) if parts else np.zeros(0, np.int32), device)
+        self._buf = dev
+        views = {nm: dev[o_:o_ + n] for nm, o_, n in zip(names, offs, sizes)}
+        for f in hb.INT_FIELDS:
+            setattr(self, f, views[f])
+        for pn in hb.PLANS:
+            p = SegPlan()
+            p.order, p.seg_ptr, p.target = views[pn + '.order'], views[pn + '.seg_ptr'], views[pn + '.target']
+            p.num_segments = getattr(hb, pn).num_segments
+            setattr(self, pn, p)
+        self.host = hb
+        self.seg_ptr_host = hb.seg_ptr
+        for f in ('B', 'nseq', 'L', 'S', 'nnz', 'max_ent', 'max_rel'):
+            setattr(self, f, getattr(hb, f))
 
 
 class HostBatch(object):
@@ -584,7 +698,7 @@ def build_batch(store, num_ent, num_rels, s, r, fh, sort=True, glob_index=None, 
         raise ValueError('history neighbour id out of range')
     lens_all = np.diff(fh.seq_ptr)
     if sort:
-        perm = np.argsort(-lens_all, kind='stable')            # ONE permutation
+        perm = length_order(lens_all)                          # ONE permutation
     else:
         perm = np.arange(B)
     lens_sorted = lens_all[perm]

@@ -888,6 +888,104 @@ class SegmentPoolFn(Function):
         return K.segment_pool_bwd(_c(dout), seg_ptr, arg, num_graphs, is_max, n), None, None, None
 
 
+class NbrAttnProjFn(Function):
+    """The two projections of the attentive encoder's score (Aggregator.py:333-334) with attn_s.weight = [W_o | W_s | W_r]:
+        P = E W_o^T  [N_ent, D]   (one row per ENTITY instead of one per neighbour occurrence)
+        q = E[s] W_s^T + R[r] W_r^T + b  [nseq, D]   (one row per kept sequence of the batch)
+    so that the score of neighbour j is v . tanh(P[nbr_j] + q).  All products on the GEMM front (the process GEMM mode)."""
+
+    @staticmethod
+    @_fwd_mode
+    def forward(ctx, ent, rel, weight, bias, nb):
+        ctx.srcs = (ent, rel, weight, bias)
+        ent, rel, weight, bias = _c(ent), _c(rel), _c(weight), _c(bias)
+        d = ent.shape[1]
+        w_o, w_s, w_r = (_c(weight[:, k * d:(k + 1) * d]) for k in range(3))
+        p = K.gemm(ent, w_o, tb=True)
+        es, rr = K.gather_rows(ent, nb.s_sorted), K.gather_rows(rel, nb.r_sorted)
+        q = K.gemm(es, w_s, tb=True, bias=bias)
+        K.gemm(rr, w_r, tb=True, out=q, beta=1.0)
+        ctx.nb = nb
+        ctx.save_for_backward(ent, rel, w_o, w_s, w_r, es, rr)
+        return p, q
+
+    @staticmethod
+    @_bwd_mode
+    def backward(ctx, dp, dq):
+        ent, rel, w_o, w_s, w_r, es, rr = ctx.saved_tensors
+        nb, d = ctx.nb, ent.shape[1]
+        t_ent, t_rel, t_w, t_b = [grad_target(t) for t in ctx.srcs]
+        dp, dq = _c(dp), _c(dq)
+        d_ent = t_ent if t_ent is not None else torch.zeros_like(ent)
+        K.gemm(dp, w_o, out=d_ent, beta=1.0)                             # += dP W_o
+        K.segment_add(K.gemm(dq, w_s), nb.plan_s, d_ent)                 # per-sequence rows -> their subject entity
+        d_rel = _segment_grad(K.gemm(dq, w_r), nb.plan_r, t_rel, rel.shape)
+        acc = t_w is not None
+        d_w = t_w if acc else torch.empty(d, 3 * d, device=ent.device, dtype=torch.float32)
+        beta = 1.0 if acc else 0.0
+        K.gemm(dp, ent, ta=True, out=d_w[:, :d], beta=beta)
+        K.gemm(dq, es, ta=True, out=d_w[:, d:2 * d], beta=beta)
+        K.gemm(dq, rr, ta=True, out=d_w[:, 2 * d:], beta=beta)
+        return (None if t_ent is not None else d_ent), d_rel, (None if acc else d_w), _colsum_grad(dq, t_b), None
+
+
+class NbrPoolFn(Function):
+    """Aggregator.py:249-285 (mean) / 316-346 (attention) up to the dropout: the packed GRU input of a
+    graph.DeviceNeighbourBatch.  p / q / v None: mean mode, out [S, 2D] = [mean_j E[nbr_j] | E[s]]; else attention,
+    out [S, 3D] = [sum_j softmax_j(v . tanh(P[nbr_j] + q)) E[nbr_j] | E[s] | R[r]] (p, q from NbrAttnProjFn).
+    Backward: renet_nbr_pool_bwd's contribution rows, summed per entity / sequence by the deterministic segmented adds."""
+
+    @staticmethod
+    @_fwd_mode
+    def forward(ctx, ent, rel, p, q, v, nb):
+        attn = p is not None
+        if nb.max_ent >= ent.shape[0] or (attn and nb.max_rel >= rel.shape[0]):
+            raise ValueError('batch entity / relation id beyond the embedding table')
+        if attn and (p.shape != ent.shape or tuple(q.shape) != (nb.nseq, ent.shape[1]) or v.numel() != ent.shape[1]
+                     or rel.shape[1] != ent.shape[1]):
+            raise ValueError('NbrPoolFn: P must be [N_ent, D], q [sequences, D], v [D, 1], R [., D]')
+        ctx.srcs = (ent, rel)
+        ent = _c(ent)
+        if attn:
+            rel, p, q, v = _c(rel), _c(p), _c(q), _c(v)
+        out, stats, w = K.nbr_pool_fwd(ent, rel if attn else None, p, q, v if attn else None, nb)
+        ctx.nb, ctx.attn, ctx.stats = nb, attn, stats
+        ctx.rel_shape = rel.shape if attn else None
+        ctx.v_shape = v.shape if attn else None
+        if attn:
+            ctx.save_for_backward(ent, p, q, v, w, out)
+        else:
+            ctx.save_for_backward(ent)
+        return out
+
+    @staticmethod
+    @_bwd_mode
+    def backward(ctx, dout):
+        nb, attn = ctx.nb, ctx.attn
+        ent = ctx.saved_tensors[0]
+        p, q, v, w, out = ctx.saved_tensors[1:] if attn else (None,) * 5
+        dev, d = ent.device, ent.shape[1]
+        t_ent, t_rel = grad_target(ctx.srcs[0]), (grad_target(ctx.srcs[1]) if attn else None)
+        ce, cp, dq_rows, dv_rows, ds_rows, dr_rows = K.nbr_pool_bwd(_c(dout), out, ent, p, q, v, w, nb)
+        d_ent = t_ent if t_ent is not None else torch.zeros(ent.shape, device=dev, dtype=torch.float32)
+        ds_seq = torch.zeros(nb.nseq, d, device=dev, dtype=torch.float32)
+        if not attn:
+            K.segment_add(ce, nb.plan_nbr, d_ent)
+            K.segment_add(ds_rows, nb.plan_seq, ds_seq)
+            K.segment_add(ds_seq, nb.plan_s, d_ent)
+            return (None if t_ent is not None else d_ent), None, None, None, None, None
+        d_p = torch.zeros(ent.shape, device=dev, dtype=torch.float32)
+        K.segment_add2(ce, cp, nb.plan_nbr, d_ent, d_p)
+        dr_seq = torch.zeros(nb.nseq, d, device=dev, dtype=torch.float32)
+        K.segment_add2(ds_rows, dr_rows, nb.plan_seq, ds_seq, dr_seq)
+        K.segment_add(ds_seq, nb.plan_s, d_ent)
+        d_rel = _segment_grad(dr_seq, nb.plan_r, t_rel, ctx.rel_shape)
+        d_q = torch.zeros(nb.nseq, d, device=dev, dtype=torch.float32)
+        K.segment_add(dq_rows, nb.plan_seq, d_q)
+        d_v = K.colsum(dv_rows).reshape(ctx.v_shape)
+        return (None if t_ent is not None else d_ent), d_rel, d_p, d_q, d_v, None
+
+
 class DropoutFn(Function):
     """Counter-based inverted dropout (Aggregator.py:69); the mask is regenerated in backward."""
 

@@ -184,6 +184,8 @@ _SIGNATURES = {
     'renet_segment_pool_fwd': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     'renet_segment_pool_bwd': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
                                        c_void_p]),
+    'renet_nbr_pool_fwd': (c_int, [c_void_p] * 12 + [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'renet_nbr_pool_bwd': (c_int, [c_void_p] * 12 + [c_int, c_int, c_int] + [c_void_p] * 7),
 }
 
 EXPORTS = sorted(_SIGNATURES)
@@ -1475,6 +1477,50 @@ def segment_pool_bwd(dout, seg_ptr, arg, num_graphs, is_max, n):
     _check(lib().renet_segment_pool_bwd(_f32(dout), _i32(seg_ptr), _i32(arg), num_graphs, d, int(is_max), n,
                                         _f32(dh), _stream()), 'segment_pool_bwd')
     return dh
+
+
+def _host_i32(a):
+    """Host pointer of a contiguous int32 numpy array (the caller keeps the array alive across the call)."""
+    if a.dtype.name != 'int32' or not a.flags['C_CONTIGUOUS']:
+        raise RenetHipError('host index arrays must be contiguous int32')
+    return a.ctypes.data_as(c_void_p)
+
+
+def nbr_pool_fwd(e, r, p, q, v, nb):
+    """Neighbour pooling of graph.NeighbourBatch `nb` (device arrays + the host copy of seg_ptr) -> (out, stats, w):
+    mean mode (p is None) out [S, 2D] = [mean E[nbr] | E[s]], stats = w = None; attention mode out [S, 3D] =
+    [softmax-weighted sum | E[s] | R[r]], stats [S, 2] = (max, log-sum) per segment, w [nnz] the softmax weights."""
+    attn = p is not None
+    d = e.shape[1]
+    out = torch.empty(nb.S, (3 if attn else 2) * d, device=e.device, dtype=torch.float32)
+    stats = torch.empty(nb.S, 2, device=e.device, dtype=torch.float32) if attn else None
+    w = torch.empty(nb.nnz, device=e.device, dtype=torch.float32) if attn else None
+    t0 = _timed()
+    _check(lib().renet_nbr_pool_fwd(_f32(e), _f32(r) if attn else None, _f32(p), _f32(q) if attn else None,
+                                    _f32(v) if attn else None, _i32(nb.nbr), _i32(nb.seg_ptr), _host_i32(nb.seg_ptr_host),
+                                    _i32(nb.seg_s), _i32(nb.seg_r), _i32(nb.seg_q), _i32(nb.out_row), nb.S, d, int(attn),
+                                    _f32(out), _f32(stats), _f32(w), _stream()), 'nbr_pool_fwd')
+    _timed_end(t0, 'nbr_pool_fwd', nbytes=float(nb.nnz * d * 4 * (2 if attn else 1) + out.numel() * 4))
+    return out, stats, w
+
+
+def nbr_pool_bwd(dout, out, e, p, q, v, w, nb):
+    """-> (cE [nnz, D], cP [nnz, D] | None, dq_rows [S, D] | None, dv_rows [S, D] | None, ds_rows [S, D],
+    dr_rows [S, D] | None): the contribution rows and per-segment partial rows of renet_nbr_pool_bwd."""
+    attn = p is not None
+    d = e.shape[1]
+
+    def rows(n, on=True):
+        return torch.empty(n, d, device=e.device, dtype=torch.float32) if on else None
+    ce, cp = rows(nb.nnz), rows(nb.nnz, attn)
+    dq, dv, ds, dr = rows(nb.S, attn), rows(nb.S, attn), rows(nb.S), rows(nb.S, attn)
+    t0 = _timed()
+    _check(lib().renet_nbr_pool_bwd(_f32(dout), _f32(out) if attn else None, _f32(e), _f32(p), _f32(q) if attn else None,
+                                    _f32(v) if attn else None, _f32(w), _i32(nb.nbr), _i32(nb.seg_ptr),
+                                    _host_i32(nb.seg_ptr_host), _i32(nb.seg_q), _i32(nb.out_row), nb.S, d, int(attn),
+                                    _f32(ce), _f32(cp), _f32(dq), _f32(dv), _f32(ds), _f32(dr), _stream()), 'nbr_pool_bwd')
+    _timed_end(t0, 'nbr_pool_bwd', nbytes=float(nb.nnz * d * 4 * (4 if attn else 1) + dout.numel() * 4))
+    return ce, cp, dq, dv, ds, dr
 
 
 def sumsq_partials(g, partial, slot0, n_slots):
