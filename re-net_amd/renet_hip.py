@@ -372,26 +372,34 @@ def segment_add2(src0, src1, plan, dst0, dst1):
                                     plan.num_segments, src0.shape[1], _f32(dst0), _f32(dst1), _stream()), 'segment_add2')
 
 
+def _heavy(rows):
+    """(pointer, count) of a hub-row list; (None, 0) without one."""
+    return (_i32(rows), rows.numel()) if rows is not None else (None, 0)
+
+
+def _gather_timed_end(t0, name, n_edges, n_rows, d, weight, has_addend, x_bytes=4, w_bytes=4):
+    """The timer record of one gather launch: nbytes = its algorithmic bytes, tag = the strict bytes (no addend row)."""
+    if t0 is not None:
+        _timed_end(t0, name, nbytes=float(gather_bytes(n_edges, n_rows, d, weight.numel(), has_addend, x_bytes, w_bytes)),
+                   tag=float(gather_bytes(n_edges, n_rows, d, weight.numel(), False, x_bytes, w_bytes)))
+
+
 def rgcn_gather(x, row_ptr, col, etype, scale, weight, type_shift, transpose_w, addend, drop_p, seed,
                 relu, out, heavy_rows=None, heavy_thresh=0, src_limit=0, addend_rows=0, n_edges=None):
     """n_edges: edges actually walked by this launch (pruned launches), for the byte accounting only."""
-    n, d = x.shape[0], x.shape[1]
+    d = x.shape[1]
     t0 = _timed()
     _check(lib().renet_rgcn_gather(_f32(x), d, _i32(row_ptr), _i32(col), _i32(etype), _f32(scale),
                                    _f32(weight), weight.shape[0], type_shift, int(transpose_w),
                                    _f32(addend), float(drop_p), int(seed), int(relu), _f32(out),
-                                   out.shape[0], _i32(heavy_rows) if heavy_rows is not None else None,
-                                   heavy_rows.numel() if heavy_rows is not None else 0, int(heavy_thresh),
+                                   out.shape[0], *_heavy(heavy_rows), int(heavy_thresh),
                                    int(src_limit), int(addend_rows), _stream()), 'rgcn_gather')
     if t0 is not None:
-        # algorithmic bytes (SURVEY 8d): per edge one source row + src + type index; per node one output
-        # row + row_ptr + norm (+ the fused addend row); the relation weight table once
-        nn = out.shape[0]
-        e = col.numel() if n_edges is None else int(n_edges)
-        nbytes = e * (d * 4 + 8) + nn * (d * 4 + 8) + weight.numel() * 4 + (nn * d * 4 if addend is not None else 0)
         # launches over the full batch graph (layer 1 and its backward) and the pruned ones (last layer:
         # subject rows only, a few thousand short rows -- launch-latency bound) are different regimes
-        _timed_end(t0, 'rgcn_gather' if n_edges is None else 'rgcn_gather_pruned', nbytes=float(nbytes))
+        e = col.numel() if n_edges is None else int(n_edges)
+        _timed_end(t0, 'rgcn_gather' if n_edges is None else 'rgcn_gather_pruned',
+                   nbytes=float(gather_bytes(e, out.shape[0], d, weight.numel(), addend is not None)))
     return out
 
 
@@ -402,6 +410,11 @@ def gather_bytes(n_edges, n_rows, d, weight_numel, has_addend, x_bytes=4, w_byte
     of the source rows / the relation table as STORED (2 in the bf16-storage forms)."""
     return (n_edges * (d * x_bytes + 8) + n_rows * (d * 4 + 8) + weight_numel * w_bytes +
             (n_rows * d * 4 if has_addend else 0))
+
+
+def _item_args(it_src, it_type, g, n_groups, col):
+    """The argument run every item entry has behind D: the item stream, then the CSR arrays the hub rows walk."""
+    return (_i32(it_src), _i32(it_type), _i32(g.grp_ptr), int(n_groups), _i32(g.row_ptr), _i32(col), _i32(g.etype))
 
 
 def rgcn_gather_items(x, g, weight, type_shift, transpose_w, addend, drop_p, seed, relu, out, use_norm=True,
@@ -422,25 +435,16 @@ def rgcn_gather_items(x, g, weight, type_shift, transpose_w, addend, drop_p, see
                            transpose_w, addend, drop_p, seed, relu, out, heavy, g.heavy_thresh, src_limit,
                            addend_rows, n_edges=g.E_out if pruned else None)
     t0 = _timed()
-    hv, nhv = (_i32(heavy), heavy.numel()) if heavy is not None else (None, 0)
+    head = (_f32(x), d) + _item_args(g.it_src, g.it_type, g, n_groups, g.col) + (_f32(g.norm) if use_norm else None,)
+    tail = (weight.shape[0], int(type_shift), int(transpose_w), _f32(addend), float(drop_p), int(seed), int(relu),
+            _f32(out), n_rows) + _heavy(heavy) + (int(src_limit), int(addend_rows), int(pruned), _stream())
     if w16 is not None:
-        _check(lib().renet_rgcn_gather_items_bf16(
-            _f32(x), d, _i32(g.it_src), _i32(g.it_type), _i32(g.grp_ptr), int(n_groups), _i32(g.row_ptr), _i32(g.col),
-            _i32(g.etype), _f32(g.norm) if use_norm else None, w16.p.data_ptr(), w16.p.shape[1], weight.shape[0],
-            int(type_shift), int(transpose_w), _f32(addend), float(drop_p), int(seed), int(relu), _f32(out), n_rows,
-            hv, nhv, int(src_limit), int(addend_rows), int(pruned), _stream()), 'rgcn_gather_items_bf16')
+        _check(lib().renet_rgcn_gather_items_bf16(*head, w16.p.data_ptr(), w16.p.shape[1], *tail),
+               'rgcn_gather_items_bf16')
     else:
-        _check(lib().renet_rgcn_gather_items(
-            _f32(x), d, _i32(g.it_src), _i32(g.it_type), _i32(g.grp_ptr), int(n_groups), _i32(g.row_ptr), _i32(g.col),
-            _i32(g.etype), _f32(g.norm) if use_norm else None, _f32(weight), weight.shape[0], int(type_shift),
-            int(transpose_w), _f32(addend), float(drop_p), int(seed), int(relu), _f32(out), n_rows, hv, nhv,
-            int(src_limit), int(addend_rows), int(pruned), _stream()), 'rgcn_gather_items')
-    if t0 is not None:
-        e = g.E_out if pruned else g.E
-        name = 'rgcn_gather_%s_%s' % ('bwdh' if transpose_w else 'fwd', 'pruned' if pruned else 'full')
-        wb = 2 if w16 is not None else 4
-        _timed_end(t0, name, nbytes=float(gather_bytes(e, n_rows, d, weight.numel(), addend is not None, 4, wb)),
-                   tag=float(gather_bytes(e, n_rows, d, weight.numel(), False, 4, wb)))       # tag: the strict bytes
+        _check(lib().renet_rgcn_gather_items(*head, _f32(weight), *tail), 'rgcn_gather_items')
+    _gather_timed_end(t0, 'rgcn_gather_%s_%s' % ('bwdh' if transpose_w else 'fwd', 'pruned' if pruned else 'full'),
+                      g.E_out if pruned else g.E, n_rows, d, weight, addend is not None, 4, 2 if w16 is not None else 4)
     return out
 
 
@@ -476,27 +480,19 @@ def rgcn_gather_items_table(table, g, weight, type_shift, addend_table, drop_p, 
     d = table.shape[1]
     n_rows = out.shape[0]
     it_src_t, it_type_t, col_t, _ = g.table_items()
-    heavy = g.heavy_rows
+    b16 = table16 is not None and w16 is not None
     t0 = _timed()
-    if table16 is not None and w16 is not None:
-        _check(lib().renet_rgcn_gather_items_table_bf16(
-            table16.p.data_ptr(), table16.p.shape[1], table.shape[0], d, _i32(it_src_t), _i32(it_type_t),
-            _i32(g.grp_ptr), int(g.n_groups), _i32(g.row_ptr), _i32(col_t), _i32(g.etype), _i32(g.node_ent),
-            _f32(g.norm), w16.p.data_ptr(), w16.p.shape[1], weight.shape[0], int(type_shift), _f32(addend_table),
-            float(drop_p), int(seed), int(relu), _f32(out), n_rows, _i32(heavy) if heavy is not None else None,
-            heavy.numel() if heavy is not None else 0, _stream()), 'rgcn_gather_items_table_bf16')
+    items = (table.shape[0], d) + _item_args(it_src_t, it_type_t, g, g.n_groups, col_t) + (_i32(g.node_ent), _f32(g.norm))
+    tail = (weight.shape[0], int(type_shift), _f32(addend_table), float(drop_p), int(seed), int(relu), _f32(out),
+            n_rows) + _heavy(g.heavy_rows) + (_stream(),)
+    if b16:
+        _check(lib().renet_rgcn_gather_items_table_bf16(table16.p.data_ptr(), table16.p.shape[1], *items,
+                                                        w16.p.data_ptr(), w16.p.shape[1], *tail),
+               'rgcn_gather_items_table_bf16')
     else:
-        _check(lib().renet_rgcn_gather_items_table(
-            _f32(table), table.shape[0], d, _i32(it_src_t), _i32(it_type_t), _i32(g.grp_ptr), int(g.n_groups),
-            _i32(g.row_ptr), _i32(col_t), _i32(g.etype), _i32(g.node_ent), _f32(g.norm), _f32(weight), weight.shape[0],
-            int(type_shift), _f32(addend_table), float(drop_p), int(seed), int(relu), _f32(out), n_rows,
-            _i32(heavy) if heavy is not None else None, heavy.numel() if heavy is not None else 0, _stream()),
-            'rgcn_gather_items_table')
-    if t0 is not None:          # SURVEY 8d's ALGORITHMIC bytes: one source row per edge, one output (+ addend) row per node
-        eb = 2 if (table16 is not None and w16 is not None) else 4
-        _timed_end(t0, 'rgcn_gather_fwd_full',
-                   nbytes=float(gather_bytes(g.E, n_rows, d, weight.numel(), addend_table is not None, eb, eb)),
-                   tag=float(gather_bytes(g.E, n_rows, d, weight.numel(), False, eb, eb)))
+        _check(lib().renet_rgcn_gather_items_table(_f32(table), *items, _f32(weight), *tail), 'rgcn_gather_items_table')
+    eb = 2 if b16 else 4       # SURVEY 8d's ALGORITHMIC bytes: one source row per edge, one output (+ addend) row per node
+    _gather_timed_end(t0, 'rgcn_gather_fwd_full', g.E, n_rows, d, weight, addend_table is not None, eb, eb)
     return out
 
 

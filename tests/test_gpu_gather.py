@@ -107,6 +107,44 @@ def test_item_gather_matches_fp64_definition(dev, d, heavy, budget):
     assert torch.equal(o1, o2)
 
 
+@pytest.mark.parametrize('d', [100, 200, 300, 400])
+def test_csr_gather_pruned_backward_arguments(dev, d):
+    """src_limit / addend_rows of the plain-CSR entry (in production reached only through the >= 2 GiB fallback of
+    rgcn_gather_items): the pruned backward launch, in place, on a small graph with a hub row of more than one 64-edge
+    index window and empty rows -- against the fp64 definition, and the item-stream entry against the same."""
+    import graph as G
+    import renet_hip as K
+    T, n, n_out, heavy = 6, 300, 110, 8
+    rng = np.random.RandomState(d)
+    deg = rng.poisson(3, n)
+    deg[57], deg[5], deg[231] = 70, 0, 0
+    dst = np.repeat(np.arange(n), deg)
+    src, et = rng.randint(0, n, len(dst)), rng.randint(0, T, len(dst))
+    hb = G.HostBatch().set_edges(n, src, dst, et, T, heavy=heavy)
+    hb.set_out_rows(n_out, src, dst, et)
+    hb.set_gather_plan(n_out, heavy=heavy)
+    g = G.DeviceGraph(hb, dev)
+    assert g.heavy_thresh == heavy and 57 in g.heavy_rows.cpu().numpy() and int(np.diff(hb.row_ptr).min()) == 0
+    w = (rng.randn(T, d * d // 100) * 0.3).astype(np.float32)
+    gn = np.zeros((n, d), np.float32)
+    gn[:n_out] = rng.randn(n_out, d)
+    dh0 = np.zeros((n, d), np.float32)
+    dh0[:n_out] = rng.randn(n_out, d)
+    ref = reference(gn, src, dst, et, w, d, T, T // 2, True, None, dh0, False, n, n_out, n_out)
+    tw, tgn = torch.from_numpy(w).to(dev), torch.from_numpy(gn).to(dev)
+    tgn[n_out:] = float('nan')                         # sources >= src_limit must never be read
+    for items in (False, True):
+        dh = torch.from_numpy(dh0).to(dev)
+        dh[n_out:] = float('nan')                      # rows >= addend_rows must be overwritten, never read
+        if items:
+            K.rgcn_gather_items(tgn, g, tw, T // 2, True, dh, 0.0, 0, False, dh, use_norm=False, pruned=True,
+                                src_limit=n_out, addend_rows=n_out)
+        else:
+            K.rgcn_gather(tgn, g.row_ptr, g.col, g.etype, None, tw, T // 2, True, dh, 0.0, 0, False, dh,
+                          heavy_rows=g.heavy_rows, heavy_thresh=g.heavy_thresh, src_limit=n_out, addend_rows=n_out)
+        np.testing.assert_allclose(dh.cpu().numpy(), ref, rtol=1e-4, atol=1e-4)
+
+
 def test_item_gather_dropout_mask_equals_the_csr_kernels(dev):
     """The fused self-loop dropout mask is keyed by (seed, row, chunk): both kernels and the backward prologue
     regenerate the same one."""
