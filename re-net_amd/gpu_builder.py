@@ -1,4 +1,4 @@
-"""Device-side batch-graph builder for the merged training batch (csrc/builder.hip, renet_build_batch_both).
+"""Device-side batch-graph builder for the merged training batch (csrc/builder_both.hip, renet_build_batch_both).
 
 The host builder (graph.build_batch_both: numpy front + the native passes of csrc/host_builder.cpp) costs ~13 ms per
 merged batch against a ~3.6 ms device step.  Here the dataset is resident in HBM -- the quadruples, the per-role
@@ -10,7 +10,7 @@ Replaces, for that case, utils.py:209-244 + 115-131 + dgl.batch of the reference
 
 The global model's full-graph batches (graph.build_full_graphs; Aggregator.py:44-55 / 87-98) are built the same way:
 `FullGraphStore` keeps the per-timestamp node lists and local fact endpoints resident, `FullGraphBatch` is the union of the
-full graphs of a list of timestamps (csrc/builder.hip: renet_build_full_graphs, the same tail kernels behind a three-kernel
+full graphs of a list of timestamps (csrc/builder_full.hip: renet_build_full_graphs, the same tail kernels behind a three-kernel
 front), again bit-identical to the host builder (tests/test_gpu_full_graph_builder.py).
 
 Grouped inference batches (graph.build_batch(group=...), RGCNAggregator.forward_grouped) are the third front:
@@ -310,7 +310,7 @@ class _Host(object):
         return self._perm
 
 
-# the fronts of csrc/builder.hip: (workspace size, build) of the C ABI
+# the fronts of csrc/builder_both.hip, builder_grouped.hip and builder_full.hip: (workspace size, build) of the C ABI
 _FRONT_BOTH = ('renet_build_batch_workspace', 'renet_build_batch_both')
 _FRONT_GROUPED = ('renet_build_batch_grouped_workspace', 'renet_build_batch_grouped')
 _FRONT_FULL = ('renet_build_full_graphs_workspace', 'renet_build_full_graphs')
@@ -516,7 +516,7 @@ class GroupedDeviceBatch(DeviceBatch):
         _PendingBatch.__init__(self, _FRONT_GROUPED, store, None, (int(seq_len),), own, cn, ce, stream)
 
 
-# ---- full-graph batches of the global model (csrc/builder.hip: renet_build_full_graphs) -----------------------------------
+# ---- full-graph batches of the global model (csrc/builder_full.hip: renet_build_full_graphs) ------------------------------
 MAX_FULL_GRAPHS = 1024       # member graphs per call (one workgroup scans their counts)
 
 

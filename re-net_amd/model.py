@@ -379,7 +379,7 @@ class RENet(nn.Module):
 
     def _prepare_both_lists_device(self, triplets, s_hist, o_hist, graph_dict):
         """prepare_both() for a batch that arrives through the reference's LIST API, with the batch graph built by the DEVICE
-        builder (csrc/builder.hip): the nested lists are flattened on the host (graph.FlatHistory.from_lists), uploaded with
+        builder (csrc/builder_both.hip): the nested lists are flattened on the host (graph.FlatHistory.from_lists), uploaded with
         the batch's (s, r, o) in one copy (gpu_builder.ListBatchStore) and everything else -- node sets, induced edges,
         norm, plans: utils.py:209-244 + 115-131 + dgl.batch -- is kernels; the arrays are those of the host builder
         (tests/test_gpu_builder.py).  None when a direction has no history at all (the caller takes the host path)."""

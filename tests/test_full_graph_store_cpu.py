@@ -1,5 +1,5 @@
 """CPU tests of the resident store behind the device builder of the global model's full-graph batches
-(gpu_builder.FullGraphStore; csrc/builder.hip: renet_build_full_graphs).  No GPU is needed or initialised here: the store
+(gpu_builder.FullGraphStore; csrc/builder_full.hip: renet_build_full_graphs).  No GPU is needed or initialised here: the store
 is built with device=None (host arrays only), and its numpy statement of the device front (host_edges) is pinned against
 graph.build_full_graphs, whose arrays the device builder must reproduce bit for bit (tests/test_gpu_full_graph_builder.py)."""
 import numpy as np

@@ -1,4 +1,4 @@
-"""GPU test of the DEVICE batch-graph builder (csrc/builder.hip, gpu_builder.py): for batches of the ICEWS18- and
+"""GPU test of the DEVICE batch-graph builder (csrc/builder_both.hip + builder_tail.hip, gpu_builder.py): for batches of the ICEWS18- and
 YAGO-shaped streams every array it produces is compared BIT FOR BIT with the host builder's (graph.build_batch_both =
 the numpy specification + the native host passes, themselves pinned against the reference's DGL path in
 tests/test_host_cpu.py), and a training step on a device-built batch equals the step on the host-built one."""
@@ -75,6 +75,32 @@ def test_device_built_batch_is_bit_identical_to_the_host_builder(dev, shape, seq
         db = None
         for attempt in range(6):                            # capacities grow on overflow
             db = gpu_builder.DeviceBatch(ds, idx, seq_len)
+            if db.finalize():
+                break
+        assert db._final, 'device builder did not converge on capacities'
+        _assert_same_batch(db, hb)
+
+
+def test_smallest_merged_batches_are_bit_identical_to_the_host_builder(dev):
+    """B = 1 and B = 2, with histories and with none: the smallest shapes of the single-workgroup stages (bb_seq_kernel,
+    bb_slots_kernel, bb_tile_scan_kernel, bb_chunks_kernel).  The host builder accepts a batch without any history (an
+    empty graph: N = E = S = 0), and so must the device builder."""
+    import gpu_builder
+    import graph as G
+    quads, ne, nr, gd, hs, ho, glob, ds = _setup('ICEWS18', 10, dev, 40)
+    store = G.store_for(gd)
+    gtimes = np.asarray(sorted(glob.keys()), dtype=np.int64)
+    ls, lo = np.asarray(hs.count), np.asarray(ho.count)
+    late = int(np.nonzero((ls > 0) & (lo > 0))[0][-1])        # a late quadruple: both of its histories are non-empty
+    assert ls[0] == 0 and lo[0] == 0 and late > 0              # quadruple 0: both are empty
+    for idx in ([late], [0], [late, 0]):
+        idx = np.asarray(idx)
+        hb = G.build_batch_both(store, ne, nr, quads[idx, 0], quads[idx, 1], quads[idx, 2], hs.take(idx), ho.take(idx),
+                                glob_index=lambda t: np.searchsorted(gtimes, t))
+        assert (hb.N > 0) == bool((idx == late).any()) and hb.B == 2 * len(idx)
+        db = None
+        for attempt in range(6):                            # capacities grow on overflow
+            db = gpu_builder.DeviceBatch(ds, idx, 10)
             if db.finalize():
                 break
         assert db._final, 'device builder did not converge on capacities'

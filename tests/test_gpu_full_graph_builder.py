@@ -1,4 +1,4 @@
-"""GPU tests of the DEVICE builder for the global model's full-graph batches (csrc/builder.hip: renet_build_full_graphs;
+"""GPU tests of the DEVICE builder for the global model's full-graph batches (csrc/builder_full.hip: renet_build_full_graphs;
 gpu_builder.FullGraphStore / FullGraphBatch; RGCNAggregator_global.device_builder): every array it produces is compared BIT
 FOR BIT with graph.build_full_graphs uploaded through graph.DeviceGraph, the capacity guard reports instead of faulting, a
 RENet_global computes exactly the same numbers with the switch on as with it off, and with the switch on it still matches

@@ -1,4 +1,4 @@
-"""GPU tests of the DEVICE builder for grouped inference batches (csrc/builder.hip: renet_build_batch_grouped;
+"""GPU tests of the DEVICE builder for grouped inference batches (csrc/builder_grouped.hip: renet_build_batch_grouped;
 gpu_builder.GroupedBatchStore / GroupedDeviceBatch; RGCNAggregator.grouped_device_builder): every array it produces is
 compared BIT FOR BIT with the host builder's graph.build_batch(..., sort=True, group=s), the capacities grow from 256, the
 guarded error paths raise, and forward_grouped / evaluate_filter_stream give the same results with the switch on and off."""

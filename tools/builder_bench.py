@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Times the device batch builder alone (csrc/builder.hip) on the bench workload: N builds back to back on an idle GPU.
+"""Times the device batch builder alone (csrc/builder_both.hip + builder_tail.hip) on the bench workload: N builds back to back on an idle GPU.
     python tools/builder_bench.py [n_builds]      (run under rocprofv3 --kernel-trace --stats for the per-kernel split)"""
 import os
 import sys
