@@ -580,6 +580,23 @@ int renet_rank_rows(const float* scores, int ld, int n, int C, const int32_t* la
                     const int32_t* filt_col, int filtered, int32_t* greater, int32_t* equal, float* row_loss,
                     void* stream);
 
+/* The three metric settings of one score matrix from ONE read of every row: counts [6, n] (int32, row-major) =
+ *   raw greater, raw equal            -- renet_rank_rows(filtered = 0),
+ *   filtered greater, equal           -- renet_rank_rows(filtered = 1) with the list `a` (time-agnostic: the other completions
+ *                                        known at ANY time),
+ *   time_filtered greater, equal      -- the same rule with the list `t` (time-aware: the other completions known at the
+ *                                        query's own timestamp; not in the reference),
+ * and row_loss as above (NULL: not computed).  A list is addressed in place in a resident column table of len_x entries:
+ * row i takes cols_x[start_x[i] .. start_x[i] + count_x[i]) (cut to the table; count <= 0: empty), every column at most once
+ * per row, columns outside [0, C) ignored.  All three pointers of a list NULL: no list -- that setting then gives the
+ * unfiltered sigmoid counts.  Both filtered settings are corrections of the same swept sigmoid counts, so they differ only in
+ * their lists.  RENET_ERR_BADARG for n < 0, C < 1, ld < C, a missing array, a list with only some of its three pointers or
+ * a negative length; n == 0 is a no-op. */
+int renet_rank_rows3(const float* scores, int ld, int n, int C, const int32_t* label, const int32_t* cols_a,
+                     const int32_t* start_a, const int32_t* count_a, int len_a, const int32_t* cols_t,
+                     const int32_t* start_t, const int32_t* count_t, int len_t, int32_t* counts, float* row_loss,
+                     void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * DEVICE batch-graph builder for the merged training batch (both directions of train.py:136-137 as one batch of 2B
  * sequences: graph.build_batch_both; replaces utils.py:209-244 + 115-131 + dgl.batch and this library's own HOST

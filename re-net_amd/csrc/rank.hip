@@ -12,6 +12,16 @@
 //                     CORRECTION after the sweep: a listed column other than the label loses its own contribution and
 //                     contributes the value 0 instead (equal when the gold value is 0, never greater).  scores is not
 //                     written.
+//   renet_rank_rows3: the same ONE read of every row gives the counts of THREE settings at once (int32 counts[6, n]):
+//                       raw            the scores against the gold score                      (model.py:365-381)
+//                       filtered       sigmoid(score), the time-agnostic list zeroed          (model.py:391-418)
+//                       time_filtered  sigmoid(score), the list of the query's own timestamp zeroed
+//                     and the loss.  The sweep counts every element against the gold score and its sigmoid against the
+//                     gold sigmoid; the two filtered settings are two independent corrections of the same swept sigmoid
+//                     counts, each by its own list, addressed IN PLACE in a resident table (cols, start[row], count[row]:
+//                     filter_index.FilterIndex.ranges -- no gathered copy of the lists).  The sweep is rank_rows_kernel's,
+//                     statement for statement (rk_take4<false, LOSS> + four sigmoid counts), so the loss is summed in the
+//                     same order; rank_rows_kernel itself is untouched.
 // One workgroup of 256 threads per row: a row is 40-92 KB (10 k - 23 k entities), n is a few thousand, so the grid covers
 // the chip several times over and a row's counters never leave the workgroup (wave shuffles + LDS, no global atomics).
 // 16-byte loads from the first 16-byte aligned element of the row, scalar head and tail.  The logsumexp is online per
@@ -166,6 +176,119 @@ __global__ __launch_bounds__(RK_THREADS) void rank_rows_kernel(const float* __re
     }
 }
 
+// this thread's share of one filter list, cols[start, start + count) cut to the table [0, len): rank_rows_kernel's rule
+__device__ __forceinline__ void rk_correct(const float* __restrict__ x, int C, int lab, float ground,
+                                           const int32_t* __restrict__ cols, int len, int start, int count, int tid,
+                                           int& gt, int& eq) {
+    const int zero_eq = ground == 0.f ? 1 : 0;
+    const int end = (int)min((long long)start + (long long)max(count, 0), (long long)len);
+    for (int k = max(start, 0) + tid; k < end; k += RK_THREADS) {
+        const int c = cols[k];
+        if (c == lab || c < 0 || c >= C) continue;               // (columns outside the row are ignored, never read)
+        int g1 = 0, e1 = 0;
+        rk_count<true>(x[c], ground, g1, e1);
+        gt -= g1;
+        eq += zero_eq - e1;
+    }
+}
+
+// raw counts through rk_take4<false, LOSS> (with the logsumexp, exactly as rank_rows_kernel<false, LOSS> takes an element),
+// sigmoid counts beside them
+template <bool LOSS>
+__device__ __forceinline__ void rk_take4_both(const float4 v, float xl, float gs, float& m, double& s, int* c) {
+    rk_take4<false, LOSS>(v, xl, m, s, c[0], c[1]);
+    rk_count<true>(v.x, gs, c[2], c[3]);
+    rk_count<true>(v.y, gs, c[2], c[3]);
+    rk_count<true>(v.z, gs, c[2], c[3]);
+    rk_count<true>(v.w, gs, c[2], c[3]);
+}
+
+template <bool LOSS>
+__global__ __launch_bounds__(RK_THREADS) void rank_rows3_kernel(const float* __restrict__ scores, int ld, int n, int C,
+                                                                const int32_t* __restrict__ label,
+                                                                const int32_t* __restrict__ cols_a,
+                                                                const int32_t* __restrict__ start_a,
+                                                                const int32_t* __restrict__ count_a, int len_a,
+                                                                const int32_t* __restrict__ cols_t,
+                                                                const int32_t* __restrict__ start_t,
+                                                                const int32_t* __restrict__ count_t, int len_t,
+                                                                int32_t* __restrict__ counts, float* __restrict__ row_loss) {
+    __shared__ int s_cnt[6][RK_WAVES];
+    __shared__ float s_m[RK_WAVES];
+    __shared__ double s_s[RK_WAVES];
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const float* x = scores + (size_t)row * ld;
+    const int lab = min(max(label[row], 0), C - 1);              // clamped as in rank_rows_kernel
+    const float xl = x[lab];
+    const float gs = rk_sigmoid(xl);
+
+    float m = -FLT_MAX;
+    double s = 0.0;
+    int c[6] = {0, 0, 0, 0, 0, 0};               // raw greater, equal; sigmoid greater, equal; the time-aware pair (below)
+    const int head = min(C, (int)((4 - (((uintptr_t)x >> 2) & 3)) & 3));
+    const int nvec = (C - head) >> 2;
+    const float4* xv = reinterpret_cast<const float4*>(x + head);
+    int i = tid;
+    for (; i + 3 * RK_THREADS < nvec; i += 4 * RK_THREADS) {
+        float4 v[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) v[q] = xv[i + q * RK_THREADS];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) rk_take4_both<LOSS>(v[q], xl, gs, m, s, c);
+    }
+    for (; i < nvec; i += RK_THREADS) rk_take4_both<LOSS>(xv[i], xl, gs, m, s, c);
+    const int ntail = C - head - 4 * nvec;
+    if (tid < head + ntail) {
+        const float v = x[tid < head ? tid : 4 * nvec + tid];
+        if (LOSS) rk_lse1(v, m, s);
+        rk_count<false>(v, xl, c[0], c[1]);
+        rk_count<true>(v, gs, c[2], c[3]);
+    }
+
+    // two corrections of the SAME swept sigmoid counts: the time-aware setting starts from this thread's swept share, then
+    // each list is applied to its own pair
+    c[4] = c[2];
+    c[5] = c[3];
+    if (cols_a) rk_correct(x, C, lab, gs, cols_a, len_a, start_a[row], count_a[row], tid, c[2], c[3]);
+    if (cols_t) rk_correct(x, C, lab, gs, cols_t, len_t, start_t[row], count_t[row], tid, c[4], c[5]);
+
+#pragma unroll
+    for (int k = 0; k < 6; ++k) c[k] = rk_wave_sum(c[k]);
+    double sd = 0.0;
+    if (LOSS) {
+        float wm = m;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) wm = fmaxf(wm, __shfl_xor(wm, o));
+        sd = s * rk_exp(m, wm);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) sd += __shfl_xor(sd, o);
+        m = wm;
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) s_cnt[k][wave] = c[k];
+        s_m[wave] = m;
+        s_s[wave] = sd;
+    }
+    __syncthreads();
+    if (tid < 6) {
+        int T = 0;
+#pragma unroll
+        for (int w = 0; w < RK_WAVES; ++w) T += s_cnt[tid][w];
+        counts[(size_t)tid * n + row] = T;
+    }
+    if (LOSS && tid == 0) {
+        float M = s_m[0];
+#pragma unroll
+        for (int w = 1; w < RK_WAVES; ++w) M = fmaxf(M, s_m[w]);
+        double S = 0.0;
+#pragma unroll
+        for (int w = 0; w < RK_WAVES; ++w) S += s_s[w] * rk_exp(s_m[w], M);
+        row_loss[row] = (float)(log(S) + (double)M - (double)xl);
+    }
+}
+
 }  // namespace
 
 int renet_rank_rows(const float* scores, int ld, int n, int C, const int32_t* label, const int32_t* filt_ptr,
@@ -188,6 +311,28 @@ int renet_rank_rows(const float* scores, int ld, int n, int C, const int32_t* la
         else RK_GO(false, false);
     }
 #undef RK_GO
+    RENET_LAUNCH_CHECK();
+    return RENET_OK;
+}
+
+int renet_rank_rows3(const float* scores, int ld, int n, int C, const int32_t* label, const int32_t* cols_a,
+                     const int32_t* start_a, const int32_t* count_a, int len_a, const int32_t* cols_t,
+                     const int32_t* start_t, const int32_t* count_t, int len_t, int32_t* counts, float* row_loss,
+                     void* stream) {
+    if (n < 0 || C < 1 || ld < C) return RENET_ERR_BADARG;
+    if (n == 0) return RENET_OK;
+    if (!scores || !label || !counts) return RENET_ERR_BADARG;
+    // a list is (cols, start, count) with the length of its table, or nothing at all
+    if ((start_a || count_a || cols_a) && (!start_a || !count_a || !cols_a || len_a < 0)) return RENET_ERR_BADARG;
+    if ((start_t || count_t || cols_t) && (!start_t || !count_t || !cols_t || len_t < 0)) return RENET_ERR_BADARG;
+    const dim3 grid(n), blk(RK_THREADS);
+    hipStream_t st = (hipStream_t)stream;
+#define RK_GO3(LOSS)                                                                                                    \
+    RENET_LAUNCH((rank_rows3_kernel<LOSS>), grid, blk, 0, st, scores, ld, n, C, label, cols_a, start_a, count_a, len_a,    \
+                 cols_t, start_t, count_t, len_t, counts, row_loss)
+    if (row_loss) RK_GO3(true);
+    else RK_GO3(false);
+#undef RK_GO3
     RENET_LAUNCH_CHECK();
     return RENET_OK;
 }

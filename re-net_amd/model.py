@@ -1028,6 +1028,26 @@ def _evaluate_filter(self, triplet, s_hist, o_hist, global_model, all_triplets):
     return np.array([rank_sub, rank_ob]), loss
 
 
+def _time_aware_ids(at, s, r, o, t):
+    """The time-aware filter sets of the quadruple (s, r, o, t): (objects o' with (s, r, o', t) in all_triplets, subjects s'
+    with (s', r, o, t) in it) -- evaluate_filter's selection (model.py:392-401) with the query's own timestamp added."""
+    return at[(at[:, 0] == s) & (at[:, 1] == r) & (at[:, 3] == t), 2], at[(at[:, 2] == o) & (at[:, 1] == r) & (at[:, 3] == t), 0]
+
+
+def _evaluate_time_filter(self, triplet, s_hist, o_hist, global_model, all_triplets):
+    """Time-aware filtered ranks of the gold subject and object (extension of the reference API; the setting of RE-GCN, xERTE,
+    TITer): evaluate_filter (model.py:384-419) with the filter sets restricted to the facts that carry the query's own
+    timestamp.  Same mechanism -- sigmoid(score), the other known completions set to 0 --, so the time-aware set being a
+    subset of the time-agnostic one gives rank_filtered <= rank_time_filtered.  This is the written definition and the
+    sequential baseline of evaluate_all_batch / evaluate_all_stream."""
+    s, r, o, t = (_as_int(triplet[k]) for k in range(4))
+    loss, sub_pred, ob_pred = self.predict(triplet, s_hist, o_hist, global_model)
+    obj_known, sub_known = _time_aware_ids(all_triplets, s, r, o, t)
+    rank_ob = _rank(ob_pred.clone(), o, torch.as_tensor(obj_known).to(ob_pred.device).long())
+    rank_sub = _rank(sub_pred.clone(), s, torch.as_tensor(sub_known).to(sub_pred.device).long())
+    return np.array([rank_sub, rank_ob]), loss
+
+
 def _host_quads(triplets):
     tr = triplets.detach().cpu().numpy() if isinstance(triplets, torch.Tensor) else np.asarray(triplets)
     return tr.astype(np.int64).reshape(-1, 4)
@@ -1158,11 +1178,39 @@ def _evaluate_batch(self, triplets, s_hist, o_hist, global_model):
     return _device_ranks(self, _host_quads(triplets), s_hist, o_hist, global_model, None)
 
 
-def _stream_groups(total_data, s_history, o_history, max_batch, evaluate):
+SETTINGS = ('raw', 'filtered', 'time_filtered')          # the metric settings of evaluate_all_batch, in renet_rank_rows3's order
+
+
+def _evaluate_all_batch(self, triplets, s_hist, o_hist, global_model, all_triplets):
+    """The raw (evaluate), filtered (evaluate_filter) and time-aware filtered (evaluate_time_filter) ranks of the n quadruples
+    of ONE timestamp from one predict_batch and one renet_rank_rows3 launch per direction (extension of the reference API):
+    returns ({'raw': r, 'filtered': r, 'time_filtered': r}, loss[n]), every r float64 [n, 2] = (rank_sub, rank_ob).  A pass
+    is not repeatable in place (predict_batch advances the inference state), and the scores are what a pass costs: the
+    three settings are one read of them.  Always on the device (whatever device_rank says), the filter lists addressed in
+    place in the resident FilterIndex tables."""
+    tr = _host_quads(triplets)
+    index = FI.filter_index_for(self, all_triplets)
+    own_loss = self.reference_shadowing                    # as in _device_ranks: predict_batch computes that loss
+    loss, sub_pred, ob_pred = self.predict_batch(tr, s_hist, o_hist, global_model, want_loss=own_loss)
+    dev = ob_pred.device
+    s, r, o, t = tr[:, 0], tr[:, 1], tr[:, 2], tr[:, 3]
+    label = torch.from_numpy(np.stack((s, o)).astype(np.int32)).to(dev)
+    counts = []
+    for side, pred, lab, key in (('s', sub_pred, label[0], o), ('o', ob_pred, label[1], s)):
+        lists = index.ranges_both(side, np.stack((key, r, t), axis=1), dev)
+        cnt, ls = K.rank_rows3(pred, lab, *lists, want_loss=not own_loss)
+        counts.append(cnt)
+        if not own_loss:
+            loss = ls if loss is None else loss + ls
+    c = torch.stack(counts, dim=2).cpu().numpy().astype(np.float64)                # [6, n, 2]: (greater, equal) per setting
+    return {name: c[2 * k] + (c[2 * k + 1] - 1.0) / 2 + 1 for k, name in enumerate(SETTINGS)}, loss
+
+
+def _stream_groups(total_data, s_history, o_history, max_batch, evaluate, width=2):
     """A time-ordered stream in groups of consecutive quadruples of one timestamp (at most max_batch each), every group
-    through evaluate(quadruples, s_hist, o_hist) -> (ranks[len, 2], loss[len])."""
+    through evaluate(quadruples, s_hist, o_hist) -> (ranks[len, width], loss[len])."""
     tr = _host_quads(total_data)
-    ranks, losses = np.zeros((len(tr), 2)), np.zeros(len(tr), dtype=np.float32)
+    ranks, losses = np.zeros((len(tr), width)), np.zeros(len(tr), dtype=np.float32)
     cut = np.concatenate(([0], np.nonzero(np.diff(tr[:, 3]))[0] + 1, [len(tr)]))
     for a, b in zip(cut[:-1], cut[1:]):
         for c in range(a, b, max_batch):
@@ -1188,6 +1236,17 @@ def _evaluate_stream(self, total_data, s_history, o_history, global_model, max_b
                           lambda q, sh, oh: self.evaluate_batch(q, sh, oh, global_model))
 
 
+def _evaluate_all_stream(self, total_data, s_history, o_history, global_model, all_triplets, max_batch=4096):
+    """evaluate_stream, evaluate_filter_stream and the time-aware filtered setting from ONE pass over a time-ordered test
+    stream (evaluate_all_batch per group; extension of the reference API).  Returns ({'raw': r, 'filtered': r,
+    'time_filtered': r}, loss[len]), every r float64 [len, 2] as utils.rank_metrics takes it."""
+    def group(q, sh, oh):
+        rk, ls = self.evaluate_all_batch(q, sh, oh, global_model, all_triplets)
+        return np.concatenate([rk[name] for name in SETTINGS], axis=1), ls
+    ranks, loss = _stream_groups(total_data, s_history, o_history, max_batch, group, width=2 * len(SETTINGS))
+    return {name: np.ascontiguousarray(ranks[:, 2 * k:2 * k + 2]) for k, name in enumerate(SETTINGS)}, loss
+
+
 RENet.init_history = _init_history
 RENet.update_cache = _update_cache
 RENet.pred_r_rank2 = _moded(_pred_r_rank2)
@@ -1209,3 +1268,6 @@ RENet.evaluate_filter_batch = _moded(_evaluate_filter_batch)
 RENet.evaluate_filter_stream = _moded(_evaluate_filter_stream)
 RENet.evaluate_batch = _moded(_evaluate_batch)
 RENet.evaluate_stream = _moded(_evaluate_stream)
+RENet.evaluate_time_filter = _moded(_evaluate_time_filter)
+RENet.evaluate_all_batch = _moded(_evaluate_all_batch)
+RENet.evaluate_all_stream = _moded(_evaluate_all_stream)

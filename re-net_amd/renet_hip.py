@@ -145,6 +145,8 @@ _SIGNATURES = {
     'renet_joint_softmax': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     'renet_rank_rows': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                 c_void_p, c_void_p]),
+    'renet_rank_rows3': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                 c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     'renet_topk_workspace': (c_size_t, [c_int]),
     'renet_topk_positive': (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
                                     c_void_p]),
@@ -1427,6 +1429,36 @@ def rank_rows(scores, label, filt_ptr=None, filt_col=None, filtered=True, want_l
                                  _i32(filt_ptr), _i32(filt_col), int(bool(filtered)), counts[0].data_ptr(),
                                  counts[1].data_ptr(), _f32(row_loss), _stream()), 'rank_rows')
     _timed_end(t0, 'rank_rows', nbytes=float(n * c * 4))
+    return counts, row_loss
+
+
+def rank_rows3(scores, label, cols_a, start_a, count_a, cols_t, start_t, count_t, want_loss=True):
+    """renet_rank_rows3 on scores [n, C] (fp32, unit inner stride; not written) for the gold columns label [n] (int32):
+    -> (counts, row_loss): counts is int32 [6, n] = raw (greater, equal), filtered (greater, equal), time_filtered (greater,
+    equal) -- rank = greater + (equal - 1) / 2 + 1 each -- from ONE read of the scores; row_loss as rank_rows gives it.
+    (cols_a, start_a [n], count_a [n]) is the time-agnostic filter list of every row as a range of the resident column
+    table cols_a (filter_index.FilterIndex.ranges; int32), (cols_t, start_t, count_t) the time-aware one; a list given as
+    three Nones (or an empty table) leaves that setting unfiltered: the sigmoid counts alone."""
+    if not (scores.is_cuda and scores.dtype == torch.float32 and scores.dim() == 2):
+        raise RenetHipError('rank_rows3 needs a 2-D float32 device tensor')
+    n, c = scores.shape
+    lists = []
+    for cols, start, count in ((cols_a, start_a, count_a), (cols_t, start_t, count_t)):
+        if cols is None and start is None and count is None:
+            lists += [None, None, None, 0]
+            continue
+        if cols is None or start is None or count is None or start.numel() != n or count.numel() != n:
+            raise RenetHipError('rank_rows3: a filter list is (cols, start [n], count [n])')
+        # (an empty table has no storage to point at: no list)
+        lists += [_i32(cols), _i32(start), _i32(count), cols.numel()] if cols.numel() else [None, None, None, 0]
+    if label.numel() != n:
+        raise RenetHipError('rank_rows3: shape mismatch')
+    counts = torch.empty(6, n, device=scores.device, dtype=torch.int32)
+    row_loss = torch.empty(n, device=scores.device, dtype=torch.float32) if want_loss else None
+    t0 = _timed()
+    _check(lib().renet_rank_rows3(scores.data_ptr(), max(_ld(scores), c) if n == 1 else _ld(scores), n, c, _i32(label),
+                                  *lists, counts.data_ptr(), _f32(row_loss), _stream()), 'rank_rows3')
+    _timed_end(t0, 'rank_rows3', nbytes=float(n * c * 4))
     return counts, row_loss
 
 

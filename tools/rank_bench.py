@@ -5,7 +5,12 @@ tail (model._known_pairs x 2, uploads, model._rank_rows x 2, softmax_ce x 2) aga
 GPU only.
 
     python tools/rank_bench.py tail [n] [C] [n_facts] [reps]        medians of `reps` alternating repetitions, JSON line
+    python tools/rank_bench.py tail3 [n] [C] [n_facts] [reps]       the same matrix: one renet_rank_rows3 launch per direction
+                                                                     with range lookups (raw + filtered + time-aware) against
+                                                                     the two one-setting device tails run back to back
     python tools/rank_bench.py stream [shape] [n_timestamps] [reps]
+    python tools/rank_bench.py stream3 [shape] [n_timestamps] [reps]   evaluate_all_stream against evaluate_stream and
+                                                                     evaluate_filter_stream (device_rank on), each timed alone
     python tools/rank_bench.py grouped [shape] [n_timestamps] [reps]   evaluate_filter_stream (device_rank on) with
                                                                      RGCNAggregator.grouped_device_builder off and on
 """
@@ -35,19 +40,24 @@ def _wall(fn):
     return time.perf_counter() - t0, out
 
 
-def tail(n=4096, C=23033, n_facts=400000, reps=7):
-    dev = torch.device('cuda:0')
+def _tail_matrix(n, C, n_facts, dev):
+    """The score matrices, facts and quadruples of the tail modes -> (facts, quads, sub_pred, ob_pred, total)."""
     rng = np.random.RandomState(3)
     num_rels = 256
     facts = np.stack((rng.randint(0, C, n_facts), rng.randint(0, num_rels, n_facts), rng.randint(0, C, n_facts),
                       rng.randint(0, 300, n_facts) * 24), axis=1).astype(np.int64)
     facts = np.concatenate((facts, facts[: n_facts // 2] + np.array([0, 0, 0, 24])))     # repeated at another time
     quads = facts[rng.choice(len(facts), n, replace=False)]
-    s, r, o = quads[:, 0], quads[:, 1], quads[:, 2]
     g = torch.Generator().manual_seed(1)
     ob_pred = (torch.randn(n, C, generator=g) * 4).to(dev)
     sub_pred = (torch.randn(n, C, generator=g) * 4).to(dev)
-    total = torch.from_numpy(facts).to(dev)
+    return facts, quads, sub_pred, ob_pred, torch.from_numpy(facts).to(dev)
+
+
+def tail(n=4096, C=23033, n_facts=400000, reps=7):
+    dev = torch.device('cuda:0')
+    facts, quads, sub_pred, ob_pred, total = _tail_matrix(n, C, n_facts, dev)
+    s, r, o = quads[:, 0], quads[:, 1], quads[:, 2]
     t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
 
     def old_tail():
@@ -97,6 +107,109 @@ def tail(n=4096, C=23033, n_facts=400000, reps=7):
                       'new_tail_ms': [round(x * 1e3, 3) for x in sorted(tnew)], 'new_tail_median_ms': float(np.median(tnew)) * 1e3,
                       'index_build_once_ms': t_build * 1e3, 'kernel_median_ms': t_k * 1e3,
                       'kernel_bytes_per_s': nbytes / t_k, 'kernel_share_of_hbm_peak': nbytes / t_k / PEAK_HBM}))
+
+
+def _event_ms(fn, reps):
+    """Median device time of fn (events) over reps launches after 3 warm-up ones, in ms."""
+    ev = []
+    for _ in range(3 + reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        ev.append(e0.elapsed_time(e1))
+    return float(np.median(ev[3:]))
+
+
+def tail3(n=4096, C=23033, n_facts=400000, reps=7):
+    """After the scores of one group, both directions: the two one-setting device tails back to back (what
+    evaluate_stream + evaluate_filter_stream with device_rank on run per group: raw counts, then lookup + filtered counts,
+    each with its label upload, loss and copy of the counts) against the one three-setting tail of evaluate_all_batch."""
+    dev = torch.device('cuda:0')
+    facts, quads, sub_pred, ob_pred, total = _tail_matrix(n, C, n_facts, dev)
+    s, r, o, tq = quads[:, 0], quads[:, 1], quads[:, 2], quads[:, 3]
+    index = FI.FilterIndex(total)
+    sides = (('s', sub_pred, 0, o), ('o', ob_pred, 1, s))
+    rank = lambda counts: (lambda c: c[0] + (c[1] - 1.0) / 2 + 1)(torch.stack(counts, dim=2).cpu().numpy().astype(np.float64))
+
+    def one_setting(filtered):
+        label = torch.from_numpy(np.stack((s, o)).astype(np.int32)).to(dev)
+        counts, loss = [], None
+        for side, pred, k, key in sides:
+            ptr, col = index.lookup(side, np.stack((key, r), axis=1), dev) if filtered else (None, None)
+            cnt, ls = K.rank_rows(pred, label[k], ptr, col, filtered=filtered)
+            counts.append(cnt)
+            loss = ls if loss is None else loss + ls
+        return rank(counts), loss
+
+    def two_tails():
+        return one_setting(False), one_setting(True)
+
+    def one_tail():
+        label = torch.from_numpy(np.stack((s, o)).astype(np.int32)).to(dev)
+        counts, loss = [], None
+        for side, pred, k, key in sides:
+            lists = index.ranges_both(side, np.stack((key, r, tq), axis=1), dev)
+            cnt, ls = K.rank_rows3(pred, label[k], *lists)
+            counts.append(cnt)
+            loss = ls if loss is None else loss + ls
+        c = torch.stack(counts, dim=2).cpu().numpy().astype(np.float64)
+        return [c[2 * k] + (c[2 * k + 1] - 1.0) / 2 + 1 for k in range(3)], loss
+
+    ((raw, l_raw), (filt, _)), (three, l3) = two_tails(), one_tail()       # warm-up (the timed tables are built here)
+    told, tnew = [], []
+    for _ in range(reps):                                       # alternating: both sides see the same machine state
+        told.append(_wall(two_tails)[0])
+        tnew.append(_wall(one_tail)[0])
+    lab = torch.from_numpy(o.astype(np.int32)).to(dev)
+    ptr, col = index.lookup('o', np.stack((s, r), axis=1), dev)
+    lists = index.ranges_both('o', np.stack((s, r, tq), axis=1), dev)
+    k_raw = _event_ms(lambda: K.rank_rows(ob_pred, lab, filtered=False), reps)
+    k_filt = _event_ms(lambda: K.rank_rows(ob_pred, lab, ptr, col, filtered=True), reps)
+    k_three = _event_ms(lambda: K.rank_rows3(ob_pred, lab, *lists), reps)
+    nbytes = float(n) * C * 4
+    print(json.dumps({'n': n, 'C': C, 'facts': int(len(facts)), 'reps': reps,
+                      'filter_nnz_per_side': int(ptr[-1]), 'time_aware_nnz_per_side': int(lists[5].sum()),
+                      'raw_identical': bool(np.array_equal(raw, three[0])), 'filtered_identical': bool(np.array_equal(filt, three[1])),
+                      'filtered_le_time_filtered': bool(np.all(three[1] <= three[2])),
+                      'rows_time_filtered_differs': int((three[1] != three[2]).any(axis=1).sum()),
+                      'loss_bit_equal': bool(torch.equal(l_raw, l3)),
+                      'two_tails_ms': [round(x * 1e3, 3) for x in sorted(told)], 'two_tails_median_ms': float(np.median(told)) * 1e3,
+                      'one_tail_ms': [round(x * 1e3, 3) for x in sorted(tnew)], 'one_tail_median_ms': float(np.median(tnew)) * 1e3,
+                      'kernel_raw_ms': k_raw, 'kernel_filtered_ms': k_filt, 'kernel_three_ms': k_three,
+                      'kernel_three_bytes_per_s': nbytes / (k_three * 1e-3),
+                      'kernel_three_share_of_hbm_peak': nbytes / (k_three * 1e-3) / PEAK_HBM}))
+
+
+def stream3(shape='ICEWS18', n_t=3, reps=3):
+    """evaluate_stream, evaluate_filter_stream (device_rank on) and evaluate_all_stream over the same stream, a fresh model
+    per pass, the three alternating; repetition 0 warms up all of them."""
+    import infer_bench
+    dev = torch.device('cuda:0')
+    runs = {'raw': lambda net, te, tes, teo, gnet, total: net.evaluate_stream(te, tes, teo, gnet),
+            'filtered': lambda net, te, tes, teo, gnet, total: net.evaluate_filter_stream(te, tes, teo, gnet, total),
+            'all': lambda net, te, tes, teo, gnet, total: net.evaluate_all_stream(te, tes, teo, gnet, total)}
+    times, ranks = {k: [] for k in runs}, {}
+    for rep in range(reps + 1):
+        for name, run in runs.items():
+            net, gnet, te, tes, teo, total = infer_bench.setup(shape, n_t, 200, dev)
+            net.device_rank = True
+            with torch.no_grad():
+                dt, (rk, _) = _wall(lambda: run(net, te, tes, teo, gnet, total))
+            if rep:
+                times[name].append(dt)
+            ranks[name] = rk
+    n = len(ranks['raw'])
+    med = {k: float(np.median(v)) for k, v in times.items()}
+    print(json.dumps({'shape': shape, 'timestamps': n_t, 'quadruples': n, 'reps': reps,
+                      'raw_identical': bool(np.array_equal(ranks['raw'], ranks['all']['raw'])),
+                      'filtered_identical': bool(np.array_equal(ranks['filtered'], ranks['all']['filtered'])),
+                      'rows_time_filtered_differs': int((ranks['all']['filtered'] != ranks['all']['time_filtered']).any(axis=1).sum()),
+                      'raw_s': [round(x, 4) for x in times['raw']], 'filtered_s': [round(x, 4) for x in times['filtered']],
+                      'all_s': [round(x, 4) for x in times['all']],
+                      'raw_median_s': med['raw'], 'filtered_median_s': med['filtered'],
+                      'two_passes_median_s': med['raw'] + med['filtered'], 'all_median_s': med['all']}))
 
 
 def stream(shape='ICEWS18', n_t=3, reps=2):
@@ -192,6 +305,10 @@ if __name__ == '__main__':
     a = sys.argv[1:]
     if a and a[0] == 'grouped':
         grouped(a[1] if len(a) > 1 else 'ICEWS18', int(a[2]) if len(a) > 2 else 3, int(a[3]) if len(a) > 3 else 2)
+    elif a and a[0] == 'stream3':
+        stream3(a[1] if len(a) > 1 else 'ICEWS18', int(a[2]) if len(a) > 2 else 3, int(a[3]) if len(a) > 3 else 3)
+    elif a and a[0] == 'tail3':
+        tail3(*[int(x) for x in a[1:5]])
     elif a and a[0] == 'stream':
         stream(a[1] if len(a) > 1 else 'ICEWS18', int(a[2]) if len(a) > 2 else 3, int(a[3]) if len(a) > 3 else 2)
     else:
