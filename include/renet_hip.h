@@ -597,6 +597,28 @@ int renet_rank_rows3(const float* scores, int ld, int n, int C, const int32_t* l
                      const int32_t* start_t, const int32_t* count_t, int len_t, int32_t* counts, float* row_loss,
                      void* stream);
 
+/* Ranked, filtered top-k predictions (not in the reference): ONE read of every row of scores [n, C] (row stride ld; never
+ * written) gives the k best CANDIDATES of row i: all columns minus those listed in cols[start[i] .. start[i] + count[i])
+ * (a range of a resident column table of len entries, cut to the table; count <= 0: empty; every column at most once per row;
+ * listed columns outside [0, C) ignored -- the list form of renet_rank_rows3), except that a listed column equal to keep[i]
+ * stays a candidate (keep NULL, or an entry outside [0, C): nothing is exempt).  All three list pointers NULL: no list.
+ *   out_idx [n, k], out_val [n, k] : the candidates by score descending, then column ascending (float comparison: -0.0 and
+ *                                    +0.0 tie; ties at the k-th value go to the lower columns: the result is deterministic);
+ *                                    out_val holds the scores themselves, bit for bit (a -0.0 as +0.0).
+ *   out_n [n]                      : min(k, number of candidates); the slots from out_n[i] on hold index -1, value -inf,
+ *                                    logp -inf.
+ *   out_logp [n, k]                : out_val - logsumexp(scores[i, 0 .. C)) over ALL columns, listed ones included (the
+ *                                    model's own log-probability: the filter removes candidates, not mass), the logsumexp
+ *                                    online in fp64 as for row_loss above, one rounding; NULL: not computed.
+ * Scores are finite or -inf: a -inf score is an ordinary candidate that sorts last (logp -inf), distinct from a filtered
+ * column.  A NaN (ranked below -inf) or +inf gives no meaningful order or logp, but never an index outside [-1, C).
+ * 1 <= k <= 1024 (k may exceed C); C <= 32768 (the row is staged in LDS), beyond that RENET_ERR_UNSUPPORTED, before any
+ * launch.  RENET_ERR_BADARG for n < 0, C < 1, ld < C, k out of range, a negative len, a list with only some of its three
+ * pointers or a missing output array; n == 0 is a no-op. */
+int renet_topk_rows(const float* scores, int ld, int n, int C, int k, const int32_t* cols, const int32_t* start,
+                    const int32_t* count, int len, const int32_t* keep, int32_t* out_idx, float* out_val, float* out_logp,
+                    int32_t* out_n, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * DEVICE batch-graph builder for the merged training batch (both directions of train.py:136-137 as one batch of 2B
  * sequences: graph.build_batch_both; replaces utils.py:209-244 + 115-131 + dgl.batch and this library's own HOST

@@ -1211,13 +1211,18 @@ def _stream_groups(total_data, s_history, o_history, max_batch, evaluate, width=
     through evaluate(quadruples, s_hist, o_hist) -> (ranks[len, width], loss[len])."""
     tr = _host_quads(total_data)
     ranks, losses = np.zeros((len(tr), width)), np.zeros(len(tr), dtype=np.float32)
+    for c, d in _stream_cuts(tr, max_batch):
+        rk, ls = evaluate(tr[c:d], (s_history[0][c:d], s_history[1][c:d]), (o_history[0][c:d], o_history[1][c:d]))
+        ranks[c:d], losses[c:d] = rk, ls.cpu().numpy()
+    return ranks, losses
+
+
+def _stream_cuts(tr, max_batch):
+    """The groups [c, d) of a time-ordered stream: consecutive quadruples of one timestamp, at most max_batch each."""
     cut = np.concatenate(([0], np.nonzero(np.diff(tr[:, 3]))[0] + 1, [len(tr)]))
     for a, b in zip(cut[:-1], cut[1:]):
         for c in range(a, b, max_batch):
-            d = min(b, c + max_batch)
-            rk, ls = evaluate(tr[c:d], (s_history[0][c:d], s_history[1][c:d]), (o_history[0][c:d], o_history[1][c:d]))
-            ranks[c:d], losses[c:d] = rk, ls.cpu().numpy()
-    return ranks, losses
+            yield c, min(b, c + max_batch)
 
 
 def _evaluate_filter_stream(self, total_data, s_history, o_history, global_model, all_triplets, max_batch=4096):
@@ -1247,6 +1252,54 @@ def _evaluate_all_stream(self, total_data, s_history, o_history, global_model, a
     return {name: np.ascontiguousarray(ranks[:, 2 * k:2 * k + 2]) for k, name in enumerate(SETTINGS)}, loss
 
 
+def _predict_topk_batch(self, triplets, s_hist, o_hist, global_model, k=10, all_triplets=None, setting='raw',
+                        keep_gold=False):
+    """The k best-ranked subjects of (?, r, o, t) and objects of (s, r, ?, t) for the n quadruples of ONE timestamp, from one
+    predict_batch and one renet_topk_rows launch per direction (csrc/topk_rows.hip; extension of the reference API): returns
+    {'sub': (idx, score, logp, n_valid), 'ob': (...)} as device tensors, row i belonging to triplets[i] -- idx int32 [n, k] by
+    score descending, then entity id ascending, score and logp (log-softmax over ALL entities) beside it, n_valid [n] the
+    number of filled slots (the rest: idx -1, -inf).  setting (one of SETTINGS) says which known completions are no
+    candidates: 'raw' none, 'filtered' those known at any time, 'time_filtered' those known at the query's own timestamp
+    (the lists addressed in place in the resident FilterIndex tables of all_triplets).  keep_gold=True leaves the quadruple's
+    own entity in (an evaluator reads hits@k off the list); keep_gold=False removes it when it is a known fact (a server
+    offers only what is new).  Like every evaluation pass, a call advances the inference state."""
+    if setting not in SETTINGS:
+        raise ValueError('setting must be one of %s, not %r' % (', '.join(SETTINGS), setting))
+    if setting != 'raw' and all_triplets is None:
+        raise ValueError("setting %r needs all_triplets (the known facts)" % setting)
+    tr = _host_quads(triplets)
+    index = FI.filter_index_for(self, all_triplets) if setting != 'raw' else None
+    # the keys and the gold entities are the rows' own, also under reference_shadowing (as the ranks of _device_ranks are)
+    _, sub_pred, ob_pred = self.predict_batch(tr, s_hist, o_hist, global_model, want_loss=False)
+    dev = ob_pred.device
+    s, r, o, t = tr[:, 0], tr[:, 1], tr[:, 2], tr[:, 3]
+    gold = torch.from_numpy(np.stack((s, o)).astype(np.int32)).to(dev) if keep_gold else (None, None)
+    out = {}
+    for name, side, pred, keep, key in (('sub', 's', sub_pred, gold[0], o), ('ob', 'o', ob_pred, gold[1], s)):
+        lists = (None, None, None)
+        if index is not None:
+            lists = index.ranges(side, np.stack((key, r, t) if setting == 'time_filtered' else (key, r), axis=1), dev)
+        out[name] = K.topk_rows(pred, k, *lists, keep=keep)
+    return out
+
+
+def _predict_topk_stream(self, total_data, s_history, o_history, global_model, k=10, all_triplets=None, setting='raw',
+                         keep_gold=False, max_batch=4096):
+    """predict_topk_batch for a whole time-ordered test stream, in the per-timestamp groups of evaluate_stream.  Returns
+    host arrays {'sub': (idx [len, k], score [len, k], logp [len, k], n_valid [len]), 'ob': (...)}."""
+    tr = _host_quads(total_data)
+    n = len(tr)
+    res = {name: (np.full((n, k), -1, dtype=np.int32), np.full((n, k), -np.inf, dtype=np.float32),
+                  np.full((n, k), -np.inf, dtype=np.float32), np.zeros(n, dtype=np.int32)) for name in ('sub', 'ob')}
+    for c, d in _stream_cuts(tr, max_batch):
+        got = self.predict_topk_batch(tr[c:d], (s_history[0][c:d], s_history[1][c:d]), (o_history[0][c:d], o_history[1][c:d]),
+                                      global_model, k, all_triplets, setting, keep_gold)
+        for name, parts in got.items():
+            for dst, src in zip(res[name], parts):
+                dst[c:d] = src.cpu().numpy()
+    return res
+
+
 RENet.init_history = _init_history
 RENet.update_cache = _update_cache
 RENet.pred_r_rank2 = _moded(_pred_r_rank2)
@@ -1271,3 +1324,5 @@ RENet.evaluate_stream = _moded(_evaluate_stream)
 RENet.evaluate_time_filter = _moded(_evaluate_time_filter)
 RENet.evaluate_all_batch = _moded(_evaluate_all_batch)
 RENet.evaluate_all_stream = _moded(_evaluate_all_stream)
+RENet.predict_topk_batch = _moded(_predict_topk_batch)
+RENet.predict_topk_stream = _moded(_predict_topk_stream)

@@ -147,6 +147,8 @@ _SIGNATURES = {
                                 c_void_p, c_void_p]),
     'renet_rank_rows3': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                  c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    'renet_topk_rows': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'renet_topk_workspace': (c_size_t, [c_int]),
     'renet_topk_positive': (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
                                     c_void_p]),
@@ -1460,6 +1462,37 @@ def rank_rows3(scores, label, cols_a, start_a, count_a, cols_t, start_t, count_t
                                   *lists, counts.data_ptr(), _f32(row_loss), _stream()), 'rank_rows3')
     _timed_end(t0, 'rank_rows3', nbytes=float(n * c * 4))
     return counts, row_loss
+
+
+def topk_rows(scores, k, cols=None, start=None, count=None, keep=None, want_logp=True):
+    """renet_topk_rows on scores [n, C] (fp32, unit inner stride; not written): the k best candidates of every row from ONE
+    read of the scores -> (idx int32 [n, k], val [n, k], logp [n, k] or None, n_valid int32 [n]), by score descending, then
+    column ascending (deterministic).  The candidates of row i are all columns minus cols[start[i] : start[i] + count[i]] (a
+    range of a resident column table, filter_index.FilterIndex.ranges; int32), a listed column equal to keep[i] (int32 [n])
+    staying in; three Nones (or an empty table): no list.  logp = val - logsumexp(whole row), listed columns included.
+    n_valid = min(k, candidates); the slots behind it hold idx -1, val -inf, logp -inf.  1 <= k <= 1024, C <= 32768."""
+    if not (scores.is_cuda and scores.dtype == torch.float32 and scores.dim() == 2 and scores.stride(1) == 1):
+        raise RenetHipError('topk_rows needs a 2-D float32 device tensor with unit inner stride')
+    n, c = scores.shape
+    if cols is None and start is None and count is None:
+        lists = [None, None, None, 0]
+    elif cols is None or start is None or count is None or start.numel() != n or count.numel() != n:
+        raise RenetHipError('topk_rows: a filter list is (cols, start [n], count [n])')
+    else:                               # (an empty table has no storage to point at: no list)
+        lists = [_i32(cols), _i32(start), _i32(count), cols.numel()] if cols.numel() else [None, None, None, 0]
+    if keep is not None and keep.numel() != n:
+        raise RenetHipError('topk_rows: shape mismatch')
+    k = int(k)
+    idx = torch.empty(n, k, device=scores.device, dtype=torch.int32)
+    val = torch.empty(n, k, device=scores.device, dtype=torch.float32)
+    logp = torch.empty(n, k, device=scores.device, dtype=torch.float32) if want_logp else None
+    n_valid = torch.empty(n, device=scores.device, dtype=torch.int32)
+    t0 = _timed()
+    _check(lib().renet_topk_rows(scores.data_ptr(), max(_ld(scores), c) if n == 1 else _ld(scores), n, c, k, *lists,
+                                 _i32(keep), idx.data_ptr(), val.data_ptr(), _f32(logp), n_valid.data_ptr(), _stream()),
+           'topk_rows')
+    _timed_end(t0, 'topk_rows', nbytes=float(n * c * 4))
+    return idx, val, logp, n_valid
 
 
 def joint_softmax(logits, num_rels, logits_r, prob_e):

@@ -8,6 +8,10 @@ GPU only.
     python tools/rank_bench.py tail3 [n] [C] [n_facts] [reps]       the same matrix: one renet_rank_rows3 launch per direction
                                                                      with range lookups (raw + filtered + time-aware) against
                                                                      the two one-setting device tails run back to back
+    python tools/rank_bench.py topk [n] [C] [k] [reps]              renet_topk_rows with the filter lists of the same matrix
+                                                                     (one launch: filtered, sorted top-k and logp) against
+                                                                     the torch formulation (clone, scatter of -inf,
+                                                                     log_softmax, topk), device events, alternating
     python tools/rank_bench.py stream [shape] [n_timestamps] [reps]
     python tools/rank_bench.py stream3 [shape] [n_timestamps] [reps]   evaluate_all_stream against evaluate_stream and
                                                                      evaluate_filter_stream (device_rank on), each timed alone
@@ -30,6 +34,7 @@ import model as M
 import renet_hip as K
 
 PEAK_HBM = 8.0e12                 # bytes/s, MI355X
+MEASURED_HBM = 6.29e12            # bytes/s a float4 copy reaches: the floor of a one-pass kernel is its bytes over this
 
 
 def _wall(fn):
@@ -182,6 +187,69 @@ def tail3(n=4096, C=23033, n_facts=400000, reps=7):
                       'kernel_three_share_of_hbm_peak': nbytes / (k_three * 1e-3) / PEAK_HBM}))
 
 
+def topk(n=4096, C=23033, k=10, reps=20, n_facts=400000, inner=10):
+    """The k best objects of (s, r, ?, t) outside the known ones, for every row of the tail modes' object score matrix:
+    K.topk_rows with the time-agnostic lists addressed in the resident table, against what a user writes in torch on the
+    same device matrix (the listed pairs already on the device).  Every repetition times `inner` back-to-back calls of one
+    side with device events, then of the other; 3 warm-up repetitions; median, minimum and maximum per call."""
+    dev = torch.device('cuda:0')
+    facts, quads, _, ob_pred, total = _tail_matrix(n, C, n_facts, dev)
+    s, r = quads[:, 0], quads[:, 1]
+    keys = np.stack((s, r), axis=1)
+    lists = FI.FilterIndex(total).ranges('o', keys, dev)
+    rows, cols = (torch.from_numpy(x).to(dev) for x in M._known_pairs(total, (0, 1), 2, keys))
+
+    def kernel():
+        return K.topk_rows(ob_pred, k, *lists)
+
+    def kernel_no_logp():                                       # what the fp64 logsumexp of the sweep costs
+        return K.topk_rows(ob_pred, k, *lists, want_logp=False)
+
+    lab = torch.from_numpy(quads[:, 2].astype(np.int32)).to(dev)
+
+    def rank_kernel():                                          # renet_rank_rows with its loss: the same sweep and logsumexp
+        return K.rank_rows(ob_pred, lab, filtered=False, want_loss=True)
+
+    def torch_path():
+        x = ob_pred.clone()
+        x[rows, cols] = float('-inf')
+        val, idx = torch.topk(torch.log_softmax(x, dim=1), k, dim=1, sorted=True)
+        return idx, val
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(inner):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / inner
+
+    (idx, val, logp, nv), (tidx, _) = kernel(), torch_path()
+    # the same entities wherever the scores are distinct (torch leaves the order of ties open; its logp is renormalised
+    # over the candidates, so only the indices are compared)
+    same_rows = int((idx.long() == tidx).all(dim=1).sum())
+    tk, tt, tn, tr = [], [], [], []
+    for rep in range(3 + reps):                                 # alternating: every side sees the same machine state
+        a, b, c, d = timed(kernel), timed(torch_path), timed(kernel_no_logp), timed(rank_kernel)
+        if rep >= 3:
+            tk.append(a)
+            tt.append(b)
+            tn.append(c)
+            tr.append(d)
+    nbytes = float(n) * C * 4
+    floor_ms = nbytes / MEASURED_HBM * 1e3
+    stat = lambda v: {'median_ms': float(np.median(v)), 'min_ms': float(np.min(v)), 'max_ms': float(np.max(v))}
+    print(json.dumps({'n': n, 'C': C, 'k': k, 'reps': reps, 'calls_per_rep': inner, 'facts': int(len(facts)),
+                      'filter_nnz': int(lists[2].sum()), 'n_valid_min': int(nv.min()),
+                      'rows_with_torch_indices': same_rows, 'kernel': stat(tk), 'torch': stat(tt),
+                      'kernel_without_logp': stat(tn), 'rank_rows_with_loss': stat(tr),
+                      'torch_over_kernel': float(np.median(tt) / np.median(tk)),
+                      'matrix_bytes': nbytes, 'one_hbm_read_ms_at_6.29TBps': floor_ms,
+                      'kernel_over_one_hbm_read': float(np.median(tk) / floor_ms),
+                      'kernel_bytes_per_s': nbytes / (float(np.median(tk)) * 1e-3)}))
+
+
 def stream3(shape='ICEWS18', n_t=3, reps=3):
     """evaluate_stream, evaluate_filter_stream (device_rank on) and evaluate_all_stream over the same stream, a fresh model
     per pass, the three alternating; repetition 0 warms up all of them."""
@@ -309,6 +377,8 @@ if __name__ == '__main__':
         stream3(a[1] if len(a) > 1 else 'ICEWS18', int(a[2]) if len(a) > 2 else 3, int(a[3]) if len(a) > 3 else 3)
     elif a and a[0] == 'tail3':
         tail3(*[int(x) for x in a[1:5]])
+    elif a and a[0] == 'topk':
+        topk(*[int(x) for x in a[1:5]])
     elif a and a[0] == 'stream':
         stream(a[1] if len(a) > 1 else 'ICEWS18', int(a[2]) if len(a) > 2 else 3, int(a[3]) if len(a) > 3 else 2)
     else:
