@@ -163,6 +163,21 @@ class DeviceStore(GraphDeviceStore):
         self.c = sd
 
 
+class ObservedStore(DeviceStore):
+    """The DeviceStore of a whole preprocess.ObservedStream (train, valid and test as one stream: true histories and graphs
+    at every timestamp) with the global-embedding table that belongs to it: `glob` [timestamps, D], rows in ascending time
+    -- the order of the store's glob_times, which glob_row of a batch indexes.  The observed evaluation pass hands `glob`
+    to RENet.finish_prepare_device; the model's own global_emb / glob_table are not involved.  `quads` is the host copy of
+    the stream (labels and filter keys are read from it)."""
+
+    def __init__(self, obs, global_emb, h_dim, device):
+        DeviceStore.__init__(self, obs.allq, obs.hist_s, obs.hist_o, obs.graph_dict, global_emb, obs.num_ent, obs.num_rels,
+                             device)
+        self.obs, self.quads = obs, obs.allq
+        ts = sorted(int(t) for t in global_emb.keys())
+        self.glob = torch.stack([torch.as_tensor(global_emb[t]).detach().reshape(h_dim).float() for t in ts]).to(device)
+
+
 def _cached_store(cache, graph_dict, device, stamp, make):
     """The entry of `cache` for graph_dict on `device`, made by make() when there is none, when the graph store object changed
     (graph.store_for re-creates it when the dict gained timestamps) or when `stamp` did.  Keyed on the dict's identity;
@@ -242,6 +257,7 @@ class ListBatchStore(object):
 
 
 MAX_GROUPED = 4096           # sequences per grouped batch (one workgroup sorts their lengths)
+MAX_BOTH = MAX_GROUPED // 2  # quadruples per merged batch: two sequences each, the same sort
 
 
 class GroupedBatchStore(ListBatchStore):

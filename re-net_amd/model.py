@@ -246,9 +246,11 @@ class RENet(nn.Module):
         import gpu_builder
         return gpu_builder.DeviceBatch(dstore, idx, self.seq_len, stream=stream)
 
-    def finish_prepare_device(self, pending):
+    def finish_prepare_device(self, pending, glob=None):
         """Waits for the pending batch's counts (~256 bytes D2H).  Returns the PreparedBatch, or None if a capacity of the
-        device builder was exceeded (the store's capacities have been raised: call prepare_both_device again)."""
+        device builder was exceeded (the store's capacities have been raised: call prepare_both_device again).
+        glob: the global-embedding matrix that belongs to the pending batch's store (rows in the order of its glob_times);
+        None = the table of this model's own global_emb."""
         if not pending.finalize():
             return None
         g = pending
@@ -257,7 +259,7 @@ class RENet(nn.Module):
         dev = self.ent_embeds.device
         prep = PreparedBatch()
         prep.subject, prep.b, prep.share = None, g.B, 1.0
-        g.glob = self.aggregator.glob_table.get(self.global_emb, self.h_dim, dev).mat
+        g.glob = glob if glob is not None else self.aggregator.glob_table.get(self.global_emb, self.h_dim, dev).mat
         prep.g = g
         prep.perm = None                     # (g.host.perm fetches it on demand)
         prep.s_idx, prep.r_idx, prep.plan_s, prep.plan_r = g.s_sorted, g.r_sorted, g.plan_s, g.plan_r
@@ -1300,6 +1302,214 @@ def _predict_topk_stream(self, total_data, s_history, o_history, global_model, k
     return res
 
 
+# =================================================================================================
+# Observed-history (single-step, ground-truth history) evaluation: at query time t every fact before t is known, the
+# evaluated split's own included -- the protocol under which RE-GCN, xERTE and TITer report the time-aware filter.  No
+# query depends on a model output, so a whole stream goes through the TRAINING path (device-built merged batches that
+# mix timestamps, encoder under no_grad) instead of one generated graph per timestamp.  Nothing here reads or writes the
+# multi-step state above (latest_time, the rolling windows and caches, graph_dict, global_emb, the candidate tables): the
+# stream, its graphs and its global-embedding table live in a preprocess.ObservedStream / gpu_builder.ObservedStore.
+# =================================================================================================
+def _observed_store(obs):
+    """obs: a preprocess.ObservedStream that has been made resident, or the gpu_builder.ObservedStore itself."""
+    store = obs if hasattr(obs, 'glob') else getattr(obs, 'device', None)
+    if store is None or not hasattr(store, 'glob'):
+        raise ValueError('the observed stream is not resident: call obs.resident(model, global_model) first')
+    return store
+
+
+def _observed_launch(self, store, idx):
+    """Enqueues the device builder for the stream positions idx (at most gpu_builder.MAX_BOTH: a merged batch holds two
+    sequences per quadruple, and one workgroup sorts their lengths) -> (idx, the pending gpu_builder.DeviceBatch)."""
+    import gpu_builder
+    if self.training and self.drop_p > 0:
+        raise RuntimeError('the observed evaluation pass runs in eval mode (model.eval())')
+    return idx, gpu_builder.DeviceBatch(store, idx, self.seq_len)
+
+
+def _eval_rows_torch(ent, rel, h_sorted, q_sorted, perm, s, r, o, num_rels):
+    """The GEMM-ready rows of both directions in quadruple order (model.py:89, 98 for subject=True / False):
+    feat_ob[i] = [ent[s_i] | h(seq i) | rel[r_i]], feat_sub[i] = [ent[o_i] | h(seq n + i) | rel[R + r_i]] and the relation
+    head's [ent | q] (q_sorted None: None); h(seq) is the row of h_sorted at the position that perm (sorted position ->
+    sequence) maps to seq.  About eight small launches per batch; a fused copy kernel was measured and left out
+    (profiles/observed_eval.md)."""
+    n = s.numel()
+    h_seq = torch.empty_like(h_sorted)
+    h_seq[perm] = h_sorted
+    es, eo = ent[s], ent[o]
+    feat_ob, feat_sub = torch.cat((es, h_seq[:n], rel[r]), dim=1), torch.cat((eo, h_seq[n:], rel[num_rels + r]), dim=1)
+    if q_sorted is None:
+        return feat_ob, feat_sub, None, None
+    q_seq = torch.empty_like(q_sorted)
+    q_seq[perm] = q_sorted
+    return feat_ob, feat_sub, torch.cat((es, q_seq[:n]), dim=1), torch.cat((eo, q_seq[n:]), dim=1)
+
+
+def _observed_features(self, store, pending, relation=False):
+    """Builder -> encoder -> rows for ONE pending batch of _observed_launch: (feat_ob [n, 3H], feat_sub [n, 3H],
+    featr_ob [n, 2H] or None, featr_sub) in the order of its positions."""
+    import gpu_builder
+    dev, H, R = self.ent_embeds.device, self.h_dim, self.num_rels
+    idx, pend = pending
+    prep = self.finish_prepare_device(pend, glob=store.glob)
+    for _ in range(8):                      # a capacity overflow: finalize() has raised the store's capacities, rebuild
+        if prep is not None:
+            break
+        prep = self.finish_prepare_device(gpu_builder.DeviceBatch(store, idx, self.seq_len), glob=store.glob)
+    if prep is None:
+        raise RuntimeError('device batch builder did not converge on its capacities')
+    g, b2 = prep.g, prep.b
+    if g.S == 0:
+        # every history of the batch is empty (the first timestamp of a stream).  The builder accepts that -- an empty
+        # graph, N = E = S = 0 (tests/test_gpu_builder.py) -- but the encoder kernels would be launched over zero rows:
+        # zero states, as loss_prepared gives a batch without a graph
+        h_sorted = torch.zeros(b2, H, device=dev)
+        q_sorted = h_sorted
+    else:
+        x, xr = self.aggregator.encode(g, self.ent_embeds, self.rel_embeds, reverse=False, _lazy_bf16=True)
+        h_sorted, q_sorted = ops.dual_gru(x, xr, self.encoder, self.encoder_r, prep.step_off, b2)
+        h_sorted, q_sorted = h_sorted.view(b2, H), q_sorted.view(b2, H)           # rows behind the non-empty ones are zero
+    pos = torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int64)).to(dev)
+    s, r, o = (store.t[k][pos].long() for k in ('q_s', 'q_r', 'q_o'))
+    perm = g._v['perm'][:b2].long()                                                 # sorted position -> sequence, on the device
+    return _eval_rows_torch(self.ent_embeds, self.rel_embeds, h_sorted, q_sorted if relation else None, perm, s, r, o, R)
+
+
+def _observed_chunks(self, store, idx, relation=False):
+    """The rows of _observed_features for idx, one ENCODER CHUNK after the other: idx[0 : MAX_BOTH], idx[MAX_BOTH : 2 MAX_BOTH],
+    ... -- each chunk one merged batch graph, the builder of chunk k + 1 enqueued before chunk k is encoded.  As in the
+    reference, the histories of a batch graph are merged per timestamp (utils.py:149-170), so a row depends on which other
+    positions share its chunk: the chunks are a function of idx alone, never of how the scoring is cut."""
+    import gpu_builder
+    step = gpu_builder.MAX_BOTH
+    pending = _observed_launch(self, store, idx[:step])
+    for c in range(0, len(idx), step):
+        ahead = _observed_launch(self, store, idx[c + step:c + 2 * step]) if c + step < len(idx) else None
+        yield _observed_features(self, store, pending, relation)
+        pending = ahead
+
+
+def _observed_cuts(chunks, max_batch):
+    """Regroups the per-chunk rows into scoring batches of max_batch positions (the last one shorter): yields
+    (c, d, rows) for the positions [c, d) of idx."""
+    cat = lambda parts: [None if p[0] is None else p[0] if len(p) == 1 else torch.cat(p) for p in zip(*parts)]
+    held, have, c = [], 0, 0
+    for rows in chunks:
+        held.append(rows)
+        have += rows[0].shape[0]
+        if have < max_batch:
+            continue
+        rows = cat(held)
+        for a in range(0, have - max_batch + 1, max_batch):
+            yield c, c + max_batch, [None if x is None else x[a:a + max_batch] for x in rows]
+            c += max_batch
+        rest = have % max_batch
+        held, have = ([[None if x is None else x[have - rest:] for x in rows]], rest) if rest else ([], 0)
+    if have:
+        yield c, c + have, cat(held)
+
+
+def _observed_positions(store, idx):
+    idx = np.asarray(idx.cpu() if isinstance(idx, torch.Tensor) else idx, dtype=np.int64).reshape(-1)
+    if len(idx) == 0 or idx.min() < 0 or idx.max() >= store.n_quads:
+        raise ValueError('observed pass: positions outside the stream (or none)')
+    return idx
+
+
+def _observed_scores(self, obs, idx):
+    """The scores of the stream positions idx (ONE batch) under observed histories: (sub_pred [n, N_ent], ob_pred
+    [n, N_ent]), ob_pred[i] the logits row that forward(..., subject=True) computes for quadruple idx[i] in eval mode
+    (model.py:82-90) from its TRUE history in the whole stream, sub_pred[i] that of subject=False.  Up to
+    gpu_builder.MAX_BOTH positions are one batch graph, as in forward; more are encoded in chunks of that size
+    (_observed_chunks)."""
+    store = _observed_store(obs)
+    idx = _observed_positions(store, idx)
+    with torch.no_grad():
+        (_, _, (feat_ob, feat_sub, _, _)), = _observed_cuts(_observed_chunks(self, store, idx), len(idx))
+        return _linear_eval(self.linear, feat_sub), _linear_eval(self.linear, feat_ob)
+
+
+def _ranks_of(counts):
+    """counts int [2 k, ...] = (greater, equal) per setting -> k float64 rank arrays (ties averaged, model.py:368-376)."""
+    c = counts.cpu().numpy().astype(np.float64)
+    return [c[2 * k] + (c[2 * k + 1] - 1.0) / 2 + 1 for k in range(len(c) // 2)]
+
+
+def _evaluate_observed(self, obs, idx, all_triplets=None, max_batch=4096, relation=False):
+    """Raw, filtered and time-aware filtered ranks of the stream positions idx under OBSERVED histories (extension of the
+    reference API): ({'raw': r, 'filtered': r, 'time_filtered': r}, loss[len]), every r float64 [len, 2] = (rank_sub,
+    rank_ob) as utils.rank_metrics takes it, loss the sum of the two directions' entity cross-entropies per row.  idx may
+    span any timestamps; scoring batches are cut every max_batch positions, not at timestamp borders.  The cut does not
+    change what is computed: the encoder's batch graphs are chunks of idx of a fixed size (_observed_chunks), so the ranks are
+    those of observed_scores(obs, idx) whatever max_batch is -- it bounds the two [max_batch, N_ent] score matrices.
+    all_triplets: the known
+    facts of the filtered settings (None: the stream itself).  The filter keys (s, r, t) / (o, r, t) are the quadruples'
+    own: every host lookup is done, and uploaded, before the first batch runs, the builder of chunk k + 1 is enqueued before
+    chunk k is encoded, and the counts come back in one copy at the end.  One renet_rank_rows3 launch per direction per
+    batch, as evaluate_all_batch.  A pass is repeatable in place and leaves the multi-step state untouched.
+    relation=True: a third result {'rank': [len, 2], 'loss': [len, 2], 'entity_loss': [len, 2]} -- raw rank and row loss
+    of the gold relation under linear_r (model.py:98-100; the head trained at weight 0.1), column 0 from the subject=False
+    pass ([ent[o] | o_q]), column 1 from subject=True ([ent[s] | s_q]), and the entity loss split the same way."""
+    store = _observed_store(obs)
+    idx = _observed_positions(store, idx)
+    dev, n = self.ent_embeds.device, len(idx)
+    max_batch = max(1, int(max_batch))
+    tr = store.quads[idx]
+    s, r, o, t = tr[:, 0], tr[:, 1], tr[:, 2], tr[:, 3]
+    index = FI.filter_index_for(store, all_triplets if all_triplets is not None else store.quads)
+    lists = np.stack(index.ranges_both_host('s', np.stack((o, r, t), axis=1)) +
+                     index.ranges_both_host('o', np.stack((s, r, t), axis=1)) + (s, o, r)).astype(np.int32)
+    up = torch.from_numpy(lists).to(dev)                                            # [11, n]: ONE upload for the whole pass
+    cols = {side: (index.resident(side, dev), index.resident(side, dev, timed=True)) for side in ('s', 'o')}
+    counts = torch.empty(6, n, 2, device=dev, dtype=torch.int32)
+    ent_loss = torch.empty(n, 2, device=dev)
+    rel_counts = torch.empty(2, n, 2, device=dev, dtype=torch.int32) if relation else None
+    rel_loss = torch.empty(n, 2, device=dev) if relation else None
+    with torch.no_grad():
+        for c, d, (feat_ob, feat_sub, featr_ob, featr_sub) in _observed_cuts(_observed_chunks(self, store, idx, relation), max_batch):
+            for col, side, feat, featr, lab, base in ((0, 's', feat_sub, featr_sub, up[8], 0), (1, 'o', feat_ob, featr_ob, up[9], 4)):
+                pred = _linear_eval(self.linear, feat)
+                cnt, ls = K.rank_rows3(pred, lab[c:d], cols[side][0], up[base][c:d], up[base + 1][c:d],
+                                       cols[side][1], up[base + 2][c:d], up[base + 3][c:d], want_loss=True)
+                counts[:, c:d, col] = cnt
+                ent_loss[c:d, col] = ls
+                if relation:
+                    cnt, ls = K.rank_rows(_linear_eval(self.linear_r, featr), up[10][c:d], filtered=False, want_loss=True)
+                    rel_counts[:, c:d, col] = cnt
+                    rel_loss[c:d, col] = ls
+    ranks = dict(zip(SETTINGS, _ranks_of(counts)))
+    loss = ent_loss.sum(dim=1).cpu().numpy()
+    if not relation:
+        return ranks, loss
+    return ranks, loss, {'rank': _ranks_of(rel_counts)[0], 'loss': rel_loss.cpu().numpy(), 'entity_loss': ent_loss.cpu().numpy()}
+
+
+def _predict_topk_observed(self, obs, idx, k=10, all_triplets=None, setting='raw', keep_gold=False):
+    """predict_topk_batch under observed histories, for the stream positions idx as ONE batch: {'sub': (idx, score, logp,
+    n_valid), 'ob': (...)} as device tensors, the layout and the meaning of setting / keep_gold as there; all_triplets None:
+    the stream itself is the set of known facts."""
+    if setting not in SETTINGS:
+        raise ValueError('setting must be one of %s, not %r' % (', '.join(SETTINGS), setting))
+    store = _observed_store(obs)
+    idx = _observed_positions(store, idx)
+    index = FI.filter_index_for(store, all_triplets if all_triplets is not None else store.quads) if setting != 'raw' else None
+    sub_pred, ob_pred = self.observed_scores(store, idx)
+    dev = ob_pred.device
+    tr = store.quads[idx]
+    s, r, o, t = tr[:, 0], tr[:, 1], tr[:, 2], tr[:, 3]
+    gold = torch.from_numpy(np.stack((s, o)).astype(np.int32)).to(dev) if keep_gold else (None, None)
+    out = {}
+    for name, side, pred, keep, key in (('sub', 's', sub_pred, gold[0], o), ('ob', 'o', ob_pred, gold[1], s)):
+        lists = (None, None, None)
+        if index is not None:
+            lists = index.ranges(side, np.stack((key, r, t) if setting == 'time_filtered' else (key, r), axis=1), dev)
+        out[name] = K.topk_rows(pred, k, *lists, keep=keep)
+    return out
+
+
+RENet.observed_scores = _moded(_observed_scores)
+RENet.evaluate_observed = _moded(_evaluate_observed)
+RENet.predict_topk_observed = _moded(_predict_topk_observed)
 RENet.init_history = _init_history
 RENet.update_cache = _update_cache
 RENet.pred_r_rank2 = _moded(_pred_r_rank2)

@@ -97,6 +97,55 @@ def build_graph_dict(quads, num_rels):
     return {int(t): TimeGraph.from_triples(q[a:b, :3], num_rels) for t, a, b in zip(times, starts, ends)}
 
 
+class ObservedStream(object):
+    """A whole dataset as ONE observed stream, for the single-step (ground-truth history) evaluation protocol: at query
+    time t every fact before t is known, the evaluated split's own included (model.RENet.evaluate_observed).
+
+    splits: the time-ordered quadruple arrays train, valid, test in file order; valid may be None or left out (ICEWS14 has
+    none).  Holds `allq` (the concatenation), `ranges` (split name -> [a, b) of positions in allq), the history index of
+    both roles over the WHOLE stream -- the history of a test quadruple at t is the last <= history_len timestamps t' < t at
+    which its entity was active in that role, with the true neighbours at t', whichever split they come from: what
+    get_history_graph.py:206-317 writes into test_history_*.txt -- and `graph_dict`, one graph per timestamp of the whole
+    stream (the reference writes the training timestamps only).  Host arrays only; resident() puts them on a device."""
+
+    def __init__(self, splits, num_ent, num_rels, history_len=10):
+        splits = [np.asarray(q, dtype=np.int64).reshape(-1, 4) for q in splits if q is not None]
+        if len(splits) not in (2, 3):
+            raise ValueError('an observed stream is (train, valid, test) or (train, test)')
+        names = ('train', 'valid', 'test') if len(splits) == 3 else ('train', 'test')
+        self.num_ent, self.num_rels, self.history_len = int(num_ent), int(num_rels), int(history_len)
+        self.allq = np.concatenate(splits)
+        ends = np.cumsum([len(q) for q in splits])
+        self.ranges = {name: (int(b - len(q)), int(b)) for name, q, b in zip(names, splits, ends)}
+        self.hist_s = HistoryIndex(self.allq, 's', history_len)         # (raises unless the stream is sorted by time)
+        self.hist_o = HistoryIndex(self.allq, 'o', history_len)
+        self.graph_dict = build_graph_dict(self.allq, num_rels)
+        self.times = np.unique(self.allq[:, 3])
+        self.device = None                                              # the ObservedStore of the last resident() call
+
+    def __len__(self):
+        return len(self.allq)
+
+    def positions(self, split):
+        """The stream positions of a split ('train', 'valid', 'test'), in file order."""
+        return np.arange(*self.ranges[split])
+
+    def global_table(self, global_model):
+        """{t: embedding} over ALL timestamps of the stream, from the global model as it stands and this stream's own
+        graphs (global_model.py:57-73; no entry depends on a model prediction)."""
+        import torch
+        with torch.no_grad():
+            return global_model.get_global_emb(self.times, self.graph_dict)
+
+    def resident(self, model, global_model):
+        """The stream on the model's device: a gpu_builder.ObservedStore (the DeviceStore of the whole stream plus the
+        global-embedding table of its own, as a matrix).  Built anew at every call -- the table follows the global model's
+        weights -- and kept in `device`, where RENet.observed_scores / evaluate_observed find it."""
+        import gpu_builder
+        self.device = gpu_builder.ObservedStore(self, self.global_table(global_model), model.h_dim, model.ent_embeds.device)
+        return self.device
+
+
 def write_reference_pickles(data_dir, history_len=10):
     """Command-line equivalent of running data/<DS>/get_history_graph.py in `data_dir`: reads stat.txt,
     train.txt, valid.txt (optional), test.txt and writes train_graphs.txt and
