@@ -619,6 +619,40 @@ int renet_topk_rows(const float* scores, int ld, int n, int C, int k, const int3
                     const int32_t* count, int len, const int32_t* keep, int32_t* out_idx, float* out_val, float* out_logp,
                     int32_t* out_n, void* stream);
 
+/* Joint (relation, entity) ranks of an event (not in the reference; csrc/joint_rank.hip).  scores [G * R, C] (row stride ld;
+ * never written) holds, for each of G histories ("groups"), the R logits rows of the entity head -- row g * R + r the query
+ * whose relation is r -- and logits_r [G, R] (row stride ld_r) the relation head's rows.  The joint log-probability of the
+ * pair (r, c) of group g is
+ *   J[g, r, c] = scores[g * R + r, c] + off[g * R + r]                      (ONE IEEE fp32 addition, never contracted)
+ *   off[g * R + r] = fp32( logsoftmax(logits_r[g, :])[r] - logsumexp(scores[g * R + r, 0 .. C)) ),
+ * both terms in fp64 from the fp32 inputs (the online logsumexp of row_loss above), rounded once.
+ * renet_joint_row_offsets writes off [G * R] from one read of the block; any C, any row alignment, 1 <= R <= 1024.
+ * RENET_ERR_BADARG for G < 0, R out of range, C < 1, ld < C, ld_r < R or a missing array; G == 0 is a no-op. */
+int renet_joint_row_offsets(const float* scores, int ld, int G, int R, int C, const float* logits_r, int ld_r,
+                            float* off_out, void* stream);
+
+/* Query q (of Q) ranks its gold pair (gold_r[q], gold_c[q]) among the R * C pairs of group[q], on the fp32 values J above
+ * with the gold value v = J[group[q], gold_r[q], gold_c[q]]: one workgroup per (q, r) sweeps row group[q] * R + r once.  Per
+ * row q * R + r (all outputs row-major):
+ *   counts [6, Q * R]  : raw greater (#c: J > v), raw equal (#c: J == v, the gold pair included), then the same two of the
+ *                        filtered and of the time_filtered setting.  The settings' lists are per (q, r) row, addressed in
+ *                        place in a resident column table as in renet_rank_rows3: row q * R + r takes
+ *                        cols_x[start_x[q * R + r] .. + count_x[q * R + r]) (cut to the table; count <= 0: empty; every
+ *                        column at most once per row; columns outside [0, C) ignored).  A listed column is NO candidate --
+ *                        it loses its contribution (the renet_topk_rows convention) -- except the gold pair itself, which
+ *                        always stays.  All three pointers of a list NULL: no list, the raw counts.
+ *   at_gold [Q * R]    : J[group[q], r, gold_c[q]] (the R values among which a relation is ranked given both endpoints)
+ *   listed [2, Q * R]  : 1 where gold_c[q] is on the row's list a / list t, else 0.
+ * The sum of a query's R rows of counts gives its pair rank: greater + (equal - 1) / 2 + 1.  group, gold_r and gold_c are
+ * device data: values outside [0, G), [0, R), [0, C) are clamped into range by the kernel.  No global atomics.
+ * RENET_ERR_BADARG for Q < 0, G < 1, R < 1, C < 1, ld < C, a missing array, a list with only some of its three pointers or
+ * a negative length; Q == 0 is a no-op. */
+int renet_joint_rank_rows(const float* scores, int ld, int G, int C, int R, const float* off, int Q, const int32_t* group,
+                          const int32_t* gold_r, const int32_t* gold_c, const int32_t* cols_a, const int32_t* start_a,
+                          const int32_t* count_a, int len_a, const int32_t* cols_t, const int32_t* start_t,
+                          const int32_t* count_t, int len_t, int32_t* counts, float* at_gold, int32_t* listed,
+                          void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * DEVICE batch-graph builder for the merged training batch (both directions of train.py:136-137 as one batch of 2B
  * sequences: graph.build_batch_both; replaces utils.py:209-244 + 115-131 + dgl.batch and this library's own HOST

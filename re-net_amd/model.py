@@ -1327,6 +1327,20 @@ def _observed_launch(self, store, idx):
     return idx, gpu_builder.DeviceBatch(store, idx, self.seq_len)
 
 
+def _observed_prepared(self, store, pending):
+    """Waits for ONE pending batch of _observed_launch -> (its positions, the PreparedBatch)."""
+    import gpu_builder
+    idx, pend = pending
+    prep = self.finish_prepare_device(pend, glob=store.glob)
+    for _ in range(8):                      # a capacity overflow: finalize() has raised the store's capacities, rebuild
+        if prep is not None:
+            break
+        prep = self.finish_prepare_device(gpu_builder.DeviceBatch(store, idx, self.seq_len), glob=store.glob)
+    if prep is None:
+        raise RuntimeError('device batch builder did not converge on its capacities')
+    return idx, prep
+
+
 def _eval_rows_torch(ent, rel, h_sorted, q_sorted, perm, s, r, o, num_rels):
     """The GEMM-ready rows of both directions in quadruple order (model.py:89, 98 for subject=True / False):
     feat_ob[i] = [ent[s_i] | h(seq i) | rel[r_i]], feat_sub[i] = [ent[o_i] | h(seq n + i) | rel[R + r_i]] and the relation
@@ -1348,16 +1362,8 @@ def _eval_rows_torch(ent, rel, h_sorted, q_sorted, perm, s, r, o, num_rels):
 def _observed_features(self, store, pending, relation=False):
     """Builder -> encoder -> rows for ONE pending batch of _observed_launch: (feat_ob [n, 3H], feat_sub [n, 3H],
     featr_ob [n, 2H] or None, featr_sub) in the order of its positions."""
-    import gpu_builder
     dev, H, R = self.ent_embeds.device, self.h_dim, self.num_rels
-    idx, pend = pending
-    prep = self.finish_prepare_device(pend, glob=store.glob)
-    for _ in range(8):                      # a capacity overflow: finalize() has raised the store's capacities, rebuild
-        if prep is not None:
-            break
-        prep = self.finish_prepare_device(gpu_builder.DeviceBatch(store, idx, self.seq_len), glob=store.glob)
-    if prep is None:
-        raise RuntimeError('device batch builder did not converge on its capacities')
+    idx, prep = _observed_prepared(self, store, pending)
     g, b2 = prep.g, prep.b
     if g.S == 0:
         # every history of the batch is empty (the first timestamp of a stream).  The builder accepts that -- an empty
@@ -1507,6 +1513,265 @@ def _predict_topk_observed(self, obs, idx, k=10, all_triplets=None, setting='raw
     return out
 
 
+# =================================================================================================
+# Event forecasts under observed history: "what will entity s do next, and with whom?" -- the pairs (r, o) of a subject
+# (direction 'ob'; the pairs (r, s) of an object: 'sub') under the model's own factorisation p(o | s, r, history) *
+# p(r | s, history) (model.py:89-103; the second factor is the linear_r / encoder_r head).  Per history ("group": the
+# positions of an encoder chunk that share entity, timestamp and direction) the entity head gives a block B [R, N_ent], row r
+# the logits of the query whose relation is r, and the joint log-probability of a pair is
+#     J[r, c] = B[r, c] + off[r],   off[r] = fp32(logsoftmax64(linear_r logits)[r] - logsumexp64(B[r, :]))
+# as ONE fp32 addition (csrc/joint_rank.hip); the joint is never stored.  History, RGCN rows and encoder_r's state do not
+# depend on r: the chunk is built and encoded once for its positions' own sequences, and only the relation segment of the GRU
+# input (Gi = p_base + q_rel[r], the broadcast of _joint_topk_many) and of the head's feature row is R-fold.  As in the rest
+# of the observed pass nothing of the multi-step state is read or written.
+# =================================================================================================
+EVENT_DIRECTIONS = (('sub', 0, 's', 2, 0), ('ob', 1, 'o', 0, 2))      # name, result column, filter side, given / ranked column
+
+
+class _EventChunk(object):
+    """What one encoder chunk holds for its blocks: p_base [S, 3H] (the relation-free part of encoder's input projection, bias
+    included; None: every history of the chunk is empty), the packed layout (step_off, lens of the sorted positions), q_seq
+    [2 n, H] (encoder_r's states by sequence) and per direction its groups -- ent [G], t [G], sp [G] (sorted position of the
+    group's sequence; ascending, so the lengths descend), seq [G] and, for the chunk's positions, gid [n]."""
+
+
+def _event_chunks(self, store, idx):
+    """One _EventChunk per encoder chunk of idx (the chunks of _observed_chunks: the same batch graphs), the builder of chunk
+    k + 1 enqueued before chunk k is encoded."""
+    import gpu_builder
+    dev, H = self.ent_embeds.device, self.h_dim
+    step = gpu_builder.MAX_BOTH
+    pending = _observed_launch(self, store, idx[:step])
+    for c in range(0, len(idx), step):
+        ahead = _observed_launch(self, store, idx[c + step:c + 2 * step]) if c + step < len(idx) else None
+        pos, prep = _observed_prepared(self, store, pending)
+        pending = ahead
+        g, b2, n = prep.g, prep.b, len(pos)
+        ch = _EventChunk()
+        ch.c, ch.n = c, n
+        if g.S == 0:                        # (the first timestamp of a stream: zero states, as _observed_features)
+            ch.p_base, ch.step_off, ch.lens = None, np.zeros(1, dtype=np.int64), np.zeros(b2, dtype=np.int64)
+            ch.q_seq = torch.zeros(b2, H, device=dev)
+            pos_of = np.arange(b2)
+        else:
+            x, xr = self.aggregator.encode(g, self.ent_embeds, self.rel_embeds, reverse=False)
+            w_ih, b_ih = self.encoder.weight_ih_l0, self.encoder.bias_ih_l0
+            ch.p_base = K.gemm(x[:, :2 * H], w_ih[:, :2 * H], tb=True, bias=b_ih)          # [h2 | ent] part + bias
+            K.gemm(x[:, 3 * H:], w_ih[:, 3 * H:], tb=True, out=ch.p_base, beta=1.0)        # + glob part
+            er = self.encoder_r
+            q_sorted = ops.GRUFn.apply(xr, er.weight_ih_l0, er.weight_hh_l0, er.bias_ih_l0, er.bias_hh_l0, prep.step_off, b2)
+            perm = g.host.perm[:b2]                                                         # sorted position -> sequence
+            ch.q_seq = torch.empty(b2, H, device=dev)
+            ch.q_seq[g._v['perm'][:b2].long()] = q_sorted.view(b2, H)
+            bs = g.host.batch_sizes
+            ch.step_off = np.concatenate(([0], np.cumsum(bs))).astype(np.int64)
+            ch.lens = (bs[:, None] > np.arange(b2)[None, :]).sum(axis=0)                    # steps of sorted position
+            pos_of = np.empty(b2, dtype=np.int64)
+            pos_of[perm] = np.arange(b2)
+        tr = store.quads[pos]
+        ch.dirs = {}
+        for name, col, side, given, ranked in EVENT_DIRECTIONS:
+            keys, first, inv = np.unique(tr[:, [given, 3]], axis=0, return_index=True, return_inverse=True)
+            seq = first + (n if name == 'sub' else 0)               # sequence i: direction ob of position i, n + i: sub
+            order = np.argsort(pos_of[seq], kind='stable')
+            rank = np.empty(len(order), dtype=np.int64)
+            rank[order] = np.arange(len(order))
+            d = ch.dirs[name] = _EventChunk()
+            d.ent, d.t, d.seq, d.sp, d.gid = keys[order, 0], keys[order, 1], seq[order], pos_of[seq[order]], rank[inv.reshape(-1)]
+        yield ch
+
+
+def _event_blocks(self, ch, name, q_rel, block_floats):
+    """The blocks of one direction of a chunk in sub-blocks of at most block_floats floats (at least one group): yields
+    (g0, g1, B [(g1 - g0) * R, N_ent], off [(g1 - g0) * R]) for the groups [g0, g1), the rows group-major, then relation.  Per
+    sub-block: the p_base rows of its groups' steps + the q_rel broadcast, ONE recurrence over the R-fold sequences (ordered
+    by sorted position, then relation: the lengths descend, the row order of _winners_pruned), the rows [ent | h | rel_r], one
+    score GEMM, renet_joint_row_offsets."""
+    R, dev, H, N = self.num_rels, self.ent_embeds.device, self.h_dim, self.in_dim
+    d = ch.dirs[name]
+    rel = self.rel_embeds[R:] if name == 'sub' else self.rel_embeds[:R]
+    w_hh, b_hh = self.encoder.weight_hh_l0.contiguous(), self.encoder.bias_hh_l0.contiguous()
+    per = max(1, int(block_floats) // max(R * N, 1))
+    for g0 in range(0, len(d.ent), per):
+        g1 = min(len(d.ent), g0 + per)
+        m = g1 - g0
+        ln = ch.lens[d.sp[g0:g1]]                                   # descending
+        if ch.p_base is not None and ln[0] > 0:
+            k_t = [int(np.count_nonzero(ln > t)) for t in range(int(ln[0]))]
+            rows = np.concatenate([ch.step_off[t] + d.sp[g0:g0 + k] for t, k in enumerate(k_t)])
+            gi = (ch.p_base[G.h2d(rows, dev)].view(-1, 1, 3 * H) + q_rel.view(1, R, 3 * H)).reshape(-1, 3 * H)
+            off = ops.host_offsets(np.concatenate(([0], np.cumsum(k_t))) * R)              # every step R times as wide
+            hh, _ = K.gru_fwd(gi, off, H, w_hh, b_hh, out_rows=m * R)                      # [m * R, H]; rows past k_t[0] * R zero
+        else:
+            hh = torch.zeros(m * R, H, device=dev)
+        ent_rows = self.ent_embeds[G.h2d(d.ent[g0:g1], dev)]                                # [m, H]
+        feat = torch.cat((ent_rows.repeat_interleave(R, dim=0), hh[:m * R], rel.repeat(m, 1)), dim=1)
+        block = _linear_eval(self.linear, feat)                                             # [m * R, N_ent]
+        logits_r = _linear_eval(self.linear_r, torch.cat((ent_rows, ch.q_seq[G.h2d(d.seq[g0:g1], dev)]), dim=1))
+        yield g0, g1, block, K.joint_row_offsets(block, R, logits_r)
+
+
+def _event_setup(self, obs, idx):
+    store = _observed_store(obs)
+    idx = _observed_positions(store, idx)
+    if self.num_rels > 1024:
+        raise ValueError('event forecasts take at most 1024 relations (renet_joint_row_offsets)')
+    return store, idx
+
+
+def _event_q_rel(self):
+    """{direction: rel_embeds of the direction against the relation segment of encoder's w_ih, [R, 3H]}."""
+    R, H = self.num_rels, self.h_dim
+    w = self.encoder.weight_ih_l0[:, 2 * H:3 * H]
+    return {'ob': K.gemm(self.rel_embeds[:R].contiguous(), w, tb=True), 'sub': K.gemm(self.rel_embeds[R:].contiguous(), w, tb=True)}
+
+
+def _observed_event_scores(self, obs, idx, block_floats=1 << 28):
+    """The blocks of the stream positions idx under observed histories (for small n: tests, inspection): {'ob': (B [n, R,
+    N_ent], off [n, R]), 'sub': (...)} as device tensors.  B[i, r] is the logits row observed_scores(obs, idx) computes for
+    position i in that direction if the quadruple's relation were r (the same encoder chunks, true history and global table;
+    the GRU input projection is associated differently), off[i, r] the row's offset: J = B + off[..., None] in fp32 is the
+    joint log-probability that evaluate_events_observed ranks.  ValueError if n * R * N_ent exceeds block_floats."""
+    store, idx = _event_setup(self, obs, idx)
+    n, R, N = len(idx), self.num_rels, self.in_dim
+    if n * R * N > int(block_floats):
+        raise ValueError('observed_event_scores: %d positions x %d relations x %d entities exceed block_floats = %d'
+                         % (n, R, N, int(block_floats)))
+    dev = self.ent_embeds.device
+    out = {name: (torch.empty(n, R, N, device=dev), torch.empty(n, R, device=dev)) for name in ('ob', 'sub')}
+    with torch.no_grad():
+        q_rel = _event_q_rel(self)
+        for ch in _event_chunks(self, store, idx):
+            for name in ('sub', 'ob'):
+                gid = G.h2d(ch.dirs[name].gid, dev)
+                for g0, g1, block, off in _event_blocks(self, ch, name, q_rel[name], block_floats):
+                    here = torch.nonzero((gid >= g0) & (gid < g1)).view(-1)
+                    out[name][0][ch.c + here] = block.view(g1 - g0, R, N)[gid[here] - g0]
+                    out[name][1][ch.c + here] = off.view(g1 - g0, R)[gid[here] - g0]
+    return out
+
+
+def _event_known(d, R):
+    """The filter keys of every (group, relation) row of one direction of a chunk, group-major: (entity, r', t) [G * R, 3]."""
+    return np.stack((np.repeat(d.ent, R), np.tile(np.arange(R, dtype=np.int64), len(d.ent)), np.repeat(d.t, R)), axis=1)
+
+
+def _evaluate_events_observed(self, obs, idx, all_triplets=None, block_floats=1 << 28):
+    """Ranks of the gold EVENT of the stream positions idx under observed histories (extension of the reference API):
+    {'pair': {setting: float64 [len, 2]}, 'relation': {setting: float64 [len, 2]}, 'logp': float32 [len, 2]}, column 0 the
+    direction sub (the object given: pairs (r, s)), column 1 ob (the subject given: pairs (r, o)); the settings are SETTINGS.
+    With J the joint log-probabilities of the position's block (observed_event_scores) and v = J[r*, gold entity] (= logp):
+      pair      rank of the gold pair among the R * N_ent pairs, greater + (equal - 1) / 2 + 1 on the fp32 values J; under
+                'filtered' the pairs (r', e') for which (s, r', e') -- (e', r', o) for sub -- is a known fact at any time are no
+                candidates at all, under 'time_filtered' those known at the query's own timestamp; the gold pair stays;
+      relation  rank of r* among J[:, gold entity] (both endpoints given), ties averaged; the filtered settings drop the
+                relations r' != r* for which the triple with both endpoints is known (at t).
+    all_triplets: the known facts (None: the stream itself).  Per encoder chunk the host filter lookups of every (group,
+    relation) row are done and uploaded before its sub-blocks run (block_floats bounds a sub-block's score block); one
+    renet_joint_row_offsets and one renet_joint_rank_rows launch per sub-block; the counts come back in one copy at the end.
+    Repeatable in place; the multi-step state is untouched."""
+    store, idx = _event_setup(self, obs, idx)
+    dev, n, R = self.ent_embeds.device, len(idx), self.num_rels
+    index = FI.filter_index_for(store, all_triplets if all_triplets is not None else store.quads)
+    cols = {side: (index.resident(side, dev), index.resident(side, dev, timed=True)) for side in ('s', 'o')}
+    gold = torch.from_numpy(np.ascontiguousarray(store.quads[idx][:, :3].T).astype(np.int32)).to(dev)      # s, r, o
+    pair = torch.zeros(6, n, 2, device=dev, dtype=torch.int64)
+    rel = torch.zeros(6, n, 2, device=dev, dtype=torch.int64)
+    logp = torch.empty(n, 2, device=dev)
+    rels = torch.arange(R, device=dev).view(1, R)
+    with torch.no_grad():
+        q_rel = _event_q_rel(self)
+        for ch in _event_chunks(self, store, idx):
+            # every host lookup of the chunk, and its upload, before the first sub-block runs
+            ups = {}
+            for name, col, side, given, ranked in EVENT_DIRECTIONS:
+                d = ch.dirs[name]
+                by_group = np.argsort(d.gid, kind='stable')                                # the chunk's positions, group-major
+                lists = np.stack(index.ranges_both_host(side, _event_known(d, R))).astype(np.int32)
+                ups[name] = (by_group, d.gid[by_group], G.h2d(by_group, dev), G.h2d(d.gid[by_group].astype(np.int32), dev),
+                             torch.from_numpy(lists).to(dev).view(4, len(d.ent), R))
+            for name, col, side, given, ranked in EVENT_DIRECTIONS:
+                by_group, gid_h, here, gid, lists = ups[name]
+                for g0, g1, block, off in _event_blocks(self, ch, name, q_rel[name], block_floats):
+                    a, b = np.searchsorted(gid_h, (g0, g1))
+                    pos = ch.c + here[a:b]                                                  # positions of idx, group-major
+                    grp = gid[a:b] - g0
+                    gr, gc = gold[1][pos].contiguous(), gold[ranked][pos].contiguous()
+                    rows = lists[:, g0:g1][:, grp.long()].reshape(4, -1).contiguous()       # [4, Q * R]: per (query, relation)
+                    cnt, at_gold, listed, _ = K.joint_rank_rows(block, R, off, grp.contiguous(), gr, gc, cols[side][0], rows[0],
+                                                                rows[1], cols[side][1], rows[2], rows[3])
+                    pair[:, pos, col] = cnt
+                    v = at_gold.gather(1, gr.long().view(-1, 1))
+                    logp[pos, col] = v.view(-1)
+                    own = rels == gr.long().view(-1, 1)
+                    for k, keep in enumerate((None, (listed[0] == 0) | own, (listed[1] == 0) | own)):
+                        gt, eq = at_gold > v, at_gold == v
+                        rel[2 * k, pos, col] = (gt if keep is None else gt & keep).sum(dim=1)
+                        rel[2 * k + 1, pos, col] = (eq if keep is None else eq & keep).sum(dim=1)
+    # ONE copy: the counts of both kinds and logp as [13, n, 2] float64 (counts and fp32 values are exact in it)
+    back = torch.cat((pair.double(), rel.double(), logp.double().view(1, n, 2))).cpu().numpy()
+    ranks = [{name: c[2 * k] + (c[2 * k + 1] - 1.0) / 2 + 1 for k, name in enumerate(SETTINGS)} for c in (back[0:6], back[6:12])]
+    return {'pair': ranks[0], 'relation': ranks[1], 'logp': back[12].astype(np.float32)}
+
+
+def _predict_events_observed(self, obs, idx, k=10, all_triplets=None, setting='raw'):
+    """The k most probable events of the stream positions idx under observed histories: {'ob': (rel int32 [n, k], ent int32
+    [n, k], logp [n, k], n_valid int32 [n]), 'sub': (...)} as device tensors -- for 'ob' the pairs (r, o) of the position's
+    subject, for 'sub' the pairs (r, s) of its object, by joint log-probability J descending, then relation, then entity
+    ascending (deterministic); logp is J, bit for bit B + off of observed_event_scores.  setting (one of SETTINGS) says which
+    known facts are no candidates, as in predict_topk_observed; there is no keep_gold: hits are read from the ranks of
+    evaluate_events_observed.  n_valid = min(k, candidates); the slots behind it hold -1, -1, -inf.  Per sub-block one
+    renet_topk_rows launch gives every relation row's k best entities, and the k best of those R * k candidates are taken
+    (a pair outside its own row's k best by SCORE cannot enter: exact unless two distinct scores of a row round to one J at
+    that row's k-th place).  k <= 1024 and N_ent <= 32768 (renet_topk_rows)."""
+    if setting not in SETTINGS:
+        raise ValueError('setting must be one of %s, not %r' % (', '.join(SETTINGS), setting))
+    store, idx = _event_setup(self, obs, idx)
+    dev, n, R, N, k = self.ent_embeds.device, len(idx), self.num_rels, self.in_dim, int(k)
+    index = FI.filter_index_for(store, all_triplets if all_triplets is not None else store.quads) if setting != 'raw' else None
+    out = {name: (torch.full((n, k), -1, device=dev, dtype=torch.int32), torch.full((n, k), -1, device=dev, dtype=torch.int32),
+                  torch.full((n, k), -np.inf, device=dev), torch.zeros(n, device=dev, dtype=torch.int32)) for name in ('ob', 'sub')}
+    with torch.no_grad():
+        q_rel = _event_q_rel(self)
+        for ch in _event_chunks(self, store, idx):
+            for name, col, side, given, ranked in EVENT_DIRECTIONS:
+                d = ch.dirs[name]
+                lists = (None, None, None)
+                if index is not None:
+                    keys = _event_known(d, R)
+                    lists = index.ranges(side, keys if setting == 'time_filtered' else keys[:, :2], dev)
+                gid = G.h2d(d.gid, dev)
+                for g0, g1, block, off in _event_blocks(self, ch, name, q_rel[name], 1 << 28):
+                    m = g1 - g0
+                    row_lists = (lists[0], lists[1][g0 * R:g1 * R].contiguous(), lists[2][g0 * R:g1 * R].contiguous()) \
+                        if index is not None else lists
+                    ent, val, _, _ = K.topk_rows(block, k, *row_lists, want_logp=False)      # [m * R, k] each
+                    cand = (val + off.view(-1, 1)).view(m, R * k)                           # J, fp32; empty slots -inf
+                    ent = ent.view(m, R * k).long()
+                    code = torch.where(ent >= 0, _event_slot_rels(R, k, dev) * N + ent, R * N)      # relation-major, entity ascending
+                    by_code = torch.sort(code, dim=1, stable=True)[1]
+                    best = torch.sort(cand.gather(1, by_code), dim=1, descending=True, stable=True)[1][:, :k]
+                    take = by_code.gather(1, best)                                          # [m, min(k, R * k)]
+                    j, e = cand.gather(1, take), ent.gather(1, take)
+                    ok = e >= 0
+                    here = torch.nonzero((gid >= g0) & (gid < g1)).view(-1)
+                    grp = gid[here] - g0
+                    o_rel, o_ent, o_logp, o_n = out[name]
+                    o_rel[ch.c + here] = torch.where(ok, torch.div(take, k, rounding_mode='floor'), -1).int()[grp]
+                    o_ent[ch.c + here] = e.int()[grp]
+                    o_logp[ch.c + here] = torch.where(ok, j, -np.inf)[grp]
+                    o_n[ch.c + here] = ok.sum(dim=1).int()[grp]
+    return out
+
+
+def _event_slot_rels(R, k, dev):
+    """The relation of every slot of an [R * k] candidate row laid out relation-major."""
+    return torch.arange(R, device=dev).repeat_interleave(k).view(1, R * k)
+
+
+RENet.observed_event_scores = _moded(_observed_event_scores)
+RENet.evaluate_events_observed = _moded(_evaluate_events_observed)
+RENet.predict_events_observed = _moded(_predict_events_observed)
 RENet.observed_scores = _moded(_observed_scores)
 RENet.evaluate_observed = _moded(_evaluate_observed)
 RENet.predict_topk_observed = _moded(_predict_topk_observed)

@@ -149,6 +149,10 @@ _SIGNATURES = {
                                  c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     'renet_topk_rows': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'renet_joint_row_offsets': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    'renet_joint_rank_rows': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                      c_void_p, c_void_p, c_void_p]),
     'renet_topk_workspace': (c_size_t, [c_int]),
     'renet_topk_positive': (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
                                     c_void_p]),
@@ -1493,6 +1497,72 @@ def topk_rows(scores, k, cols=None, start=None, count=None, keep=None, want_logp
            'topk_rows')
     _timed_end(t0, 'topk_rows', nbytes=float(n * c * 4))
     return idx, val, logp, n_valid
+
+
+def _block_ld(scores):
+    """Row stride of a [rows, C] block (a one-row block may carry any stride)."""
+    return max(_ld(scores), scores.shape[1]) if scores.shape[0] == 1 else _ld(scores)
+
+
+def joint_row_offsets(scores, num_rels, logits_r):
+    """renet_joint_row_offsets on the block scores [G * R, C] (fp32, unit inner stride; not written) and the relation head's
+    logits_r [G, R]: -> off [G * R] (fp32) with off[g * R + r] = logsoftmax(logits_r[g])[r] - logsumexp(scores[g * R + r]),
+    both in fp64, rounded once.  The joint log-probability of the pair (r, c) of group g is scores[g * R + r, c] +
+    off[g * R + r] as one fp32 addition; it is never stored.  R <= 1024."""
+    if not (scores.is_cuda and scores.dtype == torch.float32 and scores.dim() == 2 and scores.stride(1) == 1):
+        raise RenetHipError('joint_row_offsets needs a 2-D float32 device tensor with unit inner stride')
+    rows, c = scores.shape
+    r = int(num_rels)
+    g = rows // max(r, 1)
+    if r < 1 or rows != g * r or tuple(logits_r.shape) != (g, r) or logits_r.dtype != torch.float32 or \
+            not logits_r.is_cuda or logits_r.stride(1) != 1:
+        raise RenetHipError('joint_row_offsets: shape mismatch')
+    off = torch.empty(rows, device=scores.device, dtype=torch.float32)
+    t0 = _timed()
+    _check(lib().renet_joint_row_offsets(scores.data_ptr(), _block_ld(scores), g, r, c, logits_r.data_ptr(),
+                                         _block_ld(logits_r), off.data_ptr(), _stream()), 'joint_row_offsets')
+    _timed_end(t0, 'joint_row_offsets', nbytes=float(rows * c * 4))
+    return off
+
+
+def joint_rank_rows(scores, num_rels, off, group, gold_r, gold_c, cols_a=None, start_a=None, count_a=None, cols_t=None,
+                    start_t=None, count_t=None):
+    """renet_joint_rank_rows: Q queries rank their gold pair (gold_r[q], gold_c[q]) among the R * C pairs of group[q] of the
+    block scores [G * R, C] (not written) on the fp32 values J = scores + off[row] (off [G * R]: joint_row_offsets, or any
+    fp32 array) -> (counts int64 [6, Q], at_gold fp32 [Q, R], listed int32 [2, Q, R], rows int32 [6, Q, R]).
+    counts = raw (greater, equal), filtered (greater, equal), time_filtered (greater, equal) over all pairs -- the kernel's
+    per-row counts `rows` summed over the R rows of a query; rank = greater + (equal - 1) / 2 + 1.  A setting's list is
+    (cols, start [Q * R], count [Q * R]), row q * R + r the columns that are no candidates in relation row r of query q (a
+    range of a resident column table, filter_index.FilterIndex.ranges; int32), the gold pair always staying; three Nones (or
+    an empty table): no list.  A column may appear AT MOST ONCE in a row's list (FilterIndex deduplicates): a listed column's
+    contribution is subtracted once per occurrence, so a repeated column would be undercounted.  at_gold[q, r] = J[group[q], r, gold_c[q]]; listed[0 / 1, q, r] = 1 where gold_c[q] is on list
+    a / t of row (q, r).  group, gold_r, gold_c: int32 [Q], clamped into range by the kernel."""
+    if not (scores.is_cuda and scores.dtype == torch.float32 and scores.dim() == 2 and scores.stride(1) == 1):
+        raise RenetHipError('joint_rank_rows needs a 2-D float32 device tensor with unit inner stride')
+    rows, c = scores.shape
+    r = int(num_rels)
+    g = rows // max(r, 1)
+    q = group.numel()
+    if r < 1 or rows != g * r or off.numel() != rows or gold_r.numel() != q or gold_c.numel() != q:
+        raise RenetHipError('joint_rank_rows: shape mismatch')
+    lists = []
+    for cols, start, count in ((cols_a, start_a, count_a), (cols_t, start_t, count_t)):
+        if cols is None and start is None and count is None:
+            lists += [None, None, None, 0]
+            continue
+        if cols is None or start is None or count is None or start.numel() != q * r or count.numel() != q * r:
+            raise RenetHipError('joint_rank_rows: a filter list is (cols, start [Q * R], count [Q * R])')
+        # (an empty table has no storage to point at: no list)
+        lists += [_i32(cols), _i32(start), _i32(count), cols.numel()] if cols.numel() else [None, None, None, 0]
+    per_row = torch.empty(6, q, r, device=scores.device, dtype=torch.int32)
+    at_gold = torch.empty(q, r, device=scores.device, dtype=torch.float32)
+    listed = torch.empty(2, q, r, device=scores.device, dtype=torch.int32)
+    t0 = _timed()
+    _check(lib().renet_joint_rank_rows(scores.data_ptr(), _block_ld(scores), g, c, r, _f32(off), q, _i32(group), _i32(gold_r),
+                                       _i32(gold_c), *lists, per_row.data_ptr(), at_gold.data_ptr(), listed.data_ptr(),
+                                       _stream()), 'joint_rank_rows')
+    _timed_end(t0, 'joint_rank_rows', nbytes=float(q * r * c * 4))
+    return per_row.sum(dim=-1), at_gold, listed, per_row
 
 
 def joint_softmax(logits, num_rels, logits_r, prob_e):

@@ -4,8 +4,12 @@ MRR / Hits of a split, every query at time t seeing all facts before t (the eval
 protocol under which RE-GCN, xERTE and TITer report the time-aware filter.  NOT the reference's multi-step protocol
 (test.py; RENet.evaluate_all_stream): the two answer different questions, their numbers must not be mixed.
 
-    python tools/run_observed_eval.py DATA_DIR --n-hidden H --seq-len L [--split valid|test] [--topk K]
+    python tools/run_observed_eval.py DATA_DIR --n-hidden H --seq-len L [--split valid|test] [--topk K] [--events [K]]
                                       [--model-dir models/<DS>] [--maxpool 1] [--max-batch 4096] [--gpu 0]
+
+--events adds the EVENT forecasts (RENet.evaluate_events_observed): MRR / Hits of the gold (relation, entity) pair among all
+pairs of the given entity, and of the gold relation given both endpoints, in the three settings; with K also the K most
+probable (relation, object) pairs of the first few queries (RENet.predict_events_observed, time-aware filtered).
 
 DATA_DIR holds stat.txt, train.txt, valid.txt (optional) and test.txt.  From the model directory (default: models/<name of
 DATA_DIR>, where the reference's drivers write) only the weights are read: `rgcn.pth` (train.py:189) and the global model's
@@ -28,6 +32,8 @@ def main():
     ap.add_argument('--seq-len', type=int, required=True)
     ap.add_argument('--split', choices=('valid', 'test'), default='test')
     ap.add_argument('--topk', type=int, default=0, help='also write the K best time-aware filtered predictions per query')
+    ap.add_argument('--events', type=int, nargs='?', const=0, default=None, metavar='K',
+                    help='also rank the gold (relation, entity) pairs; with K, print the K best forecasts of the first queries')
     ap.add_argument('--model-dir', default=None)
     ap.add_argument('--maxpool', type=int, default=1)
     ap.add_argument('--max-batch', type=int, default=4096)
@@ -83,6 +89,28 @@ def main():
               % (name, m['mrr'], m['mr'], m['hits@1'], m['hits@3'], m['hits@10']))
     print(json.dumps({'protocol': 'observed', 'split': args.split, 'n': int(len(idx)),
                       'metrics': {name: U.rank_metrics(ranks[name]) for name in SETTINGS}}))
+    if args.events is not None:
+        t3 = time.perf_counter()
+        ev = model.evaluate_events_observed(obs, idx)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t3
+        print('event forecasts, columns (given o: pairs (r, s) | given s: pairs (r, o)): pass %.2f s (%.0f quadruples/s), '
+              'mean log p of the gold event %.4f | %.4f' % ((dt, len(idx) / max(dt, 1e-9)) + tuple(ev['logp'].mean(axis=0))))
+        for kind, what in (('pair', 'pair (r, entity) among R x N_ent'), ('relation', 'relation given both endpoints')):
+            for name in SETTINGS:
+                m = U.rank_metrics(ev[kind][name])
+                print('%-30s %-14s MRR %.6f  MR %.3f  Hits@1 %.6f  Hits@3 %.6f  Hits@10 %.6f'
+                      % (what, name, m['mrr'], m['mr'], m['hits@1'], m['hits@3'], m['hits@10']))
+        print(json.dumps({'protocol': 'observed', 'task': 'events', 'split': args.split, 'n': int(len(idx)),
+                          'metrics': {kind: {name: U.rank_metrics(ev[kind][name]) for name in SETTINGS}
+                                      for kind in ('pair', 'relation')}}))
+        if args.events > 0:
+            few = idx[:5]
+            rel, ent, logp, n_valid = (x.cpu().numpy() for x in
+                                       model.predict_events_observed(obs, few, k=args.events, setting='time_filtered')['ob'])
+            for i, (s, r, o, t) in enumerate(obs.allq[few].tolist()):
+                print('t = %d, subject %d (gold: relation %d, object %d): ' % (t, s, r, o) +
+                      ', '.join('(%d, %d) %.3f' % (rel[i, j], ent[i, j], logp[i, j]) for j in range(int(n_valid[i]))))
     if args.topk > 0:
         out = os.path.join(model_dir, 'observed_top%d_%s.npz' % (args.topk, args.split))
         parts = {'sub_idx': [], 'sub_logp': [], 'ob_idx': [], 'ob_logp': []}
