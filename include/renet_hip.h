@@ -551,7 +551,10 @@ int renet_adam_step_presummed(float* p, float* g, float* m, float* v, size_t n, 
  * Inference: the joint (relation, object) distribution of pred_r_rank2 and its top-k (model.py:205-209,239).
  *   renet_joint_softmax : logits [n * R, N] (row stride ld) is overwritten, row (e, r) with
  *                           softmax(logits[e, r, :]) * softmax(logits_r[e, :])[r] * prob_e[e]
- *                         (the reference: torch.softmax x2 + two broadcast multiplies); N * 4 <= 128 KB, R <= 1024.
+ *                         (the reference: torch.softmax x2 + two broadcast multiplies); any N, R <= 1024 (beyond that
+ *                         RENET_ERR_UNSUPPORTED).  N * 4 <= 128 KB: one read and one write, the row staged in LDS; wider
+ *                         rows are streamed twice (an online max / sum sweep, then the write: the same operation order
+ *                         per element, the row sum rounded in another order).
  *   renet_topk_positive : the k largest elements of every row of x [n, M] (row stride ldx), x >= 0: values and int64
  *                         column indices, in NO particular order (torch.topk(..., sorted=False)); exact (radix select
  *                         on the bit pattern); ties at the threshold are broken arbitrarily.
@@ -613,11 +616,28 @@ int renet_rank_rows3(const float* scores, int ld, int n, int C, const int32_t* l
  * Scores are finite or -inf: a -inf score is an ordinary candidate that sorts last (logp -inf), distinct from a filtered
  * column.  A NaN (ranked below -inf) or +inf gives no meaningful order or logp, but never an index outside [-1, C).
  * 1 <= k <= 1024 (k may exceed C); C <= 32768 (the row is staged in LDS), beyond that RENET_ERR_UNSUPPORTED, before any
- * launch.  RENET_ERR_BADARG for n < 0, C < 1, ld < C, k out of range, a negative len, a list with only some of its three
+ * launch (wider rows: renet_topk_rows_wide below).  RENET_ERR_BADARG for n < 0, C < 1, ld < C, k out of range, a negative len, a list with only some of its three
  * pointers or a missing output array; n == 0 is a no-op. */
 int renet_topk_rows(const float* scores, int ld, int n, int C, int k, const int32_t* cols, const int32_t* start,
                     const int32_t* count, int len, const int32_t* keep, int32_t* out_idx, float* out_val, float* out_logp,
                     int32_t* out_n, void* stream);
+
+/* The same contract, result for result, for rows beyond one CU's LDS: any C up to RENET_TOPK_ROWS_WIDE_MAX_C, beyond that
+ * RENET_ERR_UNSUPPORTED, before any launch (narrower rows are served too).  The row is taken in pieces of stage_cols columns
+ * (0: the entry's own choice, an even split into pieces of at most 15360 columns; else 64 <= stage_cols <= 32768, anything
+ * else RENET_ERR_BADARG): a (piece, row) grid leaves every piece's sorted min(k, stage_cols) best candidates, its candidate
+ * count and its fp64 (max, sum of exponentials) in the workspace, and one workgroup per row merges the pieces in column
+ * order.  A list is applied by every piece it reaches, each listed column by the one piece that holds it; out_n comes from
+ * the sum of the pieces' counts; the logsumexp is the fixed-order fp64 combination of the pieces' pairs (one rounding of
+ * out_logp, as above).  No global atomics: the result is the same from run to run, and scores is never written.
+ * workspace: renet_topk_rows_wide_workspace bytes for the same n, C, k, stage_cols (0 for arguments the entry refuses),
+ * 8-byte aligned; too small, misaligned or NULL: RENET_ERR_WORKSPACE.  The other refusals are those of renet_topk_rows. */
+#define RENET_TOPK_ROWS_WIDE_MAX_C (1 << 20)
+size_t renet_topk_rows_wide_workspace(int n, int C, int k, int stage_cols);
+int renet_topk_rows_wide(const float* scores, int ld, int n, int C, int k, const int32_t* cols, const int32_t* start,
+                         const int32_t* count, int len, const int32_t* keep, int32_t* out_idx, float* out_val,
+                         float* out_logp, int32_t* out_n, int stage_cols, void* workspace, size_t workspace_bytes,
+                         void* stream);
 
 /* Joint (relation, entity) ranks of an event (not in the reference; csrc/joint_rank.hip).  scores [G * R, C] (row stride ld;
  * never written) holds, for each of G histories ("groups"), the R logits rows of the entity head -- row g * R + r the query

@@ -7,7 +7,8 @@
 //   renet_joint_softmax : ONE read + ONE write of the block: the row is staged in LDS (as softmax_ce_lds_kernel), max /
 //                         sum / normalise run out of LDS, and the relation and entity factors are folded into the
 //                         write.  Same operation order as the reference's expression (exp(x - max) / sum, then * p_r,
-//                         then * prob).
+//                         then * prob).  A row beyond 128 KB (N > 32768) is streamed twice instead
+//                         (joint_softmax_stream_kernel below).
 //   renet_topk_positive : exact top-k of every row of a [n, M] matrix of POSITIVE floats by radix select on the bit
 //                         pattern (monotone for positive floats): three histogram passes (12 + 12 + 8 bits, LDS
 //                         histograms, integer atomics: deterministic counts), a threshold pick per row, one collect pass.
@@ -15,6 +16,7 @@
 //                         values equal to the threshold are taken in arbitrary order, as torch.topk does.
 // HBM / L2-bound integer and exp work: no MFMA.
 #include "common.h"
+#include <float.h>
 #include <math.h>
 
 namespace {
@@ -91,6 +93,78 @@ __global__ __launch_bounds__(1024) void joint_softmax_kernel(float* x, int ld, i
     for (int w = 0; w < 16; ++w) s += red[w];
     const float pr = s_pr, pe = prob_e[e];
     for (int cc = threadIdx.x; cc < N; cc += 1024) xr[cc] = ((row[cc] / s) * pr) * pe;
+}
+
+// The same row when it does not fit LDS (N * 4 > 128 KB): one workgroup per row streams it twice.  Sweep 1 is an online
+// (max, sum): a thread folds its elements eight at a time -- the chunk's maximum first, ONE rescaling of the running sum
+// when it rises, then the eight exponentials -- and the threads' pairs are combined once, in thread order.  Sweep 2 reads
+// the row again (it was just read: L2 / MALL) and writes exp(x - max) / sum * p_r * prob: per element the operation order
+// of the LDS kernel, so the two differ only in how the sum was rounded.  Scalar 4-byte accesses, consecutive lanes on
+// consecutive columns (the row may start at any 4-byte address); eight independent loads in flight per thread.
+__global__ __launch_bounds__(1024) void joint_softmax_stream_kernel(float* x, int ld, int N, int R,
+                                                                    const float* __restrict__ logits_r, int ld_r,
+                                                                    const float* __restrict__ prob_e) {
+    __shared__ float red_m[16], red_s[16];
+    __shared__ float s_pr;
+    const int rowid = blockIdx.x;
+    const int e = rowid / R, r = rowid - e * R;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float* xr = x + (size_t)rowid * ld;
+    if (wave == 0) {                                                     // p_r, as joint_softmax_kernel forms it
+        const float* lr = logits_r + (size_t)e * ld_r;
+        float m = -INFINITY;
+        for (int c = lane; c < R; c += 64) m = fmaxf(m, lr[c]);
+        m = tk_wave_max(m);
+        float s = 0.f;
+        for (int c = lane; c < R; c += 64) s += expf(lr[c] - m);
+        s = tk_wave_sum(s);
+        if (lane == 0) s_pr = expf(lr[r] - m) / s;
+    }
+    float m = -FLT_MAX, s = 0.f;                                         // (finite: m - m is 0 before the first element)
+    int c = threadIdx.x;
+    for (; c + 7 * 1024 < N; c += 8 * 1024) {
+        float v[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) v[q] = xr[c + q * 1024];
+        const float cm = fmaxf(fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])), fmaxf(fmaxf(v[4], v[5]), fmaxf(v[6], v[7])));
+        if (cm > m) {
+            s *= expf(m - cm);
+            m = cm;
+        }
+#pragma unroll
+        for (int q = 0; q < 8; ++q) s += expf(v[q] - m);
+    }
+    for (; c < N; c += 1024) {
+        const float v = xr[c];
+        if (v > m) {
+            s *= expf(m - v);
+            m = v;
+        }
+        s += expf(v - m);
+    }
+    const float wm = tk_wave_max(m);
+    s = tk_wave_sum(s * expf(m - wm));
+    if (lane == 0) {
+        red_m[wave] = wm;
+        red_s[wave] = s;
+    }
+    __syncthreads();
+    m = red_m[0];
+#pragma unroll
+    for (int w = 1; w < 16; ++w) m = fmaxf(m, red_m[w]);
+    s = 0.f;
+#pragma unroll
+    for (int w = 0; w < 16; ++w) s += red_s[w] * expf(red_m[w] - m);
+    const float pr = s_pr, pe = prob_e[e];
+    c = threadIdx.x;
+    for (; c + 7 * 1024 < N; c += 8 * 1024) {
+        float v[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) v[q] = xr[c + q * 1024];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) xr[c + q * 1024] = ((expf(v[q] - m) / s) * pr) * pe;
+    }
+    for (; c < N; c += 1024) xr[c] = ((expf(xr[c] - m) / s) * pr) * pe;
 }
 
 // ---- radix select ---------------------------------------------------------------------------------------------
@@ -230,7 +304,13 @@ int renet_joint_softmax(float* logits, int ld, int n, int R, int N, const float*
     if (n < 0 || R <= 0 || N <= 0 || ld < N || ld_r < R || !logits || !logits_r || !prob_e) return RENET_ERR_BADARG;
     if (n == 0) return RENET_OK;
     const size_t lds = (size_t)N * sizeof(float);
-    if (lds > 128 * 1024 || R > 1024) return RENET_ERR_UNSUPPORTED;
+    if (R > 1024) return RENET_ERR_UNSUPPORTED;
+    if (lds > 128 * 1024) {                // the row does not fit LDS: two sweeps of it
+        RENET_LAUNCH(joint_softmax_stream_kernel, dim3((unsigned)(n * R)), dim3(1024), 0, (hipStream_t)stream, logits, ld, N,
+                     R, logits_r, ld_r, prob_e);
+        RENET_LAUNCH_CHECK();
+        return RENET_OK;
+    }
     static bool attr_set = false;          // benign race: the attribute is idempotent
     if (!attr_set) {
         hipError_t e = hipFuncSetAttribute((const void*)joint_softmax_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,

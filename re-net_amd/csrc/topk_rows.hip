@@ -36,6 +36,19 @@
 // the phases of a row -- HBM wait, fp64 exps, the barrier-separated chain of steps 3-5 -- overlap with nothing, which is
 // where the time goes (profiles/topk_rows.md: several times one HBM read of the matrix, several times faster than the
 // torch passes).  16 waves per workgroup keep the 16-byte loads of the sweep in flight.  No MFMA: integer and exp work.
+//   renet_topk_rows_wide : the same contract for rows that do not fit LDS (C <= RENET_TOPK_ROWS_WIDE_MAX_C), in two launches:
+//     slices  a (slice, row) grid runs steps 1-5 above -- the same kernel, instantiated with SLICE -- on the columns
+//             [slice * S, slice * S + S) of its row: the piece's own 16-byte alignment, the row's whole list with the columns
+//             outside the piece passed over (so a column is exchanged by the one piece that holds it, once), and leaves in
+//             the workspace its min(k, candidates) best as sorted (key, ~column) entries, its candidate count and its fp64
+//             (max, sum) pair.  S <= 32768, so the 16 + 16 bit packing of the gather holds per piece.
+//     merge   one workgroup per row folds the slices in slice order into a running sorted top-k held one entry per thread:
+//             max(running[i], slice[P - 1 - i]) is a bitonic sequence of the P best of both, and one bitonic merge sorts it
+//             (log2 P exchanges, shuffles inside a wave).  Exact: the row's top-k is contained in the union of the per-slice
+//             top-k, entries are distinct, and per-slice ties already come out lowest column first.  The candidate count
+//             is the sum over slices, the logsumexp the fixed-order fp64 combination of the pairs.
+//   S defaults to an even split of the row into pieces of at most 15360 columns (78 KB of LDS: two workgroups share a CU,
+//   so the phases of one piece overlap with another's); the caller may set it (tests make the pieces small).
 #include "common.h"
 #include <float.h>
 #include <math.h>
@@ -47,6 +60,16 @@ constexpr int TR_WAVES = TR_THREADS / 64;
 constexpr int TR_MAX_C = 32768;          // keys of one row: 128 KB of LDS; the (above, at) counts are packed in 16 + 16 bits
 constexpr int TR_MAX_K = 1024;           // one survivor per thread in the sort and the write
 constexpr int TR_BINS = 2048;            // 11-bit digits (the last one 10)
+constexpr int TRW_MAX_C = RENET_TOPK_ROWS_WIDE_MAX_C;
+constexpr int TRW_MIN_STAGE = 64;        // a caller's piece: [64, TR_MAX_C] columns
+constexpr int TRW_STAGE = 15360;         // the default piece is at most this wide: tr_lds_bytes = 78 KB, two workgroups per CU
+constexpr int TRW_ROWS = 32768;          // rows of one launch of the (slice, row) grid
+
+// what a slice leaves beside its entries
+struct TrSlice {
+    double m, s;                         // sum over the piece of exp(x - m), m its maximum (only with LOGP)
+    long long ncand;                     // its columns that are candidates
+};
 
 // Order-preserving key: never 0 for a real value (0 is the code of a filtered column)
 __device__ __forceinline__ unsigned tr_key(float v) {
@@ -130,15 +153,59 @@ __device__ __forceinline__ void tr_pick(unsigned* hist, int need, int* s_w, int*
     __syncthreads();
 }
 
+// One compare-exchange of a bitonic network over one entry per thread: partners less than a wave apart trade through
+// shuffles, the others through sbuf; `larger`: this end of the pair keeps the larger entry.
+__device__ __forceinline__ unsigned long long tr_exchange(unsigned long long ent, int stride, bool larger,
+                                                          unsigned long long* sbuf, int tid) {
+    unsigned long long other;
+    if (stride < 64) {
+        other = __shfl_xor(ent, stride);
+    } else {
+        __syncthreads();
+        sbuf[tid] = ent;
+        __syncthreads();
+        other = sbuf[tid ^ stride];
+    }
+    return (larger == (ent > other)) ? ent : other;
+}
+
+// thread tid < k writes place tid of the row's result from its sorted entry
 template <bool LOGP>
-__global__ __launch_bounds__(TR_THREADS) void topk_rows_kernel(const float* __restrict__ scores, int ld, int C, int k,
+__device__ __forceinline__ void tr_write(int row, int k, int tid, int nvalid, unsigned long long ent, double lse,
+                                         int32_t* __restrict__ out_idx, float* __restrict__ out_val,
+                                         float* __restrict__ out_logp, int32_t* __restrict__ out_n) {
+    if (tid < k) {                                                       // k <= TR_THREADS
+        const size_t o = (size_t)row * k + tid;
+        if (tid < nvalid) {
+            const float v = tr_value((unsigned)(ent >> 32));
+            out_idx[o] = (int)(0xFFFFFFFFu - (unsigned)ent);
+            out_val[o] = v;
+            if (LOGP) out_logp[o] = v == -INFINITY ? -INFINITY : (float)((double)v - lse);
+        } else {
+            out_idx[o] = -1;
+            out_val[o] = -INFINITY;
+            if (LOGP) out_logp[o] = -INFINITY;
+        }
+    }
+    if (tid == 0) out_n[row] = nvalid;
+}
+
+// SLICE = false: renet_topk_rows, one workgroup per row (grid.x), the results written.  SLICE = true: workgroup
+// (blockIdx.x, row0 + blockIdx.y) takes the columns [blockIdx.x * stage, + stage) of its row and leaves its sorted entries
+// (at most ws_per) and its TrSlice in the workspace; the out_* arrays are not used.
+template <bool LOGP, bool SLICE>
+__global__ __launch_bounds__(TR_THREADS) void topk_rows_kernel(const float* __restrict__ scores, int ld, int C_row, int k,
                                                                const int32_t* __restrict__ cols,
                                                                const int32_t* __restrict__ start,
                                                                const int32_t* __restrict__ count, int len,
                                                                const int32_t* __restrict__ keep,
                                                                int32_t* __restrict__ out_idx, float* __restrict__ out_val,
-                                                               float* __restrict__ out_logp, int32_t* __restrict__ out_n) {
+                                                               float* __restrict__ out_logp, int32_t* __restrict__ out_n,
+                                                               int stage, int row0, unsigned long long* __restrict__ ws_ent,
+                                                               int ws_per, TrSlice* __restrict__ ws_stat) {
     extern __shared__ __attribute__((aligned(16))) unsigned char tr_smem[];
+    const int c0 = SLICE ? (int)blockIdx.x * stage : 0;                  // the first column of this workgroup's piece
+    const int C = SLICE ? min(stage, C_row - c0) : C_row;                // and its width
     const int nalloc = (C + 7) & ~3;                         // the row shifted by at most 3, rounded up to whole groups
     unsigned* keys = reinterpret_cast<unsigned*>(tr_smem);
     unsigned* hist = keys + nalloc;
@@ -148,9 +215,9 @@ __global__ __launch_bounds__(TR_THREADS) void topk_rows_kernel(const float* __re
     int* s_w = reinterpret_cast<int*>(s_m + TR_WAVES);
     int* s_sel = s_w + TR_WAVES;
 
-    const int row = blockIdx.x, tid = threadIdx.x;
+    const int row = SLICE ? row0 + (int)blockIdx.y : (int)blockIdx.x, tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
-    const float* x = scores + (size_t)row * ld;
+    const float* x = scores + (size_t)row * ld + c0;
     // [0, head) scalar up to the first 16-byte aligned element, [head, head + 4 * nvec) as float4, the rest scalar; column c
     // lives at keys[off + c], so that column head is the start of a group
     const int head = min(C, (int)((4 - (((uintptr_t)x >> 2) & 3)) & 3));
@@ -218,11 +285,19 @@ __global__ __launch_bounds__(TR_THREADS) void topk_rows_kernel(const float* __re
         double S = lane < TR_WAVES ? s_s[lane] * tr_exp(mw, M) : 0.0;
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) S += __shfl_xor(S, o);
-        if (lane == 0) s_s[TR_WAVES] = log(S) + (double)M;
+        if (lane == 0) {
+            if (SLICE) {                                                 // the piece's pair: the merge forms the row's
+                TrSlice* st = ws_stat + (size_t)row * gridDim.x + blockIdx.x;
+                st->m = (double)M;
+                st->s = S;
+            } else {
+                s_s[TR_WAVES] = log(S) + (double)M;
+            }
+        }
     }
     for (int j = l_beg + tid, c = l_first; j < l_end;) {
-        if (c != kept && c >= 0 && c < C) {                              // (columns outside the row are ignored)
-            const unsigned old = atomicExch(&keys[off + c], 0u);
+        if (c != kept && c >= c0 && c < c0 + C) {                        // (columns outside the row, or the piece, are passed over)
+            const unsigned old = atomicExch(&keys[off + c - c0], 0u);
             if (old) atomicSub(&hist[old >> 21], 1u);
         }
         j += TR_THREADS;
@@ -308,35 +383,68 @@ __global__ __launch_bounds__(TR_THREADS) void topk_rows_kernel(const float* __re
     while (npow < n_take) npow <<= 1;
     unsigned long long ent = tid < n_take ? sbuf[tid] : 0ull;            // 0: below every entry (their key halves are >= 1)
     for (int size = 2; size <= npow; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            unsigned long long other;
-            if (stride < 64) {
-                other = __shfl_xor(ent, stride);
-            } else {
-                __syncthreads();
-                sbuf[tid] = ent;
-                __syncthreads();
-                other = sbuf[tid ^ stride];
-            }
-            const bool larger = ((tid & size) == 0) == ((tid & stride) == 0);    // this end of the pair keeps the larger
-            ent = (larger == (ent > other)) ? ent : other;
-        }
+        for (int stride = size >> 1; stride > 0; stride >>= 1)
+            ent = tr_exchange(ent, stride, ((tid & size) == 0) == ((tid & stride) == 0), sbuf, tid);
     }
 
-    if (tid < k) {                                                       // k <= TR_THREADS
-        const size_t o = (size_t)row * k + tid;
-        if (tid < nvalid) {
-            const float v = tr_value((unsigned)(ent >> 32));
-            out_idx[o] = (int)(0xFFFFFFFFu - (unsigned)ent);
-            out_val[o] = v;
-            if (LOGP) out_logp[o] = v == -INFINITY ? -INFINITY : (float)((double)v - s_s[TR_WAVES]);
-        } else {
-            out_idx[o] = -1;
-            out_val[o] = -INFINITY;
-            if (LOGP) out_logp[o] = -INFINITY;
+    if (SLICE) {                                                         // nvalid <= min(k, stage) = ws_per
+        const size_t piece = (size_t)row * gridDim.x + blockIdx.x;
+        if (tid < nvalid) ws_ent[piece * ws_per + tid] = ent - (unsigned)c0;     // ~column of the row: no borrow, c0 + c < C_row
+        if (tid == 0) ws_stat[piece].ncand = ncand;
+    } else {
+        tr_write<LOGP>(row, k, tid, nvalid, ent, LOGP ? s_s[TR_WAVES] : 0.0, out_idx, out_val, out_logp, out_n);
+    }
+}
+
+// The merge of renet_topk_rows_wide: one workgroup of P = blockDim.x threads (a power of two, max(k, 64) <= P <= 1024) per
+// row folds the nsl slices' sorted entries, in slice order, into the row's sorted k best, and writes the row's results.
+template <bool LOGP>
+__global__ __launch_bounds__(TR_THREADS) void topk_rows_merge_kernel(const unsigned long long* __restrict__ ws_ent, int ws_per,
+                                                                     const TrSlice* __restrict__ ws_stat, int nsl, int k,
+                                                                     int32_t* __restrict__ out_idx,
+                                                                     float* __restrict__ out_val,
+                                                                     float* __restrict__ out_logp,
+                                                                     int32_t* __restrict__ out_n) {
+    __shared__ unsigned long long sbuf[TR_MAX_K];
+    __shared__ double s_lse;
+    __shared__ int s_ncand;
+    const int row = blockIdx.x, tid = threadIdx.x, P = blockDim.x;
+    const TrSlice* st = ws_stat + (size_t)row * nsl;
+    const unsigned long long* e = ws_ent + (size_t)row * nsl * ws_per;
+    if (tid < 64) {                                                      // wave 0: lane l takes the slices l, l + 64, ...
+        int nc = 0;
+        double M = -DBL_MAX, S = 0.0;
+        for (int s = tid; s < nsl; s += 64) {
+            nc += (int)st[s].ncand;                                      // (C_row < 2^31)
+            if (LOGP) M = fmax(M, st[s].m);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            nc += __shfl_xor(nc, o);
+            if (LOGP) M = fmax(M, __shfl_xor(M, o));
+        }
+        if (LOGP) {
+            for (int s = tid; s < nsl; s += 64) S += st[s].s * exp(st[s].m - M);
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) S += __shfl_xor(S, o);
+        }
+        if (tid == 0) {
+            s_ncand = nc;
+            s_lse = LOGP ? log(S) + M : 0.0;
         }
     }
-    if (tid == 0) out_n[row] = nvalid;
+    int cnt = min(k, (int)st[0].ncand);
+    unsigned long long ent = tid < cnt ? e[tid] : 0ull;                  // 0: below every entry
+    for (int s = 1; s < nsl; ++s) {
+        cnt = min(k, (int)st[s].ncand);
+        if (cnt == 0) continue;                                          // (the same in every thread)
+        const int j = P - 1 - tid;
+        const unsigned long long other = j < cnt ? e[(size_t)s * ws_per + j] : 0ull;
+        ent = ent > other ? ent : other;                                 // the P best of both, a bitonic sequence
+        for (int stride = P >> 1; stride > 0; stride >>= 1) ent = tr_exchange(ent, stride, (tid & stride) == 0, sbuf, tid);
+    }
+    __syncthreads();
+    tr_write<LOGP>(row, k, tid, min(k, s_ncand), ent, s_lse, out_idx, out_val, out_logp, out_n);
 }
 
 // dynamic LDS of one workgroup: keys, histogram, sort buffer, the reduction slots (every part a multiple of 16 bytes)
@@ -344,24 +452,41 @@ inline size_t tr_lds_bytes(int C) {
     return (size_t)((C + 7) & ~3) * 4 + TR_BINS * 4 + TR_MAX_K * 8 + (TR_WAVES + 2) * 8 + TR_WAVES * 4 + TR_WAVES * 4 + 16;
 }
 
+// the argument checks both entries share, before anything depends on the width
+inline bool tr_badarg(int ld, int n, int C, int k, const int32_t* cols, const int32_t* start, const int32_t* count, int len) {
+    if (n < 0 || C < 1 || ld < C || k < 1 || k > TR_MAX_K || len < 0) return true;
+    // a list is (cols, start, count) with the length of its table, or nothing at all
+    return (cols || start || count) && (!cols || !start || !count);
+}
+
+// every instantiation may ask for the LDS of the widest piece
+template <bool LOGP, bool SLICE>
+inline hipError_t tr_set_lds() {
+    return hipFuncSetAttribute((const void*)topk_rows_kernel<LOGP, SLICE>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)tr_lds_bytes(TR_MAX_C));
+}
+
+// the piece width of a row of C columns: the caller's, or an even split into pieces of at most TRW_STAGE columns that start
+// on multiples of 4 columns
+inline int trw_stage(int C, int stage_cols) {
+    if (stage_cols) return stage_cols;
+    const int pieces = (C + TRW_STAGE - 1) / TRW_STAGE;
+    return ((C + pieces - 1) / pieces + 3) & ~3;
+}
+
 }  // namespace
 
 int renet_topk_rows(const float* scores, int ld, int n, int C, int k, const int32_t* cols, const int32_t* start,
                     const int32_t* count, int len, const int32_t* keep, int32_t* out_idx, float* out_val, float* out_logp,
                     int32_t* out_n, void* stream) {
-    if (n < 0 || C < 1 || ld < C || k < 1 || k > TR_MAX_K || len < 0) return RENET_ERR_BADARG;
-    // a list is (cols, start, count) with the length of its table, or nothing at all
-    if ((cols || start || count) && (!cols || !start || !count)) return RENET_ERR_BADARG;
+    if (tr_badarg(ld, n, C, k, cols, start, count, len)) return RENET_ERR_BADARG;
     if (C > TR_MAX_C) return RENET_ERR_UNSUPPORTED;
     if (n == 0) return RENET_OK;
     if (!scores || !out_idx || !out_val || !out_n) return RENET_ERR_BADARG;
     static bool attr_set = false;          // benign race: the attribute is idempotent
     if (!attr_set) {
-        const int most = (int)tr_lds_bytes(TR_MAX_C);
-        hipError_t e = hipFuncSetAttribute((const void*)topk_rows_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           most);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute((const void*)topk_rows_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, most);
+        hipError_t e = tr_set_lds<true, false>();
+        if (e == hipSuccess) e = tr_set_lds<false, false>();
         if (e != hipSuccess) return (int)e;
         attr_set = true;
     }
@@ -369,11 +494,63 @@ int renet_topk_rows(const float* scores, int ld, int n, int C, int k, const int3
     const size_t lds = tr_lds_bytes(C);
     hipStream_t st = (hipStream_t)stream;
 #define TR_GO(LOGP)                                                                                                     \
-    RENET_LAUNCH((topk_rows_kernel<LOGP>), grid, blk, lds, st, scores, ld, C, k, cols, start, count, len, keep, out_idx,   \
-                 out_val, out_logp, out_n)
+    RENET_LAUNCH((topk_rows_kernel<LOGP, false>), grid, blk, lds, st, scores, ld, C, k, cols, start, count, len, keep,     \
+                 out_idx, out_val, out_logp, out_n, 0, 0, nullptr, 0, nullptr)
     if (out_logp) TR_GO(true);
     else TR_GO(false);
 #undef TR_GO
+    RENET_LAUNCH_CHECK();
+    return RENET_OK;
+}
+
+size_t renet_topk_rows_wide_workspace(int n, int C, int k, int stage_cols) {
+    if (n < 1 || C < 1 || C > TRW_MAX_C || k < 1 || k > TR_MAX_K) return 0;
+    if (stage_cols && (stage_cols < TRW_MIN_STAGE || stage_cols > TR_MAX_C)) return 0;
+    const int stage = trw_stage(C, stage_cols), nsl = (C + stage - 1) / stage;
+    return (size_t)n * nsl * ((size_t)min(k, stage) * sizeof(unsigned long long) + sizeof(TrSlice));
+}
+
+int renet_topk_rows_wide(const float* scores, int ld, int n, int C, int k, const int32_t* cols, const int32_t* start,
+                         const int32_t* count, int len, const int32_t* keep, int32_t* out_idx, float* out_val,
+                         float* out_logp, int32_t* out_n, int stage_cols, void* workspace, size_t workspace_bytes,
+                         void* stream) {
+    if (tr_badarg(ld, n, C, k, cols, start, count, len)) return RENET_ERR_BADARG;
+    if (stage_cols && (stage_cols < TRW_MIN_STAGE || stage_cols > TR_MAX_C)) return RENET_ERR_BADARG;
+    if (C > TRW_MAX_C) return RENET_ERR_UNSUPPORTED;
+    if (n == 0) return RENET_OK;
+    if (!scores || !out_idx || !out_val || !out_n) return RENET_ERR_BADARG;
+    if (!workspace || ((uintptr_t)workspace & 7) || workspace_bytes < renet_topk_rows_wide_workspace(n, C, k, stage_cols))
+        return RENET_ERR_WORKSPACE;
+    static bool attr_set = false;          // benign race: the attribute is idempotent
+    if (!attr_set) {
+        hipError_t e = tr_set_lds<true, true>();
+        if (e == hipSuccess) e = tr_set_lds<false, true>();
+        if (e != hipSuccess) return (int)e;
+        attr_set = true;
+    }
+    const int stage = trw_stage(C, stage_cols), nsl = (C + stage - 1) / stage, per = min(k, stage);
+    unsigned long long* ws_ent = (unsigned long long*)workspace;         // [n, nsl, per] entries, then [n, nsl] TrSlice
+    TrSlice* ws_stat = (TrSlice*)(ws_ent + (size_t)n * nsl * per);
+    const size_t lds = tr_lds_bytes(min(stage, C));
+    hipStream_t st = (hipStream_t)stream;
+    for (int row0 = 0; row0 < n; row0 += TRW_ROWS) {                     // (grid.y holds 65535 rows at most)
+        const dim3 grid(nsl, min(n - row0, TRW_ROWS)), blk(TR_THREADS);
+#define TR_GO(LOGP)                                                                                                     \
+    RENET_LAUNCH((topk_rows_kernel<LOGP, true>), grid, blk, lds, st, scores, ld, C, k, cols, start, count, len, keep,      \
+                 nullptr, nullptr, nullptr, nullptr, stage, row0, ws_ent, per, ws_stat)
+        if (out_logp) TR_GO(true);
+        else TR_GO(false);
+#undef TR_GO
+        RENET_LAUNCH_CHECK();
+    }
+    int P = 64;                                                          // one entry per thread: the power of two >= k
+    while (P < k) P <<= 1;
+    if (out_logp)
+        RENET_LAUNCH((topk_rows_merge_kernel<true>), dim3(n), dim3(P), 0, st, ws_ent, per, ws_stat, nsl, k, out_idx, out_val,
+                     out_logp, out_n);
+    else
+        RENET_LAUNCH((topk_rows_merge_kernel<false>), dim3(n), dim3(P), 0, st, ws_ent, per, ws_stat, nsl, k, out_idx,
+                     out_val, out_logp, out_n);
     RENET_LAUNCH_CHECK();
     return RENET_OK;
 }

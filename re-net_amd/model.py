@@ -650,7 +650,7 @@ def _joint_topk_many_body(self, ents, prob, subject=True):
         logits = _linear_eval(self.linear, feat)                                     # [n*R, N_ent]
         logits_r = _linear_eval(self.linear_r, torch.cat((ent_rows, s_q), dim=1))    # [n, R]
         prob_e = prob[es_t].contiguous()
-        if self.reference_shadowing or self.in_dim * 4 > 128 * 1024 or R > 1024 or not logits.is_cuda or \
+        if self.reference_shadowing or R > 1024 or not logits.is_cuda or \
                 os.environ.get('RENET_TOPK') == 'torch':
             # the ORDER of an unsorted torch.topk result is observable through the shadowing quirk: keep
             # the reference's op sequence there
@@ -720,7 +720,7 @@ def _scaled_softmax_topk(logits, scale, k):
     """top-k of softmax(logits, dim 1) * scale[:, None] over the WHOLE block -> (values [k], flat indices [k]).  The block is
     overwritten on the GPU (fused joint-softmax with one "relation" per row, then the radix select over the block as one row)."""
     rows, n = logits.shape
-    if logits.is_cuda and n * 4 <= 128 * 1024 and os.environ.get('RENET_TOPK') != 'torch':
+    if logits.is_cuda and os.environ.get('RENET_TOPK') != 'torch':
         K.joint_softmax(logits, 1, torch.zeros(rows, 1, device=logits.device), scale.contiguous())
         vals, idx = K.topk_positive(logits.view(1, rows * n), k)
         return vals[0], idx[0]
@@ -1257,7 +1257,8 @@ def _evaluate_all_stream(self, total_data, s_history, o_history, global_model, a
 def _predict_topk_batch(self, triplets, s_hist, o_hist, global_model, k=10, all_triplets=None, setting='raw',
                         keep_gold=False):
     """The k best-ranked subjects of (?, r, o, t) and objects of (s, r, ?, t) for the n quadruples of ONE timestamp, from one
-    predict_batch and one renet_topk_rows launch per direction (csrc/topk_rows.hip; extension of the reference API): returns
+    predict_batch and one renet_hip.topk_rows call per direction (csrc/topk_rows.hip: renet_topk_rows up to 32768 entities,
+    renet_topk_rows_wide beyond, up to 2^20, with the same results; extension of the reference API): returns
     {'sub': (idx, score, logp, n_valid), 'ob': (...)} as device tensors, row i belonging to triplets[i] -- idx int32 [n, k] by
     score descending, then entity id ascending, score and logp (log-softmax over ALL entities) beside it, n_valid [n] the
     number of filled slots (the rest: idx -1, -inf).  setting (one of SETTINGS) says which known completions are no
@@ -1723,7 +1724,8 @@ def _predict_events_observed(self, obs, idx, k=10, all_triplets=None, setting='r
     evaluate_events_observed.  n_valid = min(k, candidates); the slots behind it hold -1, -1, -inf.  Per sub-block one
     renet_topk_rows launch gives every relation row's k best entities, and the k best of those R * k candidates are taken
     (a pair outside its own row's k best by SCORE cannot enter: exact unless two distinct scores of a row round to one J at
-    that row's k-th place).  k <= 1024 and N_ent <= 32768 (renet_topk_rows)."""
+    that row's k-th place).  k <= 1024; N_ent <= 2^20 (renet_hip.topk_rows: beyond 32768 entities the rows are taken in
+    pieces by renet_topk_rows_wide, with the same results)."""
     if setting not in SETTINGS:
         raise ValueError('setting must be one of %s, not %r' % (', '.join(SETTINGS), setting))
     store, idx = _event_setup(self, obs, idx)

@@ -149,6 +149,9 @@ _SIGNATURES = {
                                  c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     'renet_topk_rows': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'renet_topk_rows_wide_workspace': (c_size_t, [c_int, c_int, c_int, c_int]),
+    'renet_topk_rows_wide': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     'renet_joint_row_offsets': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     'renet_joint_rank_rows': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
@@ -1468,34 +1471,69 @@ def rank_rows3(scores, label, cols_a, start_a, count_a, cols_t, start_t, count_t
     return counts, row_loss
 
 
-def topk_rows(scores, k, cols=None, start=None, count=None, keep=None, want_logp=True):
-    """renet_topk_rows on scores [n, C] (fp32, unit inner stride; not written): the k best candidates of every row from ONE
-    read of the scores -> (idx int32 [n, k], val [n, k], logp [n, k] or None, n_valid int32 [n]), by score descending, then
-    column ascending (deterministic).  The candidates of row i are all columns minus cols[start[i] : start[i] + count[i]] (a
-    range of a resident column table, filter_index.FilterIndex.ranges; int32), a listed column equal to keep[i] (int32 [n])
-    staying in; three Nones (or an empty table): no list.  logp = val - logsumexp(whole row), listed columns included.
-    n_valid = min(k, candidates); the slots behind it hold idx -1, val -inf, logp -inf.  1 <= k <= 1024, C <= 32768."""
+TOPK_ROWS_MAX_C = 32768                 # renet_topk_rows stages the whole row in LDS; wider rows go to renet_topk_rows_wide
+TOPK_ROWS_WIDE_MAX_C = 1 << 20          # RENET_TOPK_ROWS_WIDE_MAX_C of include/renet_hip.h
+_topk_wide_ws = {}                      # device -> the workspace of renet_topk_rows_wide (the largest asked for so far)
+
+
+def _topk_rows_front(what, scores, k, cols, start, count, keep, want_logp):
+    """The checks and the outputs the two top-k entries share -> (n, C, k, ld, list arguments, idx, val, logp, n_valid)."""
     if not (scores.is_cuda and scores.dtype == torch.float32 and scores.dim() == 2 and scores.stride(1) == 1):
-        raise RenetHipError('topk_rows needs a 2-D float32 device tensor with unit inner stride')
+        raise RenetHipError(what + ' needs a 2-D float32 device tensor with unit inner stride')
     n, c = scores.shape
     if cols is None and start is None and count is None:
         lists = [None, None, None, 0]
     elif cols is None or start is None or count is None or start.numel() != n or count.numel() != n:
-        raise RenetHipError('topk_rows: a filter list is (cols, start [n], count [n])')
+        raise RenetHipError(what + ': a filter list is (cols, start [n], count [n])')
     else:                               # (an empty table has no storage to point at: no list)
         lists = [_i32(cols), _i32(start), _i32(count), cols.numel()] if cols.numel() else [None, None, None, 0]
     if keep is not None and keep.numel() != n:
-        raise RenetHipError('topk_rows: shape mismatch')
+        raise RenetHipError(what + ': shape mismatch')
     k = int(k)
     idx = torch.empty(n, k, device=scores.device, dtype=torch.int32)
     val = torch.empty(n, k, device=scores.device, dtype=torch.float32)
     logp = torch.empty(n, k, device=scores.device, dtype=torch.float32) if want_logp else None
     n_valid = torch.empty(n, device=scores.device, dtype=torch.int32)
+    return n, c, k, max(_ld(scores), c) if n == 1 else _ld(scores), lists, idx, val, logp, n_valid
+
+
+def topk_rows(scores, k, cols=None, start=None, count=None, keep=None, want_logp=True):
+    """The k best candidates of every row of scores [n, C] (fp32, unit inner stride; not written) from ONE read of the scores
+    -> (idx int32 [n, k], val [n, k], logp [n, k] or None, n_valid int32 [n]), by score descending, then column ascending
+    (deterministic).  The candidates of row i are all columns minus cols[start[i] : start[i] + count[i]] (a range of a
+    resident column table, filter_index.FilterIndex.ranges; int32), a listed column equal to keep[i] (int32 [n]) staying in;
+    three Nones (or an empty table): no list.  logp = val - logsumexp(whole row), listed columns included.
+    n_valid = min(k, candidates); the slots behind it hold idx -1, val -inf, logp -inf.  1 <= k <= 1024.
+    C <= 32768: renet_topk_rows (the row staged in one CU's LDS); wider, up to 2^20 columns: renet_topk_rows_wide (the row in
+    pieces, merged per row: topk_rows_wide below), with the same results."""
+    if scores.dim() == 2 and scores.shape[1] > TOPK_ROWS_MAX_C:
+        return topk_rows_wide(scores, k, cols, start, count, keep, want_logp)
+    n, c, k, ld, lists, idx, val, logp, n_valid = _topk_rows_front('topk_rows', scores, k, cols, start, count, keep,
+                                                                   want_logp)
     t0 = _timed()
-    _check(lib().renet_topk_rows(scores.data_ptr(), max(_ld(scores), c) if n == 1 else _ld(scores), n, c, k, *lists,
-                                 _i32(keep), idx.data_ptr(), val.data_ptr(), _f32(logp), n_valid.data_ptr(), _stream()),
-           'topk_rows')
+    _check(lib().renet_topk_rows(scores.data_ptr(), ld, n, c, k, *lists, _i32(keep), idx.data_ptr(), val.data_ptr(),
+                                 _f32(logp), n_valid.data_ptr(), _stream()), 'topk_rows')
     _timed_end(t0, 'topk_rows', nbytes=float(n * c * 4))
+    return idx, val, logp, n_valid
+
+
+def topk_rows_wide(scores, k, cols=None, start=None, count=None, keep=None, want_logp=True, stage_cols=0):
+    """renet_topk_rows_wide: topk_rows' arguments and results for any C <= 2^20, the row taken in pieces of stage_cols columns
+    (0: the library's choice; else 64 .. 32768 -- tests make the pieces small).  The workspace (the pieces' entries: n *
+    pieces * (min(k, stage_cols) * 8 + 24) bytes) is kept per device, grown to the largest size asked for, and reused by every
+    later call: calls on one device must be ordered on one stream."""
+    n, c, k, ld, lists, idx, val, logp, n_valid = _topk_rows_front('topk_rows_wide', scores, k, cols, start, count, keep,
+                                                                   want_logp)
+    stage_cols = int(stage_cols)
+    nbytes = lib().renet_topk_rows_wide_workspace(n, c, k, stage_cols)
+    ws = _topk_wide_ws.get(scores.device)
+    if nbytes and (ws is None or ws.numel() * 8 < nbytes):
+        ws = _topk_wide_ws[scores.device] = torch.empty(nbytes // 8, device=scores.device, dtype=torch.int64)
+    t0 = _timed()
+    _check(lib().renet_topk_rows_wide(scores.data_ptr(), ld, n, c, k, *lists, _i32(keep), idx.data_ptr(), val.data_ptr(),
+                                      _f32(logp), n_valid.data_ptr(), stage_cols, None if ws is None else ws.data_ptr(),
+                                      nbytes, _stream()), 'topk_rows_wide')
+    _timed_end(t0, 'topk_rows_wide', nbytes=float(n * c * 4))
     return idx, val, logp, n_valid
 
 
@@ -1566,7 +1604,8 @@ def joint_rank_rows(scores, num_rels, off, group, gold_r, gold_c, cols_a=None, s
 
 
 def joint_softmax(logits, num_rels, logits_r, prob_e):
-    """logits [n * R, N] -> IN PLACE softmax(row) * softmax(logits_r[e])[r] * prob_e[e]  (model.py:205-209)."""
+    """logits [n * R, N] -> IN PLACE softmax(row) * softmax(logits_r[e])[r] * prob_e[e]  (model.py:205-209).  Any N (rows up
+    to 32768 columns are staged in LDS, wider ones streamed twice); R <= 1024."""
     nr, n_ent = logits.shape
     n = nr // num_rels
     if nr != n * num_rels or tuple(logits_r.shape) != (n, num_rels) or prob_e.numel() != n:
