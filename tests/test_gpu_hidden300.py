@@ -113,8 +113,11 @@ def _case(dev):
 
 def _drop_mask(dev, rows, p, seed):
     """The multipliers of the float4-group mask of a [rows, 300] tensor (renet_dropout on ones: group = flat index / 4)."""
+    import dropout_masks
     import ops
-    return ops.DropoutFn.apply(torch.ones(rows, D, device=dev), p, seed).cpu().numpy().astype(np.float64)
+    mask = ops.DropoutFn.apply(torch.ones(rows, D, device=dev), p, seed).cpu().numpy().astype(np.float64)
+    assert np.array_equal(mask, dropout_masks.flat_mask(rows, D, seed, p))       # the host statement of common.h
+    return mask
 
 
 @pytest.mark.parametrize('drop_p', [0.0, 0.5])
