@@ -729,6 +729,20 @@ int renet_build_batch_both(const RenetStoreDev* store, const int32_t* idx_dev, i
                            size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * HISTORY WINDOWS of arbitrary (entity, as_of) queries against the resident history index (csrc/builder_query.hip; the
+ * host statement is preprocess.HistoryIndex.lookup, element for element).  ent_ptr0 / ent_ptr1 [num_ent + 1]: the snapshot
+ * range of every entity in role 0 (subject histories) / 1 (object histories), snap_t0 / snap_t1 the snapshot timestamps of
+ * RenetStoreDev.  ent[2][n]: per query its subject (row 0) and its object (row 1); as_of[n].  For pair (role, i), with sid
+ * the first snapshot of the entity's range whose timestamp is >= as_of[i] (binary search):
+ *     h_first[role][i] = max(range start, sid - history_len),  h_count[role][i] = sid - h_first[role][i]
+ * and (0, 0) for an entity outside [0, num_ent): an absent side.  h_first / h_count [2][n] are what RenetStoreDev takes for
+ * a store whose quadruples are the queries.  ONE launch over the 2 n pairs, no workspace, no synchronisation.  It exists so
+ * that queries which already are device tensors become a builder batch without a host round trip. */
+int renet_query_histories(const int32_t* ent_ptr0, const int32_t* ent_ptr1, const int32_t* snap_t0, const int32_t* snap_t1,
+                          int num_ent, int history_len, const int32_t* ent, const int32_t* as_of, int n, int32_t* h_first,
+                          int32_t* h_count, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * DEVICE builder for the FULL-GRAPH batches of the global model (graph.build_full_graphs; reference Aggregator.py:44-55 /
  * 87-98: dgl.batch of the whole graphs of a list of timestamps).  Resident: the per-timestamp node lists and the facts with
  * LOCAL endpoints (graph.TimeGraph.ent / ls / r / lo, concatenated in graph_dict order).  tidx_dev[G] (device int32,

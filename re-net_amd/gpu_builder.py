@@ -17,6 +17,10 @@ Grouped inference batches (graph.build_batch(group=...), RGCNAggregator.forward_
 `GroupedBatchStore` uploads one call's s / r / group / FlatHistory, `GroupedDeviceBatch` is the batch of ONE direction with
 a member graph per (group, timestamp) (renet_build_batch_grouped), bit-identical again (tests/test_gpu_grouped_builder.py).
 
+Open queries of the observed pass (`QueryStore`, made by ObservedStore.queries): a store whose positions are arbitrary
+(s, r, o, t) queries with histories as of a timestamp <= t, the windows from one renet_query_histories launch
+(csrc/builder_query.hip) on the resident tables; DeviceBatch runs on it as on the stream itself.
+
 Layout of this file: the ctypes mirrors of the structs and count slots of include/renet_hip.h (tests/test_host_cpu.py holds
 them to the header); `_Store`, the base of the resident stores, and the per-graph_dict cache `_cached_store`; `_launch`,
 the one place that lays out, allocates and calls a builder front; `_PendingBatch`, the life cycle of a batch from the
@@ -152,6 +156,7 @@ class DeviceStore(GraphDeviceStore):
             self.t['snap_t%d' % r] = _i32(h.snap_t, device)
             self.t['snap_ptr%d' % r] = _i32(h.snap_ptr, device)
             self.t['nbr_o%d' % r] = _i32(h.nbr_o, device)
+            self.t['ent_ptr%d' % r] = _i32(h.ent_ptr, device)          # (renet_query_histories: QueryStore below)
         self.history_len = int(hist_s.history_len)
         sd = _StoreDev()
         for n in ('q_s', 'q_r', 'q_o', 'times', 'trip_ptr', 'trip_s', 'trip_r', 'trip_o', 'glob_times'):
@@ -176,6 +181,11 @@ class ObservedStore(DeviceStore):
         self.obs, self.quads = obs, obs.allq
         ts = sorted(int(t) for t in global_emb.keys())
         self.glob = torch.stack([torch.as_tensor(global_emb[t]).detach().reshape(h_dim).float() for t in ts]).to(device)
+
+    def queries(self, quads, as_of=None, stream=None):
+        """The QueryStore of the queries `quads` [n, 4] = (s, r, o, t) on top of this store: histories as of `as_of` (None:
+        each query's own t), -1 for an absent subject or object."""
+        return QueryStore(self, quads, as_of, stream)
 
 
 def _cached_store(cache, graph_dict, device, stamp, make):
@@ -254,6 +264,103 @@ class ListBatchStore(object):
 
     def _give_pinned(self, buf):
         self.base._give_pinned(buf)
+
+
+class QueryStore(ListBatchStore):
+    """An observed store whose positions are QUERIES (s, r, o, t) that need not be facts of the stream: its own q_s, q_r, q_o
+    and history windows h_first / h_count on top of the resident tables of an ObservedStore (snapshot tables, graph store,
+    glob_times, `glob`, capacities, pinned count buffers: the base's).  The windows come from renet_query_histories (ONE
+    launch): per query and role the last <= history_len snapshots of its entity with snap_t < as_of; glob_row of a history
+    step follows from the step's own timestamp, so a query past the end of the stream needs no new row of the global table.
+    The encoder, score, rank and top-k path of the observed pass runs on it with idx = arange(n_quads), unmodified.
+
+    quads: int [n, 4] -- a host array (validated here: ValueError for an id out of range or as_of > t) or a device int32
+    tensor, which is NOT read back: there an entity id outside [0, num_ent) counts as absent and the relation is clamped
+    into range, so that no kernel indexes out of bounds (with as_of given, one flag comes back for the as_of <= t check).
+    as_of: None (the query's own t), a scalar or [n].  A subject or object of -1 is an ABSENT side: its sequence is empty
+    (h_count = 0) and the builder gathers entity 0 in its place; `quads` (the host copy, read back on first use for a device
+    tensor) keeps the -1, which addresses no filter list."""
+
+    def __init__(self, base, quads, as_of=None, stream=None):
+        self.base = base
+        self.device, self.num_ent, self.num_rels = base.device, base.num_ent, base.num_rels
+        self.glob, self.history_len, self.facts = base.glob, base.history_len, base.quads
+        N, R = self.num_ent, self.num_rels
+        st = stream if stream is not None else torch.cuda.current_stream()
+        on_dev = isinstance(quads, torch.Tensor) and quads.is_cuda
+        if on_dev:
+            if quads.dtype != torch.int32 or quads.dim() != 2 or quads.shape[1] != 4:
+                raise ValueError('device queries are an int32 [n, 4] tensor')
+            n = int(quads.shape[0])
+            self._host, self._quads_dev = None, quads
+            with torch.cuda.stream(st):
+                s, r, o, t = quads.t().contiguous()
+                r = r.clamp(0, R - 1)
+                a = t
+                if as_of is not None:
+                    a = torch.as_tensor(as_of).to(self.device).to(torch.int32).reshape(-1).expand(n).contiguous()
+                    if n and bool((a > t).any()):
+                        raise ValueError('as_of later than the query\'s own timestamp')
+        else:
+            q = np.asarray(quads.cpu() if isinstance(quads, torch.Tensor) else quads, dtype=np.int64).reshape(-1, 4)
+            n = len(q)
+            a = q[:, 3] if as_of is None else np.broadcast_to(
+                np.asarray(as_of.cpu() if isinstance(as_of, torch.Tensor) else as_of, dtype=np.int64).reshape(-1), (n,))
+            if n:
+                if q[:, [0, 2]].min() < -1 or q[:, [0, 2]].max() >= N:
+                    raise ValueError('query entity outside [0, num_ent) (-1: an absent side)')
+                if q[:, 1].min() < 0 or q[:, 1].max() >= R:
+                    raise ValueError('query relation outside [0, num_rels)')
+                if np.any(a > q[:, 3]):
+                    raise ValueError('as_of later than the query\'s own timestamp')
+                _check_int32('timestamps', q[:, 3])
+                if a.min() < -2 ** 31:
+                    raise ValueError('as_of must fit int32')
+            self._host, self._quads_dev = q, None
+            with torch.cuda.stream(st):
+                up = torch.from_numpy(np.ascontiguousarray(np.concatenate((q.T, a[None, :])), dtype=np.int32))
+                up = up.to(self.device, non_blocking=True)              # [5, n]: ONE upload, rows contiguous
+                s, r, o, t, a = up
+        if n == 0:
+            raise ValueError('no queries')
+        with torch.cuda.stream(st):
+            ent = torch.stack((s, o))                                   # [2, n]: the entity of role 0 / 1
+            self.present = (ent >= 0) & (ent < N)
+            gather = torch.where(self.present, ent, 0)                  # (an absent side gathers entity 0)
+            win = K.query_histories((base.t['ent_ptr0'], base.t['ent_ptr1']), (base.t['snap_t0'], base.t['snap_t1']), N,
+                                    self.history_len, ent, a)
+        self.t = dict(q_s=gather[0], q_r=r.contiguous(), q_o=gather[1], h_first0=win[0, 0], h_first1=win[0, 1],
+                      h_count0=win[1, 0], h_count1=win[1, 1], t=t, as_of=a)
+        sd = _StoreDev()
+        for f in ('q_s', 'q_r', 'q_o'):
+            setattr(sd, f, self.t[f].data_ptr())
+        for f in ('h_first', 'h_count'):
+            setattr(sd, f, (_P * 2)(self.t[f + '0'].data_ptr(), self.t[f + '1'].data_ptr()))
+        for f in ('snap_t', 'snap_ptr', 'nbr_o'):
+            setattr(sd, f, (_P * 2)(base.t[f + '0'].data_ptr(), base.t[f + '1'].data_ptr()))
+        for f in ('times', 'trip_ptr', 'trip_s', 'trip_r', 'trip_o', 'glob_times'):
+            setattr(sd, f, base.t[f].data_ptr())
+        sd.T, sd.n_glob, sd.n_facts = base.T, base.n_glob, base.n_facts
+        sd.num_ent, sd.num_rels = N, R
+        self.c = sd
+        self.n_quads = n
+
+    @property
+    def quads(self):
+        """The host copy of the queries, int64 [n, 4], absent sides as -1 (a device tensor is read back on first use)."""
+        if self._host is None:
+            self._host = self._quads_dev.cpu().numpy().astype(np.int64)
+        return self._host
+
+    def sides_present(self):
+        """(any subject present, any object present): a side that no query has needs no rows at all."""
+        if self._host is not None:
+            return bool((self._host[:, 0] >= 0).any()), bool((self._host[:, 2] >= 0).any())
+        return tuple(bool(x) for x in self.present.any(dim=1).cpu())
+
+    # filter_index.filter_index_for caches on its owner: the index of the base stream's facts belongs to the base store
+    _filter_index = property(lambda self: getattr(self.base, '_filter_index', None),
+                             lambda self, v: setattr(self.base, '_filter_index', v))
 
 
 MAX_GROUPED = 4096           # sequences per grouped batch (one workgroup sorts their lengths)

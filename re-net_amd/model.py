@@ -1715,7 +1715,7 @@ def _evaluate_events_observed(self, obs, idx, all_triplets=None, block_floats=1 
     return {'pair': ranks[0], 'relation': ranks[1], 'logp': back[12].astype(np.float32)}
 
 
-def _predict_events_observed(self, obs, idx, k=10, all_triplets=None, setting='raw'):
+def _predict_events_observed(self, obs, idx, k=10, all_triplets=None, setting='raw', sides=('sub', 'ob')):
     """The k most probable events of the stream positions idx under observed histories: {'ob': (rel int32 [n, k], ent int32
     [n, k], logp [n, k], n_valid int32 [n]), 'sub': (...)} as device tensors -- for 'ob' the pairs (r, o) of the position's
     subject, for 'sub' the pairs (r, s) of its object, by joint log-probability J descending, then relation, then entity
@@ -1725,18 +1725,22 @@ def _predict_events_observed(self, obs, idx, k=10, all_triplets=None, setting='r
     renet_topk_rows launch gives every relation row's k best entities, and the k best of those R * k candidates are taken
     (a pair outside its own row's k best by SCORE cannot enter: exact unless two distinct scores of a row round to one J at
     that row's k-th place).  k <= 1024; N_ent <= 2^20 (renet_hip.topk_rows: beyond 32768 entities the rows are taken in
-    pieces by renet_topk_rows_wide, with the same results)."""
+    pieces by renet_topk_rows_wide, with the same results).  sides: the directions to compute; one left out costs no
+    block and is missing from the result."""
     if setting not in SETTINGS:
         raise ValueError('setting must be one of %s, not %r' % (', '.join(SETTINGS), setting))
     store, idx = _event_setup(self, obs, idx)
     dev, n, R, N, k = self.ent_embeds.device, len(idx), self.num_rels, self.in_dim, int(k)
     index = FI.filter_index_for(store, all_triplets if all_triplets is not None else store.quads) if setting != 'raw' else None
     out = {name: (torch.full((n, k), -1, device=dev, dtype=torch.int32), torch.full((n, k), -1, device=dev, dtype=torch.int32),
-                  torch.full((n, k), -np.inf, device=dev), torch.zeros(n, device=dev, dtype=torch.int32)) for name in ('ob', 'sub')}
+                  torch.full((n, k), -np.inf, device=dev), torch.zeros(n, device=dev, dtype=torch.int32))
+           for name in ('ob', 'sub') if name in sides}
     with torch.no_grad():
         q_rel = _event_q_rel(self)
         for ch in _event_chunks(self, store, idx):
             for name, col, side, given, ranked in EVENT_DIRECTIONS:
+                if name not in sides:
+                    continue
                 d = ch.dirs[name]
                 lists = (None, None, None)
                 if index is not None:
@@ -1771,6 +1775,116 @@ def _event_slot_rels(R, k, dev):
     return torch.arange(R, device=dev).repeat_interleave(k).view(1, R * k)
 
 
+# =================================================================================================
+# Open-query forecasts under the observed protocol: queries (s, r, o, t) that need not be facts of the stream -- a pair
+# that did not occur at t, the timestamp after the stream's last, a side left open (-1) -- and histories AS OF an earlier
+# timestamp (as_of <= t: the model forecasts t knowing only the facts before as_of; nothing is generated in between).  A
+# gpu_builder.QueryStore gives such queries history windows on the resident tables (renet_query_histories); everything
+# behind it is the observed pass above, run over the store's positions 0 .. n - 1.  As there, the queries are encoded in
+# fixed chunks of gpu_builder.MAX_BOTH consecutive queries, each one merged batch graph, and a row inherits the reference's
+# dependence on which other queries share its batch graph (utils.py:149-170); nothing of the multi-step state, and
+# nothing resident of the base store, is written.
+# =================================================================================================
+def _query_store(obs, queries, as_of=None):
+    """The gpu_builder.QueryStore of `queries` (int [n, 4] = (s, r, o, t), host array or device int32 tensor; -1: an absent
+    side) on the resident stream obs, histories as of `as_of` (None: t; a scalar or [n]; as_of > t: ValueError)."""
+    return _observed_store(obs).queries(queries, as_of)
+
+
+def _forecast_rows(self, qs):
+    """(feat_ob [n, 3H], feat_sub [n, 3H]) of every query of the QueryStore qs, in order (the chunks of _observed_chunks)."""
+    idx = np.arange(qs.n_quads)
+    (_, _, (feat_ob, feat_sub, _, _)), = _observed_cuts(_observed_chunks(self, qs, idx), len(idx))
+    return feat_ob, feat_sub
+
+
+def _forecast_scores(self, obs, queries, as_of=None):
+    """observed_scores for arbitrary queries: (sub_pred [n, N_ent], ob_pred [n, N_ent]), ob_pred[i] the logits of the
+    objects of (s_i, r_i, ?, t_i) from the history of s_i before as_of, sub_pred[i] those of the subjects of (?, r_i, o_i,
+    t_i).  For queries that are stream facts, forecast_scores(obs, obs.allq[idx]) is observed_scores(obs, idx) bit for bit.
+    An absent side has an empty sequence, and the rows that would need it as the GIVEN entity are not computed: sub_pred is
+    None when no query has an object (ob_pred: a subject); when only some lack it, their rows of that matrix are undefined.
+    A batch whose histories are all empty takes the zero-state rows of _observed_features without an encoder launch."""
+    qs = _query_store(obs, queries, as_of)
+    has_s, has_o = qs.sides_present()
+    with torch.no_grad():
+        feat_ob, feat_sub = _forecast_rows(self, qs)
+        return (_linear_eval(self.linear, feat_sub) if has_o else None, _linear_eval(self.linear, feat_ob) if has_s else None)
+
+
+def _forecast_topk(self, obs, queries, k=10, all_triplets=None, setting='raw', as_of=None, sides=('sub', 'ob')):
+    """predict_topk_observed for arbitrary queries, without gold: {side: (idx, score, logp, n_valid)} as device tensors for
+    the sides asked for ('ob': the objects of (s, r, ?, t), 'sub': the subjects of (?, r, o, t)); a side left out costs no
+    score GEMM.  setting / all_triplets as there (None: the base stream's facts, never the queries); the filter keys are the
+    queries' own (s, r[, t]) / (o, r[, t]) -- a timestamp the facts do not hold gives empty time-aware lists.  With
+    setting='raw' and queries that are a device tensor no query content is read back to the host."""
+    if setting not in SETTINGS:
+        raise ValueError('setting must be one of %s, not %r' % (', '.join(SETTINGS), setting))
+    sides = tuple(sides)
+    if not sides or any(name not in ('sub', 'ob') for name in sides):
+        raise ValueError("sides must name 'sub', 'ob' or both")
+    qs = _query_store(obs, queries, as_of)
+    index = FI.filter_index_for(qs, all_triplets if all_triplets is not None else qs.facts) if setting != 'raw' else None
+    out = {}
+    with torch.no_grad():
+        feat_ob, feat_sub = _forecast_rows(self, qs)
+        dev = feat_ob.device
+        # the score GEMMs are enqueued first: the host lookups of the filtered settings run while the device computes them
+        preds = {name: _linear_eval(self.linear, feat) for name, feat in (('sub', feat_sub), ('ob', feat_ob)) if name in sides}
+        for name, side, key_col in (('sub', 's', 2), ('ob', 'o', 0)):
+            if name not in sides:
+                continue
+            lists = (None, None, None)
+            if index is not None:
+                tr = qs.quads
+                key, r, t = tr[:, key_col], tr[:, 1], tr[:, 3]
+                lists = index.ranges(side, np.stack((key, r, t) if setting == 'time_filtered' else (key, r), axis=1), dev)
+            out[name] = K.topk_rows(preds[name], k, *lists, keep=None)
+    return out
+
+
+def _evaluate_forecast(self, obs, queries, as_of=None, all_triplets=None, max_batch=4096, relation=False):
+    """evaluate_observed for LABELLED queries (both sides present; the gold entities are the query's own s and o), with
+    histories as of `as_of`: the same results in the same layout.  evaluate_forecast(obs, obs.allq[idx]) equals
+    evaluate_observed(obs, idx) exactly; with as_of = obs.horizon_as_of(idx, h) it is the horizon-h stale-history evaluation
+    (its numbers are not those of h = 1).  all_triplets None: the base stream's facts."""
+    qs = _query_store(obs, queries, as_of)
+    ents = qs.quads[:, [0, 2]]
+    if ents.min() < 0 or ents.max() >= qs.num_ent:
+        raise ValueError('evaluate_forecast takes labelled queries: both subject and object present')
+    return _evaluate_observed(self, qs, np.arange(qs.n_quads), all_triplets if all_triplets is not None else qs.facts,
+                              max_batch, relation)
+
+
+def _forecast_events(self, obs, ents, t, k=10, direction='ob', all_triplets=None, setting='raw', as_of=None):
+    """The k most probable events of the entities `ents` [n] at time(s) t (a scalar or [n]; it may lie past the stream's
+    end): (rel int32 [n, k], ent int32 [n, k], logp [n, k], n_valid int32 [n]) as predict_events_observed gives per
+    direction -- 'ob': the pairs (r, o) of ents as subjects, 'sub': the pairs (r, s) of ents as objects.  Runs
+    predict_events_observed over a QueryStore whose relation column is 0 (history, RGCN rows and encoder_r's state do not
+    depend on it) and whose other side is absent; the other direction is not computed."""
+    if direction not in ('ob', 'sub'):
+        raise ValueError("direction must be 'ob' or 'sub'")
+    if isinstance(ents, torch.Tensor) and ents.is_cuda:
+        e = ents.to(torch.int32).reshape(-1)
+        tt = torch.as_tensor(t).to(e.device).to(torch.int32).reshape(-1).expand(e.numel())
+        none, zero = torch.full_like(e, -1), torch.zeros_like(e)
+        quads = torch.stack((e, zero, none, tt) if direction == 'ob' else (none, zero, e, tt), dim=1).contiguous()
+    else:
+        e = np.asarray(ents.cpu() if isinstance(ents, torch.Tensor) else ents, dtype=np.int64).reshape(-1)
+        tt = np.broadcast_to(np.asarray(t.cpu() if isinstance(t, torch.Tensor) else t, dtype=np.int64).reshape(-1), e.shape)
+        none, zero = np.full_like(e, -1), np.zeros_like(e)
+        quads = np.stack((e, zero, none, tt) if direction == 'ob' else (none, zero, e, tt), axis=1)
+        if len(e) and e.min() < 0:
+            raise ValueError('forecast_events: entity id outside [0, num_ent)')
+    qs = _query_store(obs, quads, as_of)
+    return _predict_events_observed(self, qs, np.arange(qs.n_quads), k, all_triplets if all_triplets is not None else qs.facts,
+                                    setting, sides=(direction,))[direction]
+
+
+RENet.forecast_scores = _moded(_forecast_scores)
+RENet.forecast_topk = _moded(_forecast_topk)
+RENet.evaluate_forecast = _moded(_evaluate_forecast)
+RENet.forecast_events = _moded(_forecast_events)
 RENet.observed_event_scores = _moded(_observed_event_scores)
 RENet.evaluate_events_observed = _moded(_evaluate_events_observed)
 RENet.predict_events_observed = _moded(_predict_events_observed)

@@ -24,7 +24,7 @@ class HistoryIndex(object):
     """Histories of every quadruple of a (time-sorted) stream for one role ('s': subject histories of
     (r, o) rows; 'o': object histories of (r, s) rows)."""
 
-    def __init__(self, quads, role, history_len=10):
+    def __init__(self, quads, role, history_len=10, num_ent=None):
         quads = np.asarray(quads, dtype=np.int64)
         if len(quads) > 1 and np.any(np.diff(quads[:, 3]) < 0):
             raise ValueError('quadruples must be sorted by time (as the dataset files are)')
@@ -54,9 +54,33 @@ class HistoryIndex(object):
         self.first = lo
         self.count = sid - lo
         self.history_len = history_len
+        # the snapshot range of every entity, [ent_ptr[e], ent_ptr[e + 1]) (empty for an entity without snapshots): what
+        # lookup() and the device's renet_query_histories search
+        self.num_ent = int(num_ent) if num_ent is not None else (int(ent.max()) + 1 if n else 0)
+        if n and (int(ent.min()) < 0 or int(ent.max()) >= self.num_ent):
+            raise ValueError('entity id outside [0, num_ent)')
+        self.ent_ptr = np.searchsorted(self.snap_ent, np.arange(self.num_ent + 1)).astype(np.int64)
 
     def __len__(self):
         return len(self.first)
+
+    def lookup(self, ent, as_of):
+        """(first, count) int64 of the history window of ARBITRARY (entity, as_of) pairs: the last <= history_len snapshots
+        of the entity in this role with snap_t < as_of, as the range [first, first + count) of the snapshot table.  With sid
+        the first snapshot of the entity's range whose snap_t >= as_of: first = max(range start, sid - history_len), count =
+        sid - first.  An entity id < 0 or >= num_ent gives (0, 0) -- how an absent side is expressed.  For the stream's own
+        facts lookup(ent_i, t_i) = (first[i], count[i])."""
+        ent = np.asarray(ent, dtype=np.int64).reshape(-1)
+        as_of = np.broadcast_to(np.asarray(as_of, dtype=np.int64), ent.shape)
+        ok = (ent >= 0) & (ent < self.num_ent)
+        e = np.where(ok, ent, 0)
+        # snapshots are sorted by (entity, time): ONE search over the combined key; as_of clipped into the key's time digit
+        t0 = int(self.snap_t.min()) if len(self.snap_t) else 0
+        span = (int(self.snap_t.max()) if len(self.snap_t) else 0) - t0 + 2
+        sid = np.searchsorted(self.snap_ent * span + (self.snap_t - t0), e * span + np.clip(as_of - t0, 0, span - 1))
+        lo = self.ent_ptr[e] if self.num_ent else np.zeros_like(e)
+        first = np.maximum(lo, sid - self.history_len)
+        return np.where(ok, first, 0), np.where(ok, sid - first, 0)
 
     def take(self, idx, max_len=None):
         """FlatHistory of the quadruples `idx` (optionally keeping only the newest max_len steps)."""
@@ -117,8 +141,8 @@ class ObservedStream(object):
         self.allq = np.concatenate(splits)
         ends = np.cumsum([len(q) for q in splits])
         self.ranges = {name: (int(b - len(q)), int(b)) for name, q, b in zip(names, splits, ends)}
-        self.hist_s = HistoryIndex(self.allq, 's', history_len)         # (raises unless the stream is sorted by time)
-        self.hist_o = HistoryIndex(self.allq, 'o', history_len)
+        self.hist_s = HistoryIndex(self.allq, 's', history_len, self.num_ent)    # (raises unless the stream is sorted by time)
+        self.hist_o = HistoryIndex(self.allq, 'o', history_len, self.num_ent)
         self.graph_dict = build_graph_dict(self.allq, num_rels)
         self.times = np.unique(self.allq[:, 3])
         self.device = None                                              # the ObservedStore of the last resident() call
@@ -129,6 +153,44 @@ class ObservedStream(object):
     def positions(self, split):
         """The stream positions of a split ('train', 'valid', 'test'), in file order."""
         return np.arange(*self.ranges[split])
+
+    def horizon_as_of(self, idx, h, start=None):
+        """Per stream position of idx, the as-of timestamp under horizon h (int64 [len]): the timestamps of the stream from
+        `start` on (default: the first timestamp of the split that holds the first of the positions) are cut into blocks of
+        h consecutive timestamps, and a position at t gets the FIRST timestamp of its block -- the model forecasts t knowing
+        only the facts before it, up to h - 1 timestamps stale (RENet.evaluate_forecast(..., as_of=...)).  h = 1 gives t
+        itself; the result is never > t.  ValueError for h < 1 or a position before `start`."""
+        idx = np.asarray(idx, dtype=np.int64).reshape(-1)
+        h = int(h)
+        if h < 1:
+            raise ValueError('horizon must be >= 1')
+        if len(idx) == 0:
+            return np.zeros(0, dtype=np.int64)
+        if idx.min() < 0 or idx.max() >= len(self.allq):
+            raise ValueError('positions outside the stream')
+        if start is None:
+            a = max(a for a, b in self.ranges.values() if a <= idx.min() and a < b)
+            start = self.allq[a, 3]
+        ts = self.times[self.times >= int(start)]
+        t = self.allq[idx, 3]
+        if t.min() < int(start):
+            raise ValueError('a position lies before the start of the horizon blocks')
+        return ts[(np.searchsorted(ts, t) // h) * h]
+
+    def extended(self, quads):
+        """A NEW stream with the newly observed quadruples `quads` [m, 4] appended to the last split (they must be sorted
+        by time and not earlier than the stream's last timestamp: ValueError).  A host rebuild of both history indices and
+        the graphs -- the "observe" half of a forecast / observe loop; resident() is called again by the user."""
+        quads = np.asarray(quads, dtype=np.int64).reshape(-1, 4)
+        if len(quads) and ((len(self.allq) and quads[0, 3] < self.allq[-1, 3]) or np.any(np.diff(quads[:, 3]) < 0)):
+            raise ValueError('appended quadruples must be sorted by time and not earlier than the end of the stream')
+        if len(quads) and (quads[:, [0, 2]].min() < 0 or quads[:, [0, 2]].max() >= self.num_ent or quads[:, 1].min() < 0
+                           or quads[:, 1].max() >= self.num_rels):
+            raise ValueError('appended quadruples hold an entity / relation id outside the stream\'s range')
+        names = [n for n in ('train', 'valid', 'test') if n in self.ranges]
+        splits = [self.allq[slice(*self.ranges[n])] for n in names]
+        splits[-1] = np.concatenate((splits[-1], quads))
+        return ObservedStream(splits, self.num_ent, self.num_rels, self.history_len)
 
     def global_table(self, global_model):
         """{t: embedding} over ALL timestamps of the stream, from the global model as it stands and this stream's own

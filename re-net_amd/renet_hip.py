@@ -162,6 +162,8 @@ _SIGNATURES = {
     'renet_build_batch_workspace': (c_size_t, [c_void_p, c_int, c_int, c_int]),
     'renet_build_batch_both': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t,
                                        c_void_p]),
+    'renet_query_histories': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int,
+                                      c_void_p, c_void_p, c_void_p]),
     'renet_build_full_graphs_workspace': (c_size_t, [c_void_p, c_int, c_int, c_int]),
     'renet_build_full_graphs': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t,
                                         c_void_p]),
@@ -1540,6 +1542,27 @@ def topk_rows_wide(scores, k, cols=None, start=None, count=None, keep=None, want
 def _block_ld(scores):
     """Row stride of a [rows, C] block (a one-row block may carry any stride)."""
     return max(_ld(scores), scores.shape[1]) if scores.shape[0] == 1 else _ld(scores)
+
+
+def query_histories(ent_ptr, snap_t, num_ent, history_len, ent, as_of):
+    """renet_query_histories: the history windows of n arbitrary queries against a resident history index.  ent_ptr /
+    snap_t: per role (0 subject, 1 object histories) the int32 device arrays ent_ptr [num_ent + 1] and snap_t; ent int32
+    [2, n] (subjects, objects), as_of int32 [n] -> win int32 [2, 2, n]: win[0] = h_first[2][n], win[1] = h_count[2][n], equal
+    to preprocess.HistoryIndex.lookup element for element; an entity outside [0, num_ent) gets (0, 0).  ONE launch."""
+    if not (ent.dim() == 2 and ent.shape[0] == 2 and as_of.dim() == 1 and as_of.shape[0] == ent.shape[1]):
+        raise RenetHipError('query_histories: ent must be [2, n] and as_of [n]')
+    for r in (0, 1):
+        if ent_ptr[r].numel() != int(num_ent) + 1:
+            raise RenetHipError('query_histories: ent_ptr must hold num_ent + 1 entries')
+    n = int(as_of.shape[0])
+    win = torch.empty(2, 2, n, device=ent.device, dtype=torch.int32)
+    t0 = _timed()
+    _check(lib().renet_query_histories(_i32(ent_ptr[0], 'ent_ptr'), _i32(ent_ptr[1], 'ent_ptr'), _i32(snap_t[0], 'snap_t'),
+                                       _i32(snap_t[1], 'snap_t'), int(num_ent), int(history_len), _i32(ent, 'ent'),
+                                       _i32(as_of, 'as_of'), n, win[0].data_ptr(), win[1].data_ptr(), _stream()),
+           'query_histories')
+    _timed_end(t0, 'query_histories', nbytes=float(n * 28))
+    return win
 
 
 def joint_row_offsets(scores, num_rels, logits_r):

@@ -6,6 +6,13 @@ protocol under which RE-GCN, xERTE and TITer report the time-aware filter.  NOT 
 
     python tools/run_observed_eval.py DATA_DIR --n-hidden H --seq-len L [--split valid|test] [--topk K] [--events [K]]
                                       [--model-dir models/<DS>] [--maxpool 1] [--max-batch 4096] [--gpu 0]
+                                      [--horizon H] [--queries FILE [--k K]]
+
+--horizon H evaluates with STALE histories (RENet.evaluate_forecast with ObservedStream.horizon_as_of): the split's timestamps
+are cut into blocks of H, and every query forecasts from the facts before the first timestamp of its block; nothing is
+generated in between.  H is printed with the metrics: numbers of different H (H = 1 is the plain observed protocol) must not
+be mixed.  --queries FILE forecasts open queries instead of a split: a TSV of `s r o t` lines with -1 for an absent side
+(RENet.forecast_topk, time-aware filtered); prints the K best objects of (s, r, ?, t) and subjects of (?, r, o, t).
 
 --events adds the EVENT forecasts (RENet.evaluate_events_observed): MRR / Hits of the gold (relation, entity) pair among all
 pairs of the given entity, and of the gold relation given both endpoints, in the three settings; with K also the K most
@@ -38,7 +45,13 @@ def main():
     ap.add_argument('--maxpool', type=int, default=1)
     ap.add_argument('--max-batch', type=int, default=4096)
     ap.add_argument('--gpu', type=int, default=0)
+    ap.add_argument('--horizon', type=int, default=None, metavar='H',
+                    help='evaluate with histories up to H - 1 timestamps stale (blocks of H timestamps of the split)')
+    ap.add_argument('--queries', default=None, metavar='FILE', help='TSV of open queries `s r o t` (-1: an absent side)')
+    ap.add_argument('--k', type=int, default=10, help='predictions per open query (--queries)')
     args = ap.parse_args()
+    if args.horizon is not None and args.horizon < 1:
+        raise SystemExit('--horizon must be >= 1')
 
     os.environ.setdefault('TORCH_FORCE_NO_WEIGHTS_ONLY_LOAD', '1')      # (the drivers' checkpoints hold numpy arrays)
     import numpy as np
@@ -77,18 +90,39 @@ def main():
     idx = obs.positions(args.split)
     torch.cuda.synchronize()
     t1 = time.perf_counter()
-    ranks, loss = model.evaluate_observed(obs, idx, max_batch=args.max_batch)
+    if args.queries is not None:
+        q = np.loadtxt(args.queries, dtype=np.int64, ndmin=2)[:, :4]
+        got = model.forecast_topk(obs, q, k=args.k, setting='time_filtered',
+                                  sides=[n for n, c in (('sub', 2), ('ob', 0)) if (q[:, c] >= 0).any()])
+        got = {name: [x.cpu().numpy() for x in v] for name, v in got.items()}
+        for i, (s, r, o, t) in enumerate(q.tolist()):
+            for name, given, what in (('ob', s, 'objects of (%d, %d, ?, %d)' % (s, r, t)), ('sub', o, 'subjects of (?, %d, %d, %d)' % (r, o, t))):
+                if given >= 0:
+                    ent, _, logp, n_valid = got[name]
+                    print(what + ': ' + ', '.join('%d %.3f' % (ent[i, j], logp[i, j]) for j in range(int(n_valid[i]))))
+        return
+    if args.horizon is None:
+        ranks, loss = model.evaluate_observed(obs, idx, max_batch=args.max_batch)
+    else:
+        ranks, loss = model.evaluate_forecast(obs, obs.allq[idx], as_of=obs.horizon_as_of(idx, args.horizon),
+                                              max_batch=args.max_batch)
     torch.cuda.synchronize()
     t2 = time.perf_counter()
     print('observed-history protocol (single-step), %s split of %s: %d quadruples; setup %.2f s, pass %.2f s (%.0f quadruples/s)'
           % (args.split, data_dir, len(idx), t1 - t0, t2 - t1, len(idx) / max(t2 - t1, 1e-9)))
+    if args.horizon is not None:
+        print('STALE histories, horizon H = %d: as of the first timestamp of every block of %d timestamps of the split'
+              % (args.horizon, args.horizon))
     print('mean loss %.6f' % float(np.mean(loss)))
     for name in SETTINGS:
         m = U.rank_metrics(ranks[name])
         print('%-14s MRR %.6f  MR %.3f  Hits@1 %.6f  Hits@3 %.6f  Hits@10 %.6f'
               % (name, m['mrr'], m['mr'], m['hits@1'], m['hits@3'], m['hits@10']))
-    print(json.dumps({'protocol': 'observed', 'split': args.split, 'n': int(len(idx)),
-                      'metrics': {name: U.rank_metrics(ranks[name]) for name in SETTINGS}}))
+    record = {'protocol': 'observed', 'split': args.split, 'n': int(len(idx)),
+              'metrics': {name: U.rank_metrics(ranks[name]) for name in SETTINGS}}
+    if args.horizon is not None:
+        record['horizon'] = args.horizon
+    print(json.dumps(record))
     if args.events is not None:
         t3 = time.perf_counter()
         ev = model.evaluate_events_observed(obs, idx)
