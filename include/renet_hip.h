@@ -162,6 +162,12 @@ int renet_rgcn_bwd_prep_bounds(const float* g_out, const float* out, const float
  *   type_chunk_ptr[T+1] lists, per type, its range of chunks; the stored type t accumulates into
  *   dW[(t + type_shift) mod T] (same convention as renet_rgcn_gather).  Two deterministic passes:
  *   per-chunk partial sums into `workspace` (n_chunks * D*D/100 floats), then a per-type reduction.
+ *   A chunk may hold any number of edges: the planners cut at 64 (graph.CHUNK, the `chunk` argument of
+ *   renet_host_type_chunks), the kernel walks a chunk 64 edges at a time and sets no upper limit, and an EMPTY chunk
+ *   (chunk_ptr[c] == chunk_ptr[c+1]) contributes nothing, wherever it stands in its type.  A type without chunks gets
+ *   dW[tau] = beta * dW[tau]; with n_chunks == 0 that is all the call does (chunk_ptr / chunk_type are not read).
+ *   `workspace` need not be initialised (tests/test_gpu_reductions.py runs all of this on a NaN-filled workspace of
+ *   exactly renet_rgcn_bwd_w_workspace bytes).
  *   x and gn must each be smaller than 2 GiB (rows are addressed with 32-bit buffer offsets). */
 size_t renet_rgcn_bwd_w_workspace(int n_chunks, int D);
 int renet_rgcn_bwd_w(const float* x, const float* gn, const int32_t* e_src, const int32_t* e_dst,
