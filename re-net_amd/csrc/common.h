@@ -47,6 +47,13 @@ static inline int renet_gemm_tile_order() {
     return v;
 }
 
+// RENET_GEMM_EPILOGUE = direct: every tiled MFMA GEMM with a staged epilogue stores its accumulators straight from the MFMA layout (dword stores)
+// instead of 16-byte rows staged through LDS (store_tile_staged in gemm_tiles.h; same bits either way: for A/B runs)
+static inline int renet_gemm_epilogue_staged() {
+    static const int v = renet_env_is("RENET_GEMM_EPILOGUE", "direct") ? 0 : 1;
+    return v;
+}
+
 // n_hidden the kernels are built for: relation blocks of 1x1, 2x2, 3x3, 4x4 (num_bases = 100)
 static inline bool renet_dim_ok(int D) { return D == 100 || D == 200 || D == 300 || D == 400; }
 

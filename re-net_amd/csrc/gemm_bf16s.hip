@@ -225,7 +225,10 @@ __global__ __launch_bounds__(TALL ? 768 : P3_THREADS) void gemm_bf16s_kernel(Bf1
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();                                     // barrier kt
     }
-    store_tile(g, m0, n0, z, wm, wn, lane, acc);
+    // staged epilogue: MFMA wave w's 8 KB of the ring (32 / 64 KB of 96 / 144); the last round's barrier stands behind every
+    // fragment read and behind the loaders' vmcnt(0)
+    static_assert((size_t)MW * EPI_WAVE_FLOATS * sizeof(float) <= (TALL ? B1_LDS_TALL : B1_LDS), "staging fits the ring");
+    store_tile(g, m0, n0, z, wm, wn, lane, acc, reinterpret_cast<float*>(ring1) + wave * EPI_WAVE_FLOATS);
 }
 
 // fp32 [R, C] (row stride ldx) -> ONE bf16 matrix [Rp][Cp] (RNE), padding written as zeros
@@ -325,6 +328,7 @@ int renet_gemm_bf16s(int a_tr, int b_tr, int M, int N, int K, float alpha, const
     g.k_tiles_per_split = max(1, (st_total + split_k - 1) / split_k);
     g.partial = workspace;
     g.xcd_order = renet_gemm_tile_order();
+    g.staged = renet_gemm_epilogue_staged();
     hipStream_t st = (hipStream_t)stream;
     // 256 x 128 tiles when they still fill the chip (>= 256 workgroups); the matrices are padded to multiples of
     // 256 in both dimensions, so a 256-row (or, K-strided, 256-column) A image never leaves the buffer

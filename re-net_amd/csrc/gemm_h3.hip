@@ -193,7 +193,18 @@ __global__ __launch_bounds__(TALL ? 512 : 256) __attribute__((amdgpu_waves_per_e
                 const float v = fmaf(accc[i][j][r], 0.00048828125f, accm[i][j][r]);
                 accm[i][j][r] = inv_ok ? v * inv : (v * inv_a) * inv_b;
             }
-    store_tile(g, m0, n0, z, wm, wn, lane, accm);
+    // staged epilogue, once every wave has read its last fragments.  128-row tile: waves 0, 1 take 8 KB each of the A image
+    // (20 KB), waves 2, 3 of the B image; 256-row tile: eight waves, 4 KB each (16-row passes) of the 40 KB A image
+    if (tile_staged(g, z)) __syncthreads();
+    if constexpr (TALL) {
+        static_assert(8 * (EPI_WAVE_FLOATS / 2) * sizeof(float) <= 2 * PLANE_A * sizeof(_Float16), "staging fits the A image");
+        store_tile<16>(g, m0, n0, z, wm, wn, lane, accm, reinterpret_cast<float*>(sA) + __builtin_amdgcn_readfirstlane(wave) * (EPI_WAVE_FLOATS / 2));
+    } else {
+        static_assert(2 * EPI_WAVE_FLOATS * sizeof(float) <= 2 * PLANE_B * sizeof(_Float16), "staging fits an operand image");
+        const int ws = __builtin_amdgcn_readfirstlane(wave);
+        store_tile<32>(g, m0, n0, z, wm, wn, lane, accm,
+                       reinterpret_cast<float*>(ws < 2 ? sA : sB) + (ws & 1) * EPI_WAVE_FLOATS);
+    }
 }
 
 // partial maxima of |x| over a [rows, cols] matrix with row stride ld: part[b], b < gridDim.x <= 256.
@@ -341,6 +352,7 @@ int renet_gemm_f32_h3(int ta, int tb, int M, int N, int K, float alpha, const fl
     g.k_tiles_per_split = max(1, (kt_total + split_k - 1) / split_k);
     g.partial = workspace;
     g.xcd_order = renet_gemm_tile_order();
+    g.staged = renet_gemm_epilogue_staged();
     h.maxA = maxA; h.maxB = maxB; h.nA = nA; h.nB = nB;
     hipStream_t st = (hipStream_t)stream;
     const int nbx = (N + BN - 1) / BN;

@@ -85,14 +85,32 @@ __device__ __forceinline__ void p6_tile_of_index(int L, int nbx, int nby, int nb
     else { by = l; bx = sh; }
 }
 
+// workgroup-uniform: the output of this launch takes the staged epilogue (aligned base, row stride a multiple of 4 floats)
+__device__ __forceinline__ bool p6_staged(const P6Args& pa) {
+    const SplitArgs& g = pa.out;
+    // (partial planes: plane z starts z * M * N floats in, a multiple of 4 when N is one)
+    return g.split_k > 1 ? epi_staged_ok(g, g.partial, (size_t)g.N) : epi_staged_ok(g, g.C, (size_t)g.ldc);
+}
+
 __device__ __forceinline__ void p6_store_tile(const P6Args& pa, int m0, int n0, int z, int wm, int wn, int lane,
-                                              const f32x16 (&acc)[2][2]) {
+                                              const f32x16 (&acc)[2][2], float* stage) {
+#ifdef RENET_P6_NOSTORE               // probe builds only (see tools/planes_bench.py): what the C-store epilogue costs
+    if (acc[0][0][0] != 12345.678f) return;
+#endif
     const SplitArgs& g = pa.out;
     const bool split = g.split_k > 1;
     const int half = lane >> 5;
     const int n_main = pa.col_out ? g.N - 1 : g.N;
     const bool accumulate = !split && g.beta != 0.f;
     const float alpha = pa.alpha_dev ? g.alpha * pa.alpha_dev[0] : g.alpha;
+    if (p6_staged(pa)) {              // 16-byte rows through this wave's part of the (dead) ring: store_tile_staged in gemm_tiles.h
+        EpiOut o;
+        o.M = g.M; o.bias = g.bias; o.alpha = alpha; o.beta = g.beta; o.raw = split; o.accumulate = accumulate;
+        if (split) { o.base = g.partial + (size_t)z * g.M * g.N; o.ld = (size_t)g.N; o.n_main = g.N; o.col_out = nullptr; }
+        else { o.base = g.C; o.ld = (size_t)g.ldc; o.n_main = n_main; o.col_out = pa.col_out; }
+        store_tile_staged<32>(o, stage, m0 + wm * 64, n0 + wn * 64, lane, acc);
+        return;
+    }
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -295,12 +313,20 @@ __global__ __launch_bounds__(P6Cfg<WM>::THREADS, 2) void gemm_p6_kernel(P6Args p
     // accumulators and immediately issues the DMA prologue of its next tile -- the stores drain and the prologue lands while
     // the co-resident workgroup multiplies.  (One workgroup per tile paid ~16 us of launch + prologue + C-store per tile: 30 %
     // of the logits GEMM, whose K = 600 is only 38 half-stages.)
+    // staged epilogue: wave w's 8 KB of the ring (32 / 64 KB of 72 / 144); every k-loop below ends with vmcnt(0), lgkmcnt(0)
+    // and a barrier, so no DMA piece is in flight and no wave still reads fragments when a tile is stored
+    float* stage = reinterpret_cast<float*>(ring6) + wave * EPI_WAVE_FLOATS;
+    static_assert((size_t)Cfg::NW * EPI_WAVE_FLOATS * sizeof(float) <= Cfg::LDS, "staging fits the ring");
     P6Frags F0, F1;
     bool have_tile = false;
     int pm0 = 0, pn0 = 0, pz = 0;
     for (int item = blockIdx.x; item < n_items; item += gridDim.x) {
         if (have_tile) {
-            p6_store_tile(pa, pm0, pn0, pz, wm, wn, lane, acc);
+            p6_store_tile(pa, pm0, pn0, pz, wm, wn, lane, acc, stage);
+            if (p6_staged(pa)) {                                          // the staged rows have left the ring before the
+                __builtin_amdgcn_s_waitcnt(0xC07F);                       //   next tile's DMA prologue writes into it
+                __builtin_amdgcn_s_barrier();
+            }
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -349,7 +375,7 @@ __global__ __launch_bounds__(P6Cfg<WM>::THREADS, 2) void gemm_p6_kernel(P6Args p
         }
         if (j < nh) iter(j, std::integral_constant<int, 0>{});
     }
-    if (have_tile) p6_store_tile(pa, pm0, pn0, pz, wm, wn, lane, acc);
+    if (have_tile) p6_store_tile(pa, pm0, pn0, pz, wm, wn, lane, acc, stage);
 }
 
 // split-K reduction of the planes GEMM: C / col_out = alpha * sum_z partial[z] (+ bias) (+ beta * old)
@@ -479,6 +505,7 @@ int renet_gemm_planes(int a_tr, int b_tr, int M, int N, int K, float alpha, cons
     g.split_k = split_k;
     g.k_tiles_per_split = (max(1, (st_total + split_k - 1) / split_k) + 1) & ~1;     // even: see gemm_p6_kernel
     g.partial = workspace;
+    g.staged = renet_gemm_epilogue_staged();
     hipStream_t st = (hipStream_t)stream;
     // tile height: 128 rows (two workgroups per CU) unless RENET_P6_TILE=256 (one 8-wave workgroup per CU)
     static const int tile_h = renet_env_int("RENET_P6_TILE", 128, 256, 256);         // any other value: 128

@@ -268,7 +268,12 @@ __global__ __launch_bounds__(THREADS) void gemm_split_kernel(SplitArgs g) {
         TRACE_T(wave, kt - kt0, 3);
     }
 
-    store_tile(g, m0, n0, z, wm, wn, lane, acc);
+    // staged epilogue: waves 0, 1 take 8 KB each of the A image, waves 2, 3 of the B image, once every wave has read its
+    // last fragments
+    if (tile_staged(g, z)) __syncthreads();
+    static_assert(2 * EPI_WAVE_FLOATS * sizeof(float) <= 3 * PL * sizeof(__bf16), "staging fits an operand image");
+    const int ws = __builtin_amdgcn_readfirstlane(wave);
+    store_tile(g, m0, n0, z, wm, wn, lane, acc, reinterpret_cast<float*>(ws < 2 ? sA : sB) + (ws & 1) * EPI_WAVE_FLOATS);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -335,7 +340,9 @@ __global__ __launch_bounds__(THREADS_T) void gemm_split_tall_kernel(SplitArgs g)
             else lb.load_item(i - NIA, k0n, rb[i - NIA]);
         });
     }
-    store_tile(g, m0, n0, z, wm, wn, lane, acc);
+    if (tile_staged(g, z)) __syncthreads();            // staged epilogue: every wave has read its last fragments
+    static_assert((THREADS_T / 64) * EPI_WAVE_FLOATS * sizeof(float) <= TALL_LDS, "staging fits the images");
+    store_tile(g, m0, n0, z, wm, wn, lane, acc, reinterpret_cast<float*>(smem_t) + __builtin_amdgcn_readfirstlane(wave) * EPI_WAVE_FLOATS);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -607,7 +614,9 @@ __global__ __launch_bounds__(THREADS) void gemm_split_fused_kernel(SplitArgs g) 
         }
         static_for<0, 24>([&](auto w) { mfma_w<w.value>(c.F1, acc); });     // slab 1 of the last tile
     }
-    store_tile(g, m0, n0, z, wm, wn, lane, acc);
+    // (direct epilogue only: this kernel runs grids of <= 256 tiles, small outputs, in the step beside the head's planes GEMMs:
+    // no gain from the staged form that a trace could tell from its own spread)
+    store_tile<32, false>(g, m0, n0, z, wm, wn, lane, acc, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -695,7 +704,8 @@ __global__ __launch_bounds__(THREADS) void gemm_bf16_kernel(SplitArgs g) {
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
         }
     }
-    store_tile(g, m0, n0, z, wm, wn, lane, acc);
+    // (direct epilogue only: staged, this kernel gained 2-3 % of the bf16 step in most runs and lost as much in some)
+    store_tile<32, false>(g, m0, n0, z, wm, wn, lane, acc, nullptr);
 }
 
 __global__ __launch_bounds__(256) void split_reduce_kernel(const float* __restrict__ partial, int split_k,
@@ -891,6 +901,7 @@ static int gemm_split_launch(bool bf16_mode, int ta, int tb, int M, int N, int K
     g.k_tiles_per_split = max(1, (kt_total + split_k - 1) / split_k);
     g.partial = workspace;
     g.xcd_order = p.xcd_order;
+    g.staged = renet_gemm_epilogue_staged();
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(p.gx, p.gy, p.gz);
     const bool raw = p.raw != 0;

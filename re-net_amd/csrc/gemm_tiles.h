@@ -20,6 +20,7 @@ constexpr int LDS_ROW = 40;                     // bf16 per LDS row (80 B)
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
@@ -35,6 +36,7 @@ struct SplitArgs {
     int split_k;
     float* partial;
     int xcd_order;          // 0: plain order; w >= 1: XCD-aware virtual tile order with panels of <= w tiles (tile_of_block)
+    int staged;             // epilogue: 1 = 16-byte rows through LDS (store_tile_staged), 0 = straight from the MFMA layout
 };
 
 
@@ -183,10 +185,150 @@ __device__ __forceinline__ void static_for(F&& f) {
     }
 }
 
+// ---- staged epilogue -------------------------------------------------------------------------------------------------
+// A wave's 64 x 64 outputs leave the CU as 16-byte row pieces instead of 64 dword stores per lane (an epilogue of many
+// narrow stores per lane is bound by store ISSUE, not by bandwidth).  The accumulators go through a region of the
+// workgroup's LDS that is private to the wave -- the operand images are dead by then; every kernel makes sure of it with a
+// workgroup barrier behind its last fragment read -- in passes of ROWS rows x 64 columns:
+//   write  32 (16) ds_write_b32 in the MFMA layout: lanes 0-31 one row, 32 consecutive dwords (a ds_write_b32 is served in
+//          two groups of 32 lanes over 32 banks: no conflict at any pitch);
+//   read   ROWS / 4 ds_read_b128 in the row layout: lane l owns the 16 bytes at row (l >> 4) + 4 k, columns 4 (l & 15)..;
+//          a ds_read_b128 is served in four groups of 16 lanes that each cover halves of TWO rows (lanes 0-3, 12-15 of one
+//          and 4-11 of the next) over 64 banks: free of conflicts exactly when the pitch is a multiple of 64 dwords;
+//   store  one wave-instruction = 4 rows x 256 contiguous bytes.
+// LDS operations of one wave execute in order, so only the compiler has to be held (wavefront fence) between a pass's
+// writes and reads.  Element arithmetic: the expressions of the direct path, on the same operands -- same bits.
+constexpr int EPI_PITCH = 64;                              // dwords per staged row
+constexpr int EPI_WAVE_FLOATS = 32 * EPI_PITCH;            // a wave's region (8 KB); 16-row passes use half of it
+
+struct EpiOut {
+    float* base;            // C, or the split-K partial plane of this k-slice
+    size_t ld;              // its row stride (elements)
+    int M, n_main;          // rows; columns [0, n_main) go to base
+    float* col_out;         // optional (planes GEMM): column n_main goes to col_out[row]
+    const float* bias;      // optional, per column of base
+    float alpha, beta;
+    bool raw;               // split-K partial plane: the raw accumulators
+    bool accumulate;        // beta != 0: read - modify - write
+};
+
+__device__ __forceinline__ bool epi_staged_ok(const SplitArgs& g, const float* base, size_t ld) {
+    return g.staged && ((reinterpret_cast<uintptr_t>(base) & 15) == 0) && ((ld & 3) == 0);
+}
+
+// workgroup-uniform: this launch's tiles of k-slice z take the staged path (what store_tile decides; the kernels key the
+// barrier in front of the staging on it)
+__device__ __forceinline__ bool tile_staged(const SplitArgs& g, int z) {
+    const bool split = g.split_k > 1;
+    return epi_staged_ok(g, split ? g.partial + (size_t)z * g.M * g.N : g.C, (size_t)(split ? g.N : g.ldc));
+}
+
+// row0 / col0: the first output row / column of this wave's 64 x 64 block.  EDGE (wave-uniform): the block reaches beyond row M
+// or beyond column n_main -- only then are there per-lane row and column checks, and straddling groups.
+template <int ROWS, bool EDGE>
+__device__ __forceinline__ void store_block_staged(const EpiOut& o, float* stage, int row0, int col0, int lane,
+                                                   const f32x16 (&acc)[2][2]) {
+    typedef __attribute__((address_space(3))) float lds_f32;
+    typedef __attribute__((address_space(3))) f32x4 lds_f32x4;
+    constexpr int NK = ROWS / 4;                           // 16-byte pieces per lane and pass
+    lds_f32* st = (lds_f32*)stage;
+    const int half = lane >> 5;
+    const int rl = lane >> 4;                              // row of this lane inside a group of 4
+    const int c4 = col0 + 4 * (lane & 15);
+    const int nv = EDGE ? o.n_main - c4 : 4;               // columns of this lane's group that go to base (>= 4: all)
+    const bool full = nv >= 4;
+    const int cv = (EDGE && o.col_out && nv >= 0 && nv < 4) ? nv : -1;    // element of the group that is the col_out column
+    float bv[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) bv[e] = (!o.raw && o.bias && e < nv) ? o.bias[c4 + e] : 0.f;
+    // element e of row `row` of a straddling group: its address, or null where nothing may be touched
+    auto edge_ptr = [&](int row, int e) -> float* {
+        return e < nv ? o.base + (size_t)row * o.ld + c4 + e : e == cv ? o.col_out + row : nullptr;
+    };
+#pragma unroll
+    for (int p = 0; p < 64 / ROWS; ++p) {
+        constexpr int RPB = 32 / ROWS;                     // passes per 32-row MFMA block
+        const int i = p / RPB, r0 = (p % RPB) * (ROWS / 2);
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < ROWS / 2; ++r)
+                st[((r & 3) + 8 * (r >> 2) + 4 * half) * EPI_PITCH + j * 32 + (lane & 31)] = acc[i][j][r0 + r];
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        f32x4 v[NK];
+#pragma unroll
+        for (int k = 0; k < NK; ++k) v[k] = *(const lds_f32x4*)(st + (rl + 4 * k) * EPI_PITCH + 4 * (lane & 15));
+        __builtin_amdgcn_s_waitcnt(0xC07F);                // lgkmcnt(0): the region is free for the next pass
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        const int rowp = row0 + p * ROWS + rl;
+        // beta != 0: ALL reads of the pass first, then its stores (see the direct path)
+        f32x4 old[NK];
+#pragma unroll
+        for (int k = 0; k < NK; ++k) old[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (o.accumulate) {
+#pragma unroll
+            for (int k = 0; k < NK; ++k) {
+                const int row = rowp + 4 * k;
+                if (EDGE && row >= o.M) continue;
+                if (full) {
+                    old[k] = *reinterpret_cast<const f32x4*>(o.base + (size_t)row * o.ld + c4);
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const float* q = edge_ptr(row, e);
+                        if (q) old[k][e] = *q;
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+            const int row = rowp + 4 * k;
+            if (EDGE && row >= o.M) continue;
+            f32x4 w;
+            if (o.raw) {
+                w = v[k];
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) w[e] = o.alpha * v[k][e] + bv[e] + (o.accumulate ? o.beta * old[k][e] : 0.f);
+            }
+            if (full) {
+                *reinterpret_cast<f32x4*>(o.base + (size_t)row * o.ld + c4) = w;
+            } else {
+                // the group straddles column n_main: its valid columns one by one, nothing at or beyond n_main
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    float* q = edge_ptr(row, e);
+                    if (q) *q = w[e];
+                }
+            }
+        }
+    }
+}
+
+template <int ROWS>
+__device__ __forceinline__ void store_tile_staged(const EpiOut& o, float* stage, int row0, int col0, int lane,
+                                                  const f32x16 (&acc)[2][2]) {
+    static_assert(ROWS == 32 || ROWS == 16, "a pass is one or one half of a 32-row MFMA block");
+    const int n_all = o.n_main + (o.col_out ? 1 : 0);
+    if (row0 >= o.M || col0 >= n_all) return;              // wave-uniform
+    // (the epilogue's lane arithmetic starts here: hoisted above the k-loop it costs every kernel 4 VGPRs in the loop)
+    asm volatile("" : "+v"(lane));
+    if (row0 + 64 <= o.M && col0 + 64 <= o.n_main) store_block_staged<ROWS, false>(o, stage, row0, col0, lane, acc);
+    else store_block_staged<ROWS, true>(o, stage, row0, col0, lane, acc);
+}
+
 // accumulators -> C (or the split-K partial plane).  C/D layout of the 32x32 MFMA: col = lane & 31,
-// row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
+// row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5).  `stage`: this wave's EPI_WAVE_FLOATS (ROWS = 32) or half of that
+// (ROWS = 16) of dead LDS.  The staged path needs a 16-byte aligned output with a row stride that is a multiple of 4 floats;
+// any other output, and RENET_GEMM_EPILOGUE=direct, take the direct path below.  STAGED = false: a kernel that has only the
+// direct path (gemm_bf16_kernel, gemm_split_fused_kernel: no measured gain from the staged form, profiles/gemm_epilogue.md).
+template <int ROWS = 32, bool STAGED = true>
 __device__ __forceinline__ void store_tile(const SplitArgs& g, int m0, int n0, int z, int wm, int wn, int lane,
-                                           const f32x16 (&acc)[2][2]) {
+                                           const f32x16 (&acc)[2][2], float* stage) {
 #ifdef RENET_PROBE_NOSTORE          // probe builds only (tools/gemm_split_probe.py): what the C-store epilogue costs
     if (acc[0][0][0] != 12345.678f) return;
 #endif
@@ -195,6 +337,13 @@ __device__ __forceinline__ void store_tile(const SplitArgs& g, int m0, int n0, i
     const int ldo = split ? g.N : g.ldc;
     const int half = lane >> 5;
     const bool accumulate = !split && g.beta != 0.f;
+    if (STAGED && epi_staged_ok(g, Cout, (size_t)ldo)) {
+        EpiOut o;
+        o.base = Cout; o.ld = (size_t)ldo; o.M = g.M; o.n_main = g.N; o.col_out = nullptr;
+        o.bias = g.bias; o.alpha = g.alpha; o.beta = g.beta; o.raw = split; o.accumulate = accumulate;
+        store_tile_staged<ROWS>(o, stage, m0 + wm * 64, n0 + wn * 64, lane, acc);
+        return;
+    }
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
