@@ -53,6 +53,26 @@ int renet_segment_add(const float* src, const int32_t* order, const int32_t* seg
  * batch graph's nodes to entity rows, keyed by the same node -> entity map). */
 int renet_segment_add2(const float* src0, const float* src1, const int32_t* order, const int32_t* seg_ptr,
                        const int32_t* seg_target, int U, int D, float* dst0, float* dst1, void* stream);
+/* Up to RENET_SEGADD_MAX_JOBS independent segmented adds in ONE launch, each with up to two stages over its plan:
+ *   stage A:            dst[target[u]] = dst[target[u]] + sum_seg (a0[row] (+ a1[row]))     (a1 optional)
+ *   stage B (optional): dst[target[u]] = that           + sum_seg  b[row]
+ * Per segment and stage the additions are renet_segment_add's, in its order, so a job equals renet_add_inplace(a0, a1)
+ * followed by renet_segment_add(a0) and renet_segment_add(b) bit for bit (a0 + a1 is formed as the rows are loaded; a0 is
+ * not modified).  overwrite != 0: stage A starts from 0.f instead of the old row (dst[t] = 0.f + sum: what renet_zero
+ * followed by the add leaves, also for an empty segment and for a sum of -0.0 terms); accepted only where the plan covers
+ * every row of dst: U == dst_rows (targets are distinct by the plan's contract).  Refused before any launch: n out of
+ * range, a missing array, an overwrite job with U != dst_rows, two jobs with the same dst (RENET_ERR_BADARG); D > 512
+ * (RENET_ERR_UNSUPPORTED).  Jobs with U == 0 are no-ops. */
+#define RENET_SEGADD_MAX_JOBS 4
+typedef struct {
+    const int32_t *order, *seg_ptr, *seg_target;
+    int U;                                     /* segments of the plan */
+    float* dst;
+    int dst_rows;                              /* rows of dst (read for overwrite jobs only) */
+    int overwrite;
+    const float *a0, *a1, *b;                  /* a1, b: optional */
+} RenetSegAddJob;
+int renet_segment_add_multi(int n, const RenetSegAddJob* jobs, int D, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * RGCN block-diagonal gather-SpMM  (RGCN.py:79-94 msg_func + fn.sum + apply_func, fused with the
@@ -429,6 +449,23 @@ int renet_gru_fwd_layouts(int n, const float* const* Gi, const int32_t* const* s
 int renet_gru_bwd_layouts(int n, const float* const* dh_last, const int32_t* const* step_off, const int* L, int H,
                           const float* const* Whh, const float* const* saved, float* const* dGi,
                           float* const* dGh, float* workspace, size_t workspace_bytes, void* stream);
+/* The weight split of the two entries above as a call of its own, so that a caller can issue it early and on another
+ * stream (the planes depend on nothing but W_hh).  renet_gru_split_weights issues exactly the split launches of
+ * renet_gru_fwd_layouts (backward = 0: planes of W_hh) or renet_gru_bwd_layouts (backward != 0: planes of W_hh^T) for
+ * the n weight pointers, into the same workspace slots (equal pointers are split once, into the slot of the first);
+ * renet_gru_{fwd,bwd}_layouts_presplit are those entries without the split: they trust the slots.  The caller orders
+ * the split before the recurrence and keeps the workspace untouched between them; forward and backward planes share
+ * the slots.  RENET_ERR_UNSUPPORTED where the plain entries do not read planes from fixed slots (RENET_GEMM=f32,
+ * RENET_GRU=steps): call the plain entries then. */
+int renet_gru_split_weights(int n, const float* const* Whh, int H, int backward, float* workspace,
+                            size_t workspace_bytes, void* stream);
+int renet_gru_fwd_layouts_presplit(int n, const float* const* Gi, const int32_t* const* step_off, const int* L, int H,
+                                   const float* const* Whh, const float* const* bhh, float* const* h_last,
+                                   const int* out_rows, float* const* saved, float* workspace, size_t workspace_bytes,
+                                   void* stream);
+int renet_gru_bwd_layouts_presplit(int n, const float* const* dh_last, const int32_t* const* step_off, const int* L,
+                                   int H, const float* const* Whh, const float* const* saved, float* const* dGi,
+                                   float* const* dGh, float* workspace, size_t workspace_bytes, void* stream);
 /* renet_gru_bwd_layouts that additionally emits the operand bound of dGi for renet_gemm_f32_h3: bounds[k] receives
  * renet_gru_bound_parts(max over the problems of their sequence count) floats, one maximum of |dGi| per workgroup
  * (|dGh| <= |dGi| elementwise: the same bound serves both).  Only the persistent bf16x6 recurrence emits them;
@@ -827,6 +864,9 @@ int renet_build_batch_grouped(const RenetGroupedStoreDev* store, const int32_t* 
  *                          is recorded when the entity head's weight / bias gradients are complete (early all-reduce bucket),
  *                          ev_gru_done (optional) when both encoders' parameter gradients are (the middle bucket)
  *   both return the number of C-ABI launches they issued in *n_launches (optional).
+ *   RENET_STEP_BATCH (environment, read once; default 6): bit 2 = the head's and the sequence assembly's segmented adds as one
+ *   renet_segment_add_multi launch, bit 4 = the W_hh splits issued early on the side stream (renet_gru_split_weights); 0 = one
+ *   launch per sum, the splits inside the GRU calls.  Same bits of every result either way.
  * fp32-class default mode only (bf16x6 GEMMs, bf16x6 recurrences); tensors below 2 GiB. */
 typedef struct { const int32_t *order, *seg_ptr, *target; int num_segments; } RenetSegPlan;
 typedef struct {

@@ -19,6 +19,9 @@
 // results at 2.7x the f32-input MFMA rate (the recurrence was matrix-pipe bound: 13 unit blocks x 156 f32 MFMAs
 // per step on 4 SIMDs).  RENET_GEMM=f32 selects the exact-fp32 kernels (v_mfma_f32_16x16x4_f32).
 //
+// The split is also an entry point of its own (renet_gru_split_weights) with recurrence entries that trust the slots
+// (renet_gru_{fwd,bwd}_layouts_presplit): the training step issues it early on its side stream (csrc/step.cpp).
+//
 // Sources: this file is the host front (layout validation, workspace, choice of the recurrence, the exported entry points);
 // the kernels live with their launchers in gru_f32.hip (exact fp32), gru_planes.hip (persistent, bf16 planes) and
 // gru_steps.hip (one launch per time step, RENET_GRU=steps); gru_common.h holds what they share.
@@ -130,6 +133,18 @@ int plane_slot(int k, const float* const* W) {
     return k;
 }
 
+// the two fragment-ordered splits of W_hh [3H, H] (the recurrences and renet_gru_split_weights issue the same launches)
+int split_fwd(const float* W, int H, void* planes, hipStream_t st, int npl) {
+    return renet_gru_split_frag(W, H, H, 3, (size_t)H * H, (size_t)H, 1, planes, st, npl);
+}
+int split_bwd(const float* W, int H, void* planes, hipStream_t st, int npl) {
+    return renet_gru_split_frag(W, H, 3 * H, 1, 0, 1, (size_t)H, planes, st, npl);
+}
+
+// whether the recurrence of arithmetic npl reads bf16 planes from workspace slots whose place does not depend on the batch:
+// not the exact-fp32 kernels (no planes), not the step kernels (their slices carry per-batch state)
+bool planes_in_fixed_slots(int npl) { return npl == 3 && !use_f32() && use_persistent(); }
+
 int max_batch(int n, const int* B_of) {
     int Bmax = 0;
     for (int k = 0; k < n; ++k) Bmax = B_of[k] > Bmax ? B_of[k] : Bmax;
@@ -140,9 +155,10 @@ int max_batch(int n, const int* B_of) {
 // for by the caller (per model)
 int gru_fwd_impl(int npl, int n, const float* const* Gi, const int32_t* const* step_off, const int* L, int H,
                  const float* const* Whh, const float* const* bhh, float* const* h_last, const int* out_rows,
-                 float* const* saved, float* workspace, size_t workspace_bytes, void* stream) {
+                 float* const* saved, float* workspace, size_t workspace_bytes, void* stream, bool presplit = false) {
     Layouts ly;
     int B_of[MAXP];
+    if (presplit && !planes_in_fixed_slots(npl)) return RENET_ERR_UNSUPPORTED;
     const int e0 = make_layouts(n, step_off, L, out_rows, true, ly, B_of);
     if (e0 != RENET_OK) return e0;
     if (max_rows(ly) == 0) return RENET_OK;
@@ -166,8 +182,8 @@ int gru_fwd_impl(int npl, int n, const float* const* Gi, const int32_t* const* s
         const int k = i < n ? i : 0;
         const int slot = plane_slot(k, Whh);
         bf16x8* planes = reinterpret_cast<bf16x8*>(ws + (size_t)slot * per);
-        if (i < n && slot == k) {                   // gate g of unit u, input k: W_hh[g*H + u][k]
-            const int e = renet_gru_split_frag(Whh[k], H, H, 3, (size_t)H * H, (size_t)H, 1, planes, st, npl);
+        if (i < n && slot == k && !presplit) {      // gate g of unit u, input k: W_hh[g*H + u][k]
+            const int e = split_fwd(Whh[k], H, planes, st, npl);
             if (e != RENET_OK) return e;
         }
         ps.p[i] = {Gi[k], planes, bhh[k], h_last[k], saved[k]};
@@ -184,9 +200,10 @@ int gru_fwd_impl(int npl, int n, const float* const* Gi, const int32_t* const* s
 int gru_bwd_impl(int npl, int n, const float* const* dh_last, const int32_t* const* step_off, const int* L, int H,
                  const float* const* Whh, const float* const* saved, float* const* dGi, float* const* dGh,
                  float* workspace, size_t workspace_bytes, void* stream, int out_ld = 0,
-                 float* const* bounds = nullptr) {
+                 float* const* bounds = nullptr, bool presplit = false) {
     Layouts ly;
     int B_of[MAXP];
+    if (presplit && !planes_in_fixed_slots(npl)) return RENET_ERR_UNSUPPORTED;
     const int e0 = make_layouts(n, step_off, L, nullptr, false, ly, B_of);
     if (e0 != RENET_OK) return e0;
     if (max_rows(ly) == 0) return RENET_OK;
@@ -204,9 +221,9 @@ int gru_bwd_impl(int npl, int n, const float* const* dh_last, const int32_t* con
         const int k = i < n ? i : 0;
         const int slot = plane_slot(k, Whh);
         wt[i] = ws + (size_t)slot * per;
-        if (i < n && slot == k) {                   // W_hh^T: unit u = hidden unit, k = gate column c: W_hh[c][u]
+        if (i < n && slot == k && !presplit) {      // W_hh^T: unit u = hidden unit, k = gate column c: W_hh[c][u]
             const int e = f32 ? renet_gru_transpose(Whh[k], 3 * H, H, reinterpret_cast<float*>(wt[i]), st)
-                              : renet_gru_split_frag(Whh[k], H, 3 * H, 1, 0, 1, (size_t)H, wt[i], st, npl);
+                              : split_bwd(Whh[k], H, wt[i], st, npl);
             if (e != RENET_OK) return e;
         }
     }
@@ -255,6 +272,27 @@ int renet_gru_fwd_layouts_bf16(GRU_FWD_PARAMS) { return gru_fwd_impl(1, GRU_FWD_
 int renet_gru_bwd_layouts(GRU_BWD_PARAMS) { return gru_bwd_impl(3, GRU_BWD_ARGS); }
 int renet_gru_bwd_layouts_f32(GRU_BWD_PARAMS) { return gru_bwd_impl(0, GRU_BWD_ARGS); }
 int renet_gru_bwd_layouts_bf16(GRU_BWD_PARAMS) { return gru_bwd_impl(1, GRU_BWD_ARGS); }
+
+int renet_gru_fwd_layouts_presplit(GRU_FWD_PARAMS) { return gru_fwd_impl(3, GRU_FWD_ARGS, true); }
+int renet_gru_bwd_layouts_presplit(GRU_BWD_PARAMS) { return gru_bwd_impl(3, GRU_BWD_ARGS, 0, nullptr, true); }
+
+int renet_gru_split_weights(int n, const float* const* Whh, int H, int backward, float* workspace, size_t workspace_bytes,
+                            void* stream) {
+    if (n < 1 || n > MAXP || !Whh) return RENET_ERR_BADARG;
+    for (int k = 0; k < n; ++k)
+        if (!Whh[k]) return RENET_ERR_BADARG;
+    if (!renet_dim_ok(H) || !planes_in_fixed_slots(3)) return RENET_ERR_UNSUPPORTED;
+    const size_t per = slice_bytes(0, H);
+    if (!workspace || workspace_bytes < (size_t)n * per) return RENET_ERR_WORKSPACE;
+    char* ws = reinterpret_cast<char*>(workspace);
+    for (int k = 0; k < n; ++k) {
+        if (plane_slot(k, Whh) != k) continue;
+        const int e = backward ? split_bwd(Whh[k], H, ws + (size_t)k * per, (hipStream_t)stream, 3)
+                               : split_fwd(Whh[k], H, ws + (size_t)k * per, (hipStream_t)stream, 3);
+        if (e != RENET_OK) return e;
+    }
+    return RENET_OK;
+}
 
 int renet_gru_bound_parts(int max_rows) { return max(1, (max_rows + MT - 1) / MT); }
 

@@ -92,6 +92,113 @@ __global__ __launch_bounds__(kSegWaves * 64) void segment_add_kernel(const float
     }
 }
 
+// ---- several segmented adds in one launch (renet_segment_add_multi) ------------------------------------------------------
+// The small scatters of the backward pass are latency chains (pointer -> order -> rows -> read-modify-write of the
+// destination), a few microseconds of dependent round trips each whatever their bytes: up to 4 jobs share ONE grid (a
+// contiguous range of workgroups per job, the job table in the kernel arguments), and a job may carry a second stage over
+// the same plan whose sum is added to the destination row while it is still in registers (short segments) or by the thread
+// that wrote it (long ones).  Inside a job the segments are dealt to workgroups and waves as segment_add_kernel deals them,
+// and every sum is formed by seg_rows_sum in that kernel's order; `a0 + a1` is one addition per element at load.
+struct SegJobK {
+    const float4 *a0, *a1, *b;
+    const int32_t *order, *seg_ptr, *seg_target;
+    float4* dst;
+    int U, nwg, blk0, overwrite;
+};
+struct SegJobsK { SegJobK j[RENET_SEGADD_MAX_JOBS]; int n; };
+
+// sum of the rows order[k], k = kbeg + i * stride + q (q < kSegUnr) below k1, in increasing k: kSegUnr loads in flight
+template <bool TWO>
+__device__ __forceinline__ float4 seg_rows_sum(const float4* __restrict__ a0, const float4* __restrict__ a1,
+                                               const int32_t* __restrict__ order, int CH, int ch, int kbeg, int k1,
+                                               int stride) {
+    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int k = kbeg; k < k1; k += stride) {
+        float4 v[kSegUnr];
+        if (TWO) {                                     // two halves: the same 8 loads in flight, 4 rows of each source
+#pragma unroll
+            for (int h = 0; h < kSegUnr; h += kSegUnr / 2) {
+                float4 w[kSegUnr / 2];
+#pragma unroll
+                for (int q = 0; q < kSegUnr / 2; ++q) {
+                    const size_t at = (size_t)order[min(k + h + q, k1 - 1)] * CH + ch;
+                    v[h + q] = a0[at];
+                    w[q] = a1[at];
+                }
+#pragma unroll
+                for (int q = 0; q < kSegUnr / 2; ++q) v[h + q] = f4_add(v[h + q], w[q]);
+            }
+        } else {
+#pragma unroll
+            for (int q = 0; q < kSegUnr; ++q) v[q] = a0[(size_t)order[min(k + q, k1 - 1)] * CH + ch];
+        }
+#pragma unroll
+        for (int q = 0; q < kSegUnr; ++q)
+            if (k + q < k1) s = f4_add(s, v[q]);
+    }
+    return s;
+}
+
+__device__ __forceinline__ float4 seg_stage_sum(const float4* a0, const float4* a1, const int32_t* order, int CH, int ch,
+                                                int kbeg, int k1, int stride) {
+    return a1 ? seg_rows_sum<true>(a0, a1, order, CH, ch, kbeg, k1, stride)
+              : seg_rows_sum<false>(a0, nullptr, order, CH, ch, kbeg, k1, stride);
+}
+
+// (8 waves per SIMD = two workgroups per CU, as segment_add_kernel has: the registers stay at 64)
+__global__ __launch_bounds__(kSegWaves * 64, 8) void segment_add_multi_kernel(const SegJobsK js, int CH) {
+    __shared__ float4 red[kSegWaves][128];
+    SegJobK J = js.j[0];                                                   // workgroup-uniform selection
+#pragma unroll
+    for (int i = 1; i < RENET_SEGADD_MAX_JOBS; ++i)
+        if (i < js.n && (int)blockIdx.x >= js.j[i].blk0) J = js.j[i];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int bl = blockIdx.x - J.blk0, nwg = J.nwg, U = J.U;
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    // ---- this wave's own segment, if short (an empty one is written only where the job overwrites)
+    {
+        const int u = bl + wave * nwg;
+        const int k0 = u < U ? J.seg_ptr[u] : 0, k1 = u < U ? J.seg_ptr[u + 1] : 0;
+        const int len = k1 - k0;
+        if (u < U && len <= kSegShort && (len > 0 || J.overwrite)) {
+            const size_t tgt = (size_t)__builtin_amdgcn_readfirstlane(J.seg_target[u]) * CH;     // (u is wave-uniform)
+            for (int ch = lane; ch < CH; ch += 64) {
+                const float4 sa = seg_stage_sum(J.a0, J.a1, J.order, CH, ch, k0, k1, kSegUnr);
+                float4 d = f4_add(J.overwrite ? zero : J.dst[tgt + ch], sa);
+                if (J.b) d = f4_add(d, seg_stage_sum(J.b, nullptr, J.order, CH, ch, k0, k1, kSegUnr));
+                J.dst[tgt + ch] = d;
+            }
+        }
+    }
+    // ---- the long segments of this workgroup's 16, one after the other, all waves together; stage after stage
+    const int stages = J.b ? 2 : 1;
+    for (int j = 0; j < kSegWaves; ++j) {
+        const int u = bl + j * nwg;
+        if (u >= U) break;
+        const int k0 = J.seg_ptr[u], k1 = J.seg_ptr[u + 1];                // workgroup-uniform
+        if (k1 - k0 <= kSegShort) continue;
+        const size_t tgt = (size_t)__builtin_amdgcn_readfirstlane(J.seg_target[u]) * CH;
+        for (int st = 0; st < stages; ++st) {
+            const float4* s0 = st ? J.b : J.a0;
+            const float4* s1 = st ? nullptr : J.a1;
+            for (int ch = lane; ch < CH; ch += 64)
+                red[wave][ch] = seg_stage_sum(s0, s1, J.order, CH, ch, k0 + wave * kSegUnr, k1, kSegWaves * kSegUnr);
+            __syncthreads();
+            if (wave == 0) {
+                for (int ch = lane; ch < CH; ch += 64) {
+                    float4 r = red[0][ch];
+#pragma unroll 5                                                           // (LDS reads in three batches: registers)
+                    for (int w = 1; w < kSegWaves; ++w) r = f4_add(r, red[w][ch]);
+                    const float4 d = (st == 0 && J.overwrite) ? zero : J.dst[tgt + ch];   // (stage B: this thread's own store)
+                    J.dst[tgt + ch] = f4_add(d, r);
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -135,6 +242,33 @@ int renet_segment_add2(const float* src0, const float* src1, const int32_t* orde
     RENET_LAUNCH(segment_add_kernel, dim3(seg_grid(U), 2), dim3(kSegWaves * 64), 0,
                        (hipStream_t)stream, (const float4*)src0, (const float4*)src1, order, seg_ptr, seg_target, U, D / 4,
                        (float4*)dst0, (float4*)dst1);
+    RENET_LAUNCH_CHECK();
+    return RENET_OK;
+}
+
+int renet_segment_add_multi(int n, const RenetSegAddJob* jobs, int D, void* stream) {
+    if (n < 1 || n > RENET_SEGADD_MAX_JOBS || !jobs || D <= 0 || (D & 3)) return RENET_ERR_BADARG;
+    for (int i = 0; i < n; ++i) {
+        const RenetSegAddJob& q = jobs[i];
+        if (q.U < 0 || !q.dst || !q.a0) return RENET_ERR_BADARG;
+        if (q.U > 0 && (!q.order || !q.seg_ptr || !q.seg_target)) return RENET_ERR_BADARG;
+        if (q.overwrite && q.U != q.dst_rows) return RENET_ERR_BADARG;   // a row outside the plan would keep its old value
+        for (int k = 0; k < i; ++k)
+            if (jobs[k].dst == q.dst) return RENET_ERR_BADARG;           // two jobs updating one destination race
+    }
+    if (D > 512) return RENET_ERR_UNSUPPORTED;
+    SegJobsK js{};
+    int blocks = 0;
+    for (int i = 0; i < n; ++i) {
+        const RenetSegAddJob& q = jobs[i];
+        if (q.U == 0) continue;
+        SegJobK& k = js.j[js.n++];
+        k = {(const float4*)q.a0, (const float4*)q.a1, (const float4*)q.b, q.order, q.seg_ptr, q.seg_target, (float4*)q.dst,
+             q.U, seg_grid(q.U), blocks, q.overwrite ? 1 : 0};
+        blocks += k.nwg;
+    }
+    if (js.n == 0) return RENET_OK;
+    RENET_LAUNCH(segment_add_multi_kernel, dim3(blocks), dim3(kSegWaves * 64), 0, (hipStream_t)stream, js, D / 4);
     RENET_LAUNCH_CHECK();
     return RENET_OK;
 }

@@ -8,13 +8,15 @@
 // HIP events.  This file contains NO arithmetic: every launch goes through an extern "C" entry point of the library with
 // the arguments re-net_amd/ops.py passes on the autograd path (RGCNTableLayerFn, RGCNLayerFn, SeqAssembleFn, MultiGRUFn,
 // DualHeadCEFn -- each block below names the Function it mirrors), so the two paths produce bit-identical losses and
-// gradients (tests/test_gpu_step_plan.py).
+// gradients (tests/test_gpu_step_plan.py).  Two groups of small launches are issued in a batched form that carries the same
+// sums in the same order (RENET_STEP_BATCH below; tests/test_gpu_backward_batching.py, profiles/backward_batching.md): the
+// segmented adds of the head and of the sequence assembly as ONE launch, the W_hh fragment splits early on the side stream.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdint>
 #include <cstdlib>
 #include <vector>
-#include "../../include/renet_hip.h"
+#include "common.h"
 
 namespace {
 
@@ -71,6 +73,18 @@ struct Lay {
 };
 
 bool use_planes(const RenetStepModel& m) { return m.lin_w_planes != nullptr; }
+
+// RENET_STEP_BATCH: which of the batched forms of the small launches the list uses (default 6 = both; 0 = one launch per
+// sum and the W_hh splits inside the GRU calls; the bits exist for A/B timing and for tests against that list):
+//   2  the head's and the sequence assembly's segmented adds as ONE renet_segment_add_multi call
+//   4  the W_hh fragment splits issued early on the side stream (renet_gru_split_weights), the recurrences presplit
+// (Bit 1 is not assigned: the four GRU bias column sums as one pair of launches measured no gain of their own and are not
+// in the tree, profiles/backward_batching.md section 5.)
+enum { kBatchSegAdd = 2, kBatchSplit = 4 };
+int step_batch() {
+    static const int v = renet_env_int("RENET_STEP_BATCH", 6, 0, 7);
+    return v;
+}
 
 Lay layout(const RenetStepModel& m, const RenetStepBatch& b) {
     Lay L{};
@@ -239,6 +253,18 @@ int renet_step_forward(const RenetStepModel* mp, const RenetStepBatch* bp, const
     const bool pruned = nA < N;
     float* wsm = F(L.gemm_ws_main);
     float* wss = F(L.gemm_ws_side);
+    const float* whh2[2] = {m.whh, m.whh_r};
+
+    // The W_hh planes of the recurrence depend on nothing in the step but the weights: split them now, as the first launch of
+    // the side stream.  The fork orders it behind everything the caller enqueued on the main stream (the optimizer's update
+    // of W_hh, the last reader of the workspace block); the join in front of the recurrence covers it.
+    bool presplit = false;
+    if (step_batch() & kBatchSplit) {
+        s.fork();
+        const int e = renet_gru_split_weights(2, whh2, D, 0, F(L.gru_ws), L.gru_ws_bytes, s.side);
+        if (e == RENET_OK) { presplit = true; ++launches; }
+        else if (e != RENET_ERR_UNSUPPORTED) return e;              // (unsupported: the recurrence splits for itself)
+    }
 
     // ---- ops.RGCNTableLayerFn.forward (RGCN.py:33-51,79-94 of layer 1 on h0 = ent_embeds[id], utils.py:239)
     CK(gemm(s.main, wsm, L.gemm_ws_bytes, 0, 0, NE, D, D, m.ent, D, m.loop1, D, 0.f, F(L.ew), D, nullptr));
@@ -263,14 +289,14 @@ int renet_step_forward(const RenetStepModel* mp, const RenetStepBatch* bp, const
         const float* gi[2] = {F(L.gi0), F(L.gi1)};
         const int32_t* so[2] = {b.step_off_host, b.step_off_host};
         const int ls[2] = {b.L, b.L};
-        const float* whh[2] = {m.whh, m.whh_r};
         const float* bhh[2] = {m.bhh, m.bhh_r};
         float* hl[2] = {F(L.hs0), F(L.hs1)};
         const int bmax = b.step_off_host[1] - b.step_off_host[0];
         const int rows[2] = {std::max(B, bmax), std::max(B, bmax)};
         float* sv[2] = {F(L.sv0), F(L.sv1)};
         if (rows[0] != B) return RENET_ERR_BADARG;
-        CK(renet_gru_fwd_layouts(2, gi, so, ls, D, whh, bhh, hl, rows, sv, F(L.gru_ws), L.gru_ws_bytes, s.main));
+        CK((presplit ? renet_gru_fwd_layouts_presplit : renet_gru_fwd_layouts)(2, gi, so, ls, D, whh2, bhh, hl, rows, sv,
+                                                                               F(L.gru_ws), L.gru_ws_bytes, s.main));
     }
     // ---- ops.DualHeadCEFn.forward (model.py:89-103): the relation head on the side stream
     s.fork();
@@ -324,6 +350,16 @@ int renet_step_backward(const RenetStepModel* mp, const RenetStepBatch* bp, cons
     // into it once (in-loop-split head) or into the planes GEMMs' alpha (planes head)
     if (!pl) CK(renet_scale_by_device_scalar(F(L.dl1), (size_t)B * NE, g, s.main));
     s.fork();
+    // the planes of W_hh^T for the backward recurrence: first launch behind the first fork (the forward recurrence, the last
+    // reader of the slots, is in front of it); the join behind concat3_bwd covers it
+    const int batch = step_batch();
+    const float* whh2[2] = {m.whh, m.whh_r};
+    bool presplit = false;
+    if (batch & kBatchSplit) {
+        const int e = renet_gru_split_weights(2, whh2, D, 1, F(L.gru_ws), L.gru_ws_bytes, s.side);
+        if (e == RENET_OK) { presplit = true; ++launches; }
+        else if (e != RENET_ERR_UNSUPPORTED) return e;
+    }
     CK(renet_scale_by_device_scalar(F(L.dl2), (size_t)B * C2, g, s.side));
     CK(gemm(s.side, wss, L.gemm_ws_bytes, 0, 0, B, 2 * D, C2, F(L.dl2), C2, m.linr_w, 2 * D, 0.f, F(L.dfeat2), 2 * D, nullptr));
     CK(gemm(s.side, wss, L.gemm_ws_bytes, 1, 0, C2, 2 * D, B, F(L.dl2), C2, F(L.feat2), 2 * D, 1.f, m.g_linr_w, 2 * D, nullptr));
@@ -349,20 +385,25 @@ int renet_step_backward(const RenetStepModel* mp, const RenetStepBatch* bp, cons
         const hipError_t e = hipEventRecord((hipEvent_t)ev_head_done, s.main);
         if (e != hipSuccess) return (int)e;
     }
-    CK(renet_add_inplace(F(L.da1), F(L.da2), (size_t)B * D, s.main));
-    CK(renet_segment_add(F(L.da1), b.plan_s.order, b.plan_s.seg_ptr, b.plan_s.target, b.plan_s.num_segments, D, m.g_ent, s.main));
-    CK(renet_segment_add(F(L.dc1), b.plan_r.order, b.plan_r.seg_ptr, b.plan_r.target, b.plan_r.num_segments, D, m.g_rel, s.main));
+    // The heads' gradients wrt the gathered rows ent[s] / rel[r] (da1 + da2, dc1).  Nothing reads g_ent / g_rel before the end
+    // of the step: batched, they wait (untouched: the workspace reuses no region) for the merged launch behind the sequence
+    // assembly's backward, which adds them first and the sequence side's rows second -- every destination's order of updates.
+    if (!(batch & kBatchSegAdd)) {
+        CK(renet_add_inplace(F(L.da1), F(L.da2), (size_t)B * D, s.main));
+        CK(renet_segment_add(F(L.da1), b.plan_s.order, b.plan_s.seg_ptr, b.plan_s.target, b.plan_s.num_segments, D, m.g_ent, s.main));
+        CK(renet_segment_add(F(L.dc1), b.plan_r.order, b.plan_r.seg_ptr, b.plan_r.target, b.plan_r.num_segments, D, m.g_rel, s.main));
+    }
 
     // ---- ops.MultiGRUFn.backward: the recurrences and dX on this stream, every parameter gradient on the side stream
     {
         const float* dhl[2] = {F(L.dh1), F(L.dh2)};
         const int32_t* so[2] = {b.step_off_host, b.step_off_host};
         const int ls[2] = {b.L, b.L};
-        const float* whh[2] = {m.whh, m.whh_r};
         const float* sv[2] = {F(L.sv0), F(L.sv1)};
         float* dgi[2] = {F(L.dgi0), F(L.dgi1)};
         float* dgh[2] = {F(L.dgh0), F(L.dgh1)};
-        CK(renet_gru_bwd_layouts(2, dhl, so, ls, D, whh, sv, dgi, dgh, F(L.gru_ws), L.gru_ws_bytes, s.main));
+        CK((presplit ? renet_gru_bwd_layouts_presplit : renet_gru_bwd_layouts)(2, dhl, so, ls, D, whh2, sv, dgi, dgh, F(L.gru_ws),
+                                                                               L.gru_ws_bytes, s.main));
     }
     // The parameter gradients of both encoders (~0.4 ms of chip-filling GEMMs that feed only the optimizer) run on the side
     // stream, forked in front of the dX GEMMs (behind them: 1 % slower, profiles/r06_d_step_plan.md).
@@ -399,11 +440,27 @@ int renet_step_backward(const RenetStepModel* mp, const RenetStepBatch* bp, cons
     // ---- ops.SeqAssembleFn.backward
     CK(renet_seq_assemble_bwd(F(L.dX), F(L.dXr), b.step_off, b.L, S, B, D, p, r->seed_x, r->seed_xr, F(L.d_rows), F(L.d_ent_seq),
                               F(L.d_rel_seq), s.main));
-    CK(renet_zero(F(L.d_h2), (size_t)nA * D, s.main));
-    CK(renet_segment_add(F(L.d_rows), b.plan_subj_row.order, b.plan_subj_row.seg_ptr, b.plan_subj_row.target,
-                         b.plan_subj_row.num_segments, D, F(L.d_h2), s.main));
-    CK(renet_segment_add(F(L.d_ent_seq), b.plan_s.order, b.plan_s.seg_ptr, b.plan_s.target, b.plan_s.num_segments, D, m.g_ent, s.main));
-    CK(renet_segment_add(F(L.d_rel_seq), b.plan_r.order, b.plan_r.seg_ptr, b.plan_r.target, b.plan_r.num_segments, D, m.g_rel, s.main));
+    if (batch & kBatchSegAdd) {
+        // ONE launch: (dc1, then d_rel_seq) -> g_rel, (da1 + da2, then d_ent_seq) -> g_ent, d_rows -> d_h2.  The relation job
+        // (a few hundred long segments) goes first so that its workgroups are dispatched first.  d_h2 needs no zero pass
+        // where the plan names every one of its rows; otherwise it is zeroed and accumulated into as before.
+        const bool cover = b.plan_subj_row.num_segments == nA;
+        if (!cover) CK(renet_zero(F(L.d_h2), (size_t)nA * D, s.main));
+        const RenetSegAddJob jobs[3] = {
+            {b.plan_r.order, b.plan_r.seg_ptr, b.plan_r.target, b.plan_r.num_segments, m.g_rel, 0, 0, F(L.dc1), nullptr,
+             F(L.d_rel_seq)},
+            {b.plan_s.order, b.plan_s.seg_ptr, b.plan_s.target, b.plan_s.num_segments, m.g_ent, 0, 0, F(L.da1), F(L.da2),
+             F(L.d_ent_seq)},
+            {b.plan_subj_row.order, b.plan_subj_row.seg_ptr, b.plan_subj_row.target, b.plan_subj_row.num_segments, F(L.d_h2), nA,
+             cover ? 1 : 0, F(L.d_rows), nullptr, nullptr}};
+        CK(renet_segment_add_multi(3, jobs, D, s.main));
+    } else {
+        CK(renet_zero(F(L.d_h2), (size_t)nA * D, s.main));
+        CK(renet_segment_add(F(L.d_rows), b.plan_subj_row.order, b.plan_subj_row.seg_ptr, b.plan_subj_row.target,
+                             b.plan_subj_row.num_segments, D, F(L.d_h2), s.main));
+        CK(renet_segment_add(F(L.d_ent_seq), b.plan_s.order, b.plan_s.seg_ptr, b.plan_s.target, b.plan_s.num_segments, D, m.g_ent, s.main));
+        CK(renet_segment_add(F(L.d_rel_seq), b.plan_r.order, b.plan_r.seg_ptr, b.plan_r.target, b.plan_r.num_segments, D, m.g_rel, s.main));
+    }
 
     // ---- ops.RGCNLayerFn.backward (layer 2, evaluated on the row prefix)
     const int pair_shift = (T / 2) % T;

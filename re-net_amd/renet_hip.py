@@ -40,6 +40,10 @@ _SIGNATURES = {
     'renet_segment_add': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     'renet_segment_add2': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
                                    c_void_p]),
+    'renet_segment_add_multi': (c_int, [c_int, c_void_p, c_int, c_void_p]),
+    'renet_gru_split_weights': (c_int, [c_int, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    'renet_gru_fwd_layouts_presplit': (c_int, _GRU_FWD_LAYOUTS_ARGS),
+    'renet_gru_bwd_layouts_presplit': (c_int, _GRU_BWD_LAYOUTS_ARGS),
     'renet_rgcn_gather': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                   c_int, c_int, c_void_p, c_float, c_u64, c_int, c_void_p, c_int, c_void_p,
                                   c_int, c_int, c_int, c_int, c_void_p]),
@@ -383,6 +387,32 @@ def segment_add2(src0, src1, plan, dst0, dst1):
     """dst0[target] += segment sums of src0 and dst1[target] += segment sums of src1, one launch, one plan."""
     _check(lib().renet_segment_add2(_f32(src0), _f32(src1), _i32(plan.order), _i32(plan.seg_ptr), _i32(plan.target),
                                     plan.num_segments, src0.shape[1], _f32(dst0), _f32(dst1), _stream()), 'segment_add2')
+
+
+class SegAddJobC(ctypes.Structure):
+    """RenetSegAddJob"""
+    _fields_ = [('order', c_void_p), ('seg_ptr', c_void_p), ('seg_target', c_void_p), ('U', c_int), ('dst', c_void_p),
+                ('dst_rows', c_int), ('overwrite', c_int), ('a0', c_void_p), ('a1', c_void_p), ('b', c_void_p)]
+
+
+def segment_add_multi(jobs):
+    """jobs: up to 4 of (plan, dst, a0, a1 | None, b | None, overwrite) -- per job dst[target] (+)= segment sums of a0 (+ a1),
+    then of b, in ONE launch (renet_segment_add_multi); -> the library's return code."""
+    arr = (SegAddJobC * max(len(jobs), 1))()
+    d = 0
+    for j, (plan, dst, a0, a1, b, overwrite) in zip(arr, jobs):
+        j.order, j.seg_ptr, j.seg_target, j.U = _i32(plan.order), _i32(plan.seg_ptr), _i32(plan.target), plan.num_segments
+        j.dst, j.dst_rows, j.overwrite = _f32(dst), dst.shape[0], int(bool(overwrite))
+        j.a0, j.a1, j.b = _f32(a0), _f32(a1), _f32(b)
+        d = dst.shape[1]
+    return lib().renet_segment_add_multi(len(jobs), ctypes.addressof(arr), d, _stream())
+
+
+def gru_split_weights(w_hhs, hdim, backward, ws, ws_bytes):
+    """The W_hh plane split of gru_fwd_layouts (backward=False) / gru_bwd_layouts (True) into the slots of `ws`, on the current
+    stream (renet_gru_split_weights); -> the library's return code."""
+    return lib().renet_gru_split_weights(len(w_hhs), _ptrs(w_hhs), hdim, int(bool(backward)), ws.data_ptr(), ws_bytes,
+                                         _stream())
 
 
 def _heavy(rows):
