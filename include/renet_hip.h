@@ -786,6 +786,33 @@ int renet_query_histories(const int32_t* ent_ptr0, const int32_t* ent_ptr1, cons
                           int32_t* h_count, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * APPEND of newly observed facts to the resident history index of ONE role (csrc/builder_append.hip; the host statement
+ * is preprocess.HistoryIndex.appended, array for array, and the result equals the HistoryIndex of the longer stream bit for
+ * bit).  Old index (device int32, only read): ent_ptr [num_ent + 1], snap_t [n_snaps], snap_ptr [n_snaps + 1], nbr_o /
+ * h_first / h_count [n_quads], and q_ent [n_quads], the entity of every old quadruple in this role (q_s for role 0, q_o for
+ * role 1).  New facts (device int32 [m]), every timestamp >= every old one, SORTED stably by (entity, time, input order):
+ * new_ent, new_t, new_other (the neighbour) and new_pos, the input position of each sorted fact -- new quadruple new_pos[j]
+ * becomes position n_quads + new_pos[j] of the longer stream.  A new (entity, time) group whose time equals the entity's
+ * last old snapshot joins that snapshot; every other group opens one.  Outputs (the caller's fresh allocations):
+ * ent_ptr_out [num_ent + 1], snap_t_out [cap_snaps], snap_ptr_out [cap_snaps + 1], nbr_o_out / h_first_out / h_count_out
+ * [n_quads + m]; totals[2] = (snapshots of the longer index, of which opened).  cap_snaps in [n_snaps, n_snaps + m] is what
+ * the snapshot outputs hold: no store goes past it, and the outputs are complete when totals[0] == cap_snaps (a caller
+ * that knows which entities were active at the last old timestamp knows the count beforehand).  m == 0 gives copies.  Runs
+ * on `stream`, no host synchronisation, no atomics.  Negative sizes, a missing array, a capacity outside its range or a
+ * workspace below renet_store_append_workspace(num_ent, m): RENET_ERR_BADARG; n_quads + m, n_snaps + m or num_ent + 1 beyond
+ * int32: RENET_ERR_UNSUPPORTED, before any launch.
+ * renet_append_i32: out[0 .. n_old + n_add) = old[0 .. n_old) followed by add[0 .. n_add) -- the flat arrays of the store
+ * (quadruples, timestamps, fact lists), which an append only lengthens. */
+size_t renet_store_append_workspace(int num_ent, int m);
+int renet_store_append(const int32_t* ent_ptr, const int32_t* snap_t, const int32_t* snap_ptr, const int32_t* nbr_o,
+                       const int32_t* h_first, const int32_t* h_count, const int32_t* q_ent, int num_ent, int n_snaps,
+                       int n_quads, int history_len, const int32_t* new_ent, const int32_t* new_t, const int32_t* new_other,
+                       const int32_t* new_pos, int m, int cap_snaps, int32_t* ent_ptr_out, int32_t* snap_t_out,
+                       int32_t* snap_ptr_out, int32_t* nbr_o_out, int32_t* h_first_out, int32_t* h_count_out, int32_t* totals,
+                       void* workspace, size_t workspace_bytes, void* stream);
+int renet_append_i32(const int32_t* old, int n_old, const int32_t* add, int n_add, int32_t* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * DEVICE builder for the FULL-GRAPH batches of the global model (graph.build_full_graphs; reference Aggregator.py:44-55 /
  * 87-98: dgl.batch of the whole graphs of a list of timestamps).  Resident: the per-timestamp node lists and the facts with
  * LOCAL endpoints (graph.TimeGraph.ent / ls / r / lo, concatenated in graph_dict order).  tidx_dev[G] (device int32,

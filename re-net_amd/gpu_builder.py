@@ -158,6 +158,10 @@ class DeviceStore(GraphDeviceStore):
             self.t['nbr_o%d' % r] = _i32(h.nbr_o, device)
             self.t['ent_ptr%d' % r] = _i32(h.ent_ptr, device)          # (renet_query_histories: QueryStore below)
         self.history_len = int(hist_s.history_len)
+        self._fill_struct()
+
+    def _fill_struct(self):
+        """`c`, the RenetStoreDev of the tensors in `t`."""
         sd = _StoreDev()
         for n in ('q_s', 'q_r', 'q_o', 'times', 'trip_ptr', 'trip_s', 'trip_r', 'trip_o', 'glob_times'):
             setattr(sd, n, self.t[n].data_ptr())
@@ -180,12 +184,103 @@ class ObservedStore(DeviceStore):
                              device)
         self.obs, self.quads = obs, obs.allq
         ts = sorted(int(t) for t in global_emb.keys())
+        self._glob_times = np.asarray(ts, dtype=np.int64)               # (host copy of t['glob_times']: appended() cuts by it)
         self.glob = torch.stack([torch.as_tensor(global_emb[t]).detach().reshape(h_dim).float() for t in ts]).to(device)
 
     def queries(self, quads, as_of=None, stream=None):
         """The QueryStore of the queries `quads` [n, 4] = (s, r, o, t) on top of this store: histories as of `as_of` (None:
         each query's own t), -1 for an absent subject or object."""
         return QueryStore(self, quads, as_of, stream)
+
+    # the host GraphStore behind subject_index(): an appended store makes it when first asked
+    _store = property(lambda self: self._graph_store(), lambda self, v: setattr(self, '_gstore', v))
+
+    def _graph_store(self):
+        if self._gstore is None:
+            self._gstore = G.store_for(self.obs.graph_dict)
+        return self._gstore
+
+    def appended(self, quads, global_emb_new, _obs=None):
+        """A NEW ObservedStore: this one with the newly observed quadruples `quads` (host int [m, 4], validated as
+        ObservedStream.extended validates them: the same ValueErrors) appended ON THE DEVICE -- equal, tensor for tensor and
+        bit for bit, to ObservedStore(obs.extended(quads), ...).  Per role one renet_store_append over the resident history
+        index (csrc/builder_append.hip; host statement preprocess.HistoryIndex.appended), renet_append_i32 for the arrays an
+        append only lengthens; uploaded: the new facts, sorted per role by (entity, time, input order) on the host (m is
+        small), and the tails of times / trip_ptr.  All on the current stream, into fresh tensors: this store, and any batch
+        still pending on it, stays valid.
+
+        global_emb_new: {t: row} for EVERY timestamp of the longer stream >= the first appended one (ValueError otherwise;
+        empty for m = 0) -- `glob` is this store's rows of the earlier timestamps followed by them.  cap_nodes / cap_edges
+        are carried over; no filter index is; `obs` / `quads` are the light stream of ObservedStream._appended."""
+        old = self.obs
+        quads = old._checked_new(quads)
+        obs = _obs if _obs is not None else old._appended(quads)
+        m, nq, dev = len(quads), self.n_quads, self.device
+        _check_int32('ids / timestamps', quads)
+        if max(nq + m, obs.num_ent + 1) >= 2 ** 31 - 1024:
+            raise ValueError('fact count must fit int32')
+        t0 = int(quads[0, 3]) if m else None
+        want = [int(t) for t in obs.times if t >= t0] if m else []
+        if sorted(int(t) for t in global_emb_new.keys()) != want:
+            raise ValueError('global_emb_new must hold exactly the timestamps of the longer stream from the first appended one on')
+        # host side, over the new facts and the old stream's LAST timestamp only: per role the sorted new facts and the
+        # snapshot count of the longer index (a new (entity, time) group joins an old snapshot only at the old last time)
+        joined = m and len(old.allq) and t0 == int(old.allq[-1, 3])
+        tail = old.allq[np.searchsorted(old.allq[:, 3], t0):] if joined else np.zeros((0, 4), np.int64)
+        packs, caps = [], []
+        for c, oc in ((0, 2), (2, 0)):
+            order = np.lexsort((np.arange(m), quads[:, 3], quads[:, c]))
+            packs.append(np.stack((quads[order, c], quads[order, 3], quads[order, oc], order)))
+            groups = np.unique(quads[:, [c, 3]], axis=0) if m else np.zeros((0, 2), np.int64)
+            n_join = int(np.isin(groups[groups[:, 1] == t0, 0], tail[:, c]).sum()) if joined else 0
+            caps.append(int(self.t['snap_t%d' % (c // 2)].numel()) + len(groups) - n_join)
+        new_t = np.unique(quads[:, 3])
+        if joined:
+            new_t = new_t[1:]
+        ends = self.n_facts + np.searchsorted(quads[:, 3], np.unique(quads[:, 3]), side='right')
+        flat = np.concatenate([a.reshape(-1) for a in packs] + [quads[:, 0], quads[:, 1], quads[:, 2], new_t, ends,
+                               np.asarray(want, dtype=np.int64)])
+        up = torch.from_numpy(np.ascontiguousarray(flat, dtype=np.int32)).to(dev, non_blocking=True)     # ONE upload
+        role = [up[k * 4 * m:(k + 1) * 4 * m].view(4, m) for k in (0, 1)]
+        o = 8 * m
+        n_s, n_r, n_o = up[o:o + m], up[o + m:o + 2 * m], up[o + 2 * m:o + 3 * m]
+        o += 3 * m
+        n_times, n_ends = up[o:o + len(new_t)], up[o + len(new_t):o + len(new_t) + len(ends)]
+        n_glob_t = up[o + len(new_t) + len(ends):]
+
+        new = ObservedStore.__new__(ObservedStore)
+        _Store.__init__(new, dev, self.num_ent, self.num_rels)
+        t, ot = {}, self.t
+        totals = []
+        for r, q_ent in enumerate((ot['q_s'], ot['q_o'])):
+            names = ['%s%d' % (f, r) for f in ('ent_ptr', 'snap_t', 'snap_ptr', 'nbr_o', 'h_first', 'h_count')]
+            out, tot = K.store_append([ot[f] for f in names], q_ent, self.num_ent, self.history_len, role[r], caps[r])
+            t.update(zip(names, out))
+            totals.append(tot)
+        t['q_s'], t['q_r'], t['q_o'] = K.append_i32(ot['q_s'], n_s), K.append_i32(ot['q_r'], n_r), K.append_i32(ot['q_o'], n_o)
+        t['trip_s'], t['trip_r'], t['trip_o'] = (K.append_i32(ot['trip_s'], n_s), K.append_i32(ot['trip_r'], n_r),
+                                                 K.append_i32(ot['trip_o'], n_o))
+        t['times'] = K.append_i32(ot['times'], n_times)
+        # (a timestamp equal to the old last one: its end moves, no entry is added)
+        t['trip_ptr'] = K.append_i32(ot['trip_ptr'], n_ends, n_old=self.T + (0 if joined else 1))
+        keep = int(np.searchsorted(self._glob_times, t0)) if m else self.n_glob
+        rows = [torch.as_tensor(global_emb_new[tt]).detach().reshape(self.glob.shape[1]).float().to(dev) for tt in want]
+        new.glob = torch.cat((self.glob[:keep], torch.stack(rows))) if rows else self.glob[:keep].clone()
+        t['glob_times'] = K.append_i32(ot['glob_times'], n_glob_t, n_old=keep)
+        new._glob_times = np.concatenate((self._glob_times[:keep], np.asarray(want, dtype=np.int64)))
+        new.t = t
+        new.n_quads = new.n_facts = nq + m
+        new.T, new.n_glob = int(t['times'].numel()), int(t['glob_times'].numel())
+        new.cap_nodes, new.cap_edges = self.cap_nodes, self.cap_edges
+        new.history_len = self.history_len
+        new._gstore = None
+        new.obs, new.quads = obs, obs.allq
+        new._fill_struct()
+        # the snapshot outputs were sized from the host's count: the kernels report theirs (8 bytes per role, one read)
+        got = torch.stack(totals).cpu().numpy()
+        if [int(x) for x in got[:, 0]] != caps:
+            raise K.RenetHipError('store append: %s snapshots on the device where the host counts %s' % (got[:, 0], caps))
+        return new
 
 
 def _cached_store(cache, graph_dict, device, stamp, make):

@@ -54,6 +54,7 @@ class HistoryIndex(object):
         self.first = lo
         self.count = sid - lo
         self.history_len = history_len
+        self.role = role
         # the snapshot range of every entity, [ent_ptr[e], ent_ptr[e + 1]) (empty for an entity without snapshots): what
         # lookup() and the device's renet_query_histories search
         self.num_ent = int(num_ent) if num_ent is not None else (int(ent.max()) + 1 if n else 0)
@@ -63,6 +64,75 @@ class HistoryIndex(object):
 
     def __len__(self):
         return len(self.first)
+
+    def appended(self, ent_old, new_quads):
+        """The index of the stream with new_quads [m, 4] APPENDED, from this index's six resident fields (first, count,
+        snap_t, snap_ptr, nbr_o, ent_ptr), ent_old [n] (this role's entity of every old quadruple) and the new quadruples
+        alone: no sort over the old facts.  The host statement of the device append (csrc/builder_append.hip,
+        renet_store_append), array for array; equal to HistoryIndex(old ++ new) in those six fields (and in snap_ent, which
+        follows from ent_ptr; nbr_r is not carried: to_lists() needs a full index).
+
+        New facts have t >= every old fact (ValueError otherwise) and come later in file order, so in the (entity, time,
+        file order) sort they land at the END of their entity's run.  With the new facts sorted the same way: add_fact[e]
+        = new facts of e, add_snap[e] = distinct new times of e, minus one if the first of them is e's last old snap_t (those
+        facts JOIN that snapshot); fshift / sshift = their exclusive scans over the entities.  Then ent_ptr' = ent_ptr +
+        sshift, old snapshot k of e moves to k + sshift[e], the old fact run of e moves by fshift[e] and e's new facts follow
+        it, snap_ptr' is the scan of the merged snapshot sizes; an old quadruple keeps count and has first + sshift[its
+        entity]; a new one with snapshot id sid has first = max(ent_ptr'[e], sid - history_len), count = sid - first."""
+        q = np.asarray(new_quads, dtype=np.int64).reshape(-1, 4)
+        ent_old = np.asarray(ent_old, dtype=np.int64).reshape(-1)
+        m, n, N, S = len(q), len(self.first), self.num_ent, len(self.snap_t)
+        if len(ent_old) != n:
+            raise ValueError('ent_old must hold the entity of every old quadruple')
+        if m and (np.any(np.diff(q[:, 3]) < 0) or (S and q[0, 3] < self.snap_t.max())):
+            raise ValueError('appended quadruples must be sorted by time and not earlier than the end of the stream')
+        ent = q[:, 0] if self.role == 's' else q[:, 2]
+        other = q[:, 2] if self.role == 's' else q[:, 0]
+        if m and (int(ent.min()) < 0 or int(ent.max()) >= N):
+            raise ValueError('entity id outside [0, num_ent)')
+        order = np.lexsort((np.arange(m), q[:, 3], ent))              # entity, then time, then input order
+        e_s, t_s = ent[order], q[order, 3]
+        head_e = np.ones(m, dtype=bool)
+        head_e[1:] = e_s[1:] != e_s[:-1]
+        head_s = head_e.copy()
+        head_s[1:] |= t_s[1:] != t_s[:-1]
+        old_cnt = np.diff(self.ent_ptr)
+        join = np.zeros(m, dtype=bool)
+        cand = head_e & (old_cnt[e_s] > 0)                              # entity heads with an old snapshot to join
+        join[cand] = self.snap_t[self.ent_ptr[e_s[cand] + 1] - 1] == t_s[cand]
+        opens = head_s & ~join
+        add_fact = np.bincount(e_s, minlength=N)
+        add_snap = np.bincount(e_s[opens], minlength=N)
+        fshift = np.concatenate(([0], np.cumsum(add_fact))).astype(np.int64)
+        sshift = np.concatenate(([0], np.cumsum(add_snap))).astype(np.int64)
+        ent_ptr2 = self.ent_ptr + sshift
+        S2 = S + int(sshift[-1])
+        snap_ent_old = np.repeat(np.arange(N, dtype=np.int64), old_cnt)
+        # snapshot id of every sorted new fact: the snapshots its entity opened up to it, behind the entity's old ones
+        oinc = np.cumsum(opens)
+        rank = oinc - (oinc - opens)[fshift[e_s]] if m else oinc
+        sid = ent_ptr2[e_s + 1] - add_snap[e_s] + rank - 1
+        snap_t2 = np.empty(S2, dtype=np.int64)
+        size2 = np.zeros(S2, dtype=np.int64)
+        old_to = np.arange(S, dtype=np.int64) + sshift[snap_ent_old]
+        snap_t2[old_to] = self.snap_t
+        size2[old_to] = np.diff(self.snap_ptr)
+        snap_t2[sid[opens]] = t_s[opens]
+        np.add.at(size2, sid, 1)
+        nbr2 = np.empty(n + m, dtype=np.int64)
+        nbr2[np.arange(n, dtype=np.int64) + fshift[np.repeat(snap_ent_old, np.diff(self.snap_ptr))]] = self.nbr_o
+        nbr2[self.snap_ptr[self.ent_ptr[e_s + 1]] + np.arange(m, dtype=np.int64)] = other[order]
+        first2, count2 = np.empty(n + m, dtype=np.int64), np.empty(n + m, dtype=np.int64)
+        first2[:n], count2[:n] = self.first + sshift[ent_old], self.count
+        lo = np.maximum(ent_ptr2[e_s], sid - self.history_len)
+        first2[n + order], count2[n + order] = lo, sid - lo
+        out = HistoryIndex.__new__(HistoryIndex)
+        out.first, out.count, out.snap_t, out.nbr_o, out.ent_ptr = first2, count2, snap_t2, nbr2, ent_ptr2
+        out.snap_ptr = np.concatenate(([0], np.cumsum(size2))).astype(np.int64)
+        out.snap_ent = np.repeat(np.arange(N, dtype=np.int64), np.diff(ent_ptr2))
+        out.nbr_r = None
+        out.history_len, out.role, out.num_ent = self.history_len, self.role, N
+        return out
 
     def lookup(self, ent, as_of):
         """(first, count) int64 of the history window of ARBITRARY (entity, as_of) pairs: the last <= history_len snapshots
@@ -130,7 +200,8 @@ class ObservedStream(object):
     both roles over the WHOLE stream -- the history of a test quadruple at t is the last <= history_len timestamps t' < t at
     which its entity was active in that role, with the true neighbours at t', whichever split they come from: what
     get_history_graph.py:206-317 writes into test_history_*.txt -- and `graph_dict`, one graph per timestamp of the whole
-    stream (the reference writes the training timestamps only).  Host arrays only; resident() puts them on a device."""
+    stream (the reference writes the training timestamps only).  Host arrays only; resident() puts them on a device, and
+    observe() appends newly observed quadruples to the resident copy."""
 
     def __init__(self, splits, num_ent, num_rels, history_len=10):
         splits = [np.asarray(q, dtype=np.int64).reshape(-1, 4) for q in splits if q is not None]
@@ -141,14 +212,23 @@ class ObservedStream(object):
         self.allq = np.concatenate(splits)
         ends = np.cumsum([len(q) for q in splits])
         self.ranges = {name: (int(b - len(q)), int(b)) for name, q, b in zip(names, splits, ends)}
-        self.hist_s = HistoryIndex(self.allq, 's', history_len, self.num_ent)    # (raises unless the stream is sorted by time)
-        self.hist_o = HistoryIndex(self.allq, 'o', history_len, self.num_ent)
+        self._hist = {'s': HistoryIndex(self.allq, 's', history_len, self.num_ent),   # (raises unless the stream is sorted by time)
+                      'o': HistoryIndex(self.allq, 'o', history_len, self.num_ent)}
         self.graph_dict = build_graph_dict(self.allq, num_rels)
         self.times = np.unique(self.allq[:, 3])
         self.device = None                                              # the ObservedStore of the last resident() call
 
     def __len__(self):
         return len(self.allq)
+
+    def _history(self, role):
+        # a stream made by observe() has no host index until somebody asks: the device path reads the resident tables
+        if self._hist[role] is None:
+            self._hist[role] = HistoryIndex(self.allq, role, self.history_len, self.num_ent)
+        return self._hist[role]
+
+    hist_s = property(lambda self: self._history('s'))
+    hist_o = property(lambda self: self._history('o'))
 
     def positions(self, split):
         """The stream positions of a split ('train', 'valid', 'test'), in file order."""
@@ -180,17 +260,70 @@ class ObservedStream(object):
     def extended(self, quads):
         """A NEW stream with the newly observed quadruples `quads` [m, 4] appended to the last split (they must be sorted
         by time and not earlier than the stream's last timestamp: ValueError).  A host rebuild of both history indices and
-        the graphs -- the "observe" half of a forecast / observe loop; resident() is called again by the user."""
+        the graphs; resident() is called again by the user.  (observe() gives the same resident stream without the rebuild: the
+        "observe" half of a forecast / observe loop.)"""
+        quads = self._checked_new(quads)
+        names = [n for n in ('train', 'valid', 'test') if n in self.ranges]
+        splits = [self.allq[slice(*self.ranges[n])] for n in names]
+        splits[-1] = np.concatenate((splits[-1], quads))
+        return ObservedStream(splits, self.num_ent, self.num_rels, self.history_len)
+
+    def _checked_new(self, quads):
+        """quads as int64 [m, 4], or the ValueError of extended()."""
         quads = np.asarray(quads, dtype=np.int64).reshape(-1, 4)
         if len(quads) and ((len(self.allq) and quads[0, 3] < self.allq[-1, 3]) or np.any(np.diff(quads[:, 3]) < 0)):
             raise ValueError('appended quadruples must be sorted by time and not earlier than the end of the stream')
         if len(quads) and (quads[:, [0, 2]].min() < 0 or quads[:, [0, 2]].max() >= self.num_ent or quads[:, 1].min() < 0
                            or quads[:, 1].max() >= self.num_rels):
             raise ValueError('appended quadruples hold an entity / relation id outside the stream\'s range')
-        names = [n for n in ('train', 'valid', 'test') if n in self.ranges]
-        splits = [self.allq[slice(*self.ranges[n])] for n in names]
-        splits[-1] = np.concatenate((splits[-1], quads))
-        return ObservedStream(splits, self.num_ent, self.num_rels, self.history_len)
+        return quads
+
+    def _appended(self, quads):
+        """The LIGHT stream of extended(quads), for the device append (gpu_builder.ObservedStore.appended): allq, ranges and
+        times by concatenation; graph_dict a new dict that shares this stream's TimeGraph objects and adds -- for a timestamp
+        equal to the last one, replaces -- only the appended timestamps' graphs; no history index (hist_s / hist_o are built
+        when first read: nothing on the device path reads them).  quads must have passed _checked_new."""
+        new = ObservedStream.__new__(ObservedStream)
+        new.num_ent, new.num_rels, new.history_len = self.num_ent, self.num_rels, self.history_len
+        new.allq = np.concatenate((self.allq, quads))
+        last = [n for n in ('train', 'valid', 'test') if n in self.ranges][-1]
+        new.ranges = dict(self.ranges)
+        new.ranges[last] = (self.ranges[last][0], self.ranges[last][1] + len(quads))
+        new._hist = {'s': None, 'o': None}
+        new.graph_dict = dict(self.graph_dict)
+        t_all = new.allq[:, 3]
+        for t in np.unique(quads[:, 3]):                              # (ascending: the dict stays in time order)
+            a, b = np.searchsorted(t_all, [t, t + 1])
+            new.graph_dict[int(t)] = TimeGraph.from_triples(new.allq[a:b, :3], self.num_rels)
+        new.times = np.asarray(list(new.graph_dict.keys()), dtype=np.int64)
+        new.device = None
+        return new
+
+    def observe(self, quads, global_model):
+        """extended(quads) + resident() WITHOUT the host rebuild: a new stream whose `device` is the resident store of this
+        one with the quadruples appended on the device (gpu_builder.ObservedStore.appended: kernels over the resident tables,
+        nothing but the new facts is uploaded).  Of the global-embedding table only the rows that can have changed are
+        computed -- those of the timestamps >= the first appended one: the row of t_k is global_model.predict(t_{k+1}), the
+        last one predict(last + time unit) (get_global_emb's own rule), and a row of an earlier timestamp reads no appended
+        graph.  Needs an earlier resident() (ValueError); the old stream and its store stay valid.  Equal to
+        extended(quads).resident(model, global_model) bit for bit, PROVIDED the global model's weights have not changed since
+        the rows of the earlier timestamps were computed -- after a weight update call resident() instead."""
+        import torch
+        if self.device is None:
+            raise ValueError('observe() appends to a resident stream: call resident() first')
+        quads = self._checked_new(quads)
+        new = self._appended(quads)
+        rows = {}
+        if len(quads):
+            ts = [int(t) for t in new.times]
+            unit = ts[1] - ts[0] if len(ts) > 1 else 1
+            with torch.no_grad():
+                for k, t in enumerate(ts):
+                    if t >= quads[0, 3]:
+                        nxt = ts[k + 1] if k + 1 < len(ts) else t + unit
+                        rows[t] = global_model.predict(nxt, new.graph_dict)[0].detach()
+        new.device = self.device.appended(quads, rows, _obs=new)
+        return new
 
     def global_table(self, global_model):
         """{t: embedding} over ALL timestamps of the stream, from the global model as it stands and this stream's own

@@ -168,6 +168,10 @@ _SIGNATURES = {
                                        c_void_p]),
     'renet_query_histories': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int,
                                       c_void_p, c_void_p, c_void_p]),
+    'renet_store_append_workspace': (c_size_t, [c_int, c_int]),
+    'renet_store_append': (c_int, [c_void_p] * 7 + [c_int] * 4 + [c_void_p] * 4 + [c_int, c_int] + [c_void_p] * 8
+                           + [c_size_t, c_void_p]),
+    'renet_append_i32': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     'renet_build_full_graphs_workspace': (c_size_t, [c_void_p, c_int, c_int, c_int]),
     'renet_build_full_graphs': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t,
                                         c_void_p]),
@@ -1593,6 +1597,50 @@ def query_histories(ent_ptr, snap_t, num_ent, history_len, ent, as_of):
            'query_histories')
     _timed_end(t0, 'query_histories', nbytes=float(n * 28))
     return win
+
+
+def store_append(old, q_ent, num_ent, history_len, new, cap_snaps):
+    """renet_store_append: the history index of ONE role after the facts `new` were observed.  old = (ent_ptr [num_ent + 1],
+    snap_t, snap_ptr, nbr_o, h_first, h_count) and q_ent [n_quads] (the role's entity of every old quadruple), int32 device
+    tensors that are only read; new = int32 [4, m]: the new facts' entity, time, neighbour and input position, sorted stably
+    by (entity, time, input order); cap_snaps = the snapshots of the longer index (any value in [n_snaps, n_snaps + m]: no
+    store goes past it) -> ((ent_ptr, snap_t, snap_ptr, nbr_o, h_first, h_count) freshly allocated, totals int32 [2] on the
+    device = (snapshots of the longer index, of which opened): the tables are complete when totals[0] == cap_snaps).  Equal
+    to preprocess.HistoryIndex.appended array for array.  On the current stream; nothing is read back."""
+    ent_ptr, snap_t, snap_ptr, nbr_o, h_first, h_count = old
+    num_ent, cap = int(num_ent), int(cap_snaps)
+    n_snaps, nq = int(snap_t.numel()), int(q_ent.numel())
+    if not (new.dim() == 2 and new.shape[0] == 4):
+        raise RenetHipError('store_append: new must be [4, m]')
+    m = int(new.shape[1])
+    if ent_ptr.numel() != num_ent + 1 or snap_ptr.numel() != n_snaps + 1 or \
+            any(int(a.numel()) != nq for a in (nbr_o, h_first, h_count)):
+        raise RenetHipError('store_append: the old index does not fit num_ent / its own lengths')
+    dev = ent_ptr.device
+    mk = lambda n: torch.empty(n, device=dev, dtype=torch.int32)
+    out = (mk(num_ent + 1), mk(cap), mk(cap + 1), mk(nq + m), mk(nq + m), mk(nq + m))
+    totals = mk(2)
+    nbytes = lib().renet_store_append_workspace(num_ent, m)
+    ws = mk(nbytes // 4 + 64)
+    t0 = _timed()
+    _check(lib().renet_store_append(*[_i32(a, 'old index') for a in old], _i32(q_ent, 'q_ent'), num_ent, n_snaps, nq,
+                                    int(history_len), *[_i32(new[k], 'new') if m else None for k in range(4)], m, cap,
+                                    *[_i32(a) for a in out], totals.data_ptr(), ws.data_ptr(), nbytes, _stream()),
+           'store_append')
+    _timed_end(t0, 'store_append', nbytes=float((num_ent + 2 * n_snaps + 4 * nq) * 8))
+    return out, totals
+
+
+def append_i32(old, add, n_old=None):
+    """renet_append_i32: a fresh int32 tensor old[:n_old] ++ add (n_old: None = all of old); both int32 device tensors."""
+    n_old = int(old.numel()) if n_old is None else int(n_old)
+    if not 0 <= n_old <= old.numel():
+        raise RenetHipError('append_i32: n_old outside the old array')
+    n_add = int(add.numel())
+    out = torch.empty(n_old + n_add, device=old.device, dtype=torch.int32)
+    _check(lib().renet_append_i32(_i32(old) if n_old else None, n_old, _i32(add) if n_add else None, n_add,
+                                  out.data_ptr(), _stream()), 'append_i32')
+    return out
 
 
 def joint_row_offsets(scores, num_rels, logits_r):

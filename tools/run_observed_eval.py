@@ -6,13 +6,20 @@ protocol under which RE-GCN, xERTE and TITer report the time-aware filter.  NOT 
 
     python tools/run_observed_eval.py DATA_DIR --n-hidden H --seq-len L [--split valid|test] [--topk K] [--events [K]]
                                       [--model-dir models/<DS>] [--maxpool 1] [--max-batch 4096] [--gpu 0]
-                                      [--horizon H] [--queries FILE [--k K]]
+                                      [--horizon H] [--queries FILE [--k K]] [--observe-loop]
 
 --horizon H evaluates with STALE histories (RENet.evaluate_forecast with ObservedStream.horizon_as_of): the split's timestamps
 are cut into blocks of H, and every query forecasts from the facts before the first timestamp of its block; nothing is
 generated in between.  H is printed with the metrics: numbers of different H (H = 1 is the plain observed protocol) must not
 be mixed.  --queries FILE forecasts open queries instead of a split: a TSV of `s r o t` lines with -1 for an absent side
 (RENet.forecast_topk, time-aware filtered); prints the K best objects of (s, r, ?, t) and subjects of (?, r, o, t).
+
+--observe-loop evaluates the split as a FORECAST / OBSERVE loop: the stream starts with the facts before the split; per
+timestamp t of the split, the facts of t are forecast on the resident store as it stands (RENet.evaluate_forecast: nothing
+of t or later is in it), then observed (ObservedStream.observe: appended on the device, one new row of the global table).
+The filtered settings filter by the whole dataset, as the plain pass does.  Every timestamp is a batch graph of its own
+here, and a row depends on what shares its batch graph: the metrics are those of the plain pass asked timestamp by timestamp,
+close to but not bit for bit those of the plain pass over the whole split.  The times of the two halves are printed apart.
 
 --events adds the EVENT forecasts (RENet.evaluate_events_observed): MRR / Hits of the gold (relation, entity) pair among all
 pairs of the given entity, and of the gold relation given both endpoints, in the three settings; with K also the K most
@@ -32,6 +39,54 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 're-net_amd'))
 
 
+def observe_loop(args, model, global_model, splits, num_ent, num_rels, data_dir):
+    """--observe-loop: forecast t on the store as it stands, then observe t, for every timestamp of the split."""
+    import numpy as np
+    import torch
+    import utils as U
+    from model import SETTINGS
+    from preprocess import ObservedStream
+    known = np.concatenate([q for q in splits if q is not None])       # what the filtered settings filter by, as the plain pass
+    names = [n for n, q in zip(('train', 'valid', 'test'), splits) if q is not None]
+    k = names.index(args.split)
+    evaluated = splits[[i for i, q in enumerate(splits) if q is not None][k]]
+    start = [q for q in splits if q is not None][:k] + [np.zeros((0, 4), dtype=np.int64)]
+    if len(start) < 2:
+        raise SystemExit('nothing lies before the %s split' % args.split)
+    t0 = time.perf_counter()
+    obs = ObservedStream(start, num_ent, num_rels, args.seq_len)
+    obs.resident(model, global_model)
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    ranks, loss, t_forecast, t_observe = {name: [] for name in SETTINGS}, [], 0.0, 0.0
+    times, first = np.unique(evaluated[:, 3], return_index=True)
+    for a, b in zip(first, list(first[1:]) + [len(evaluated)]):
+        q = evaluated[a:b]
+        ta = time.perf_counter()
+        r, l = model.evaluate_forecast(obs, q, all_triplets=known, max_batch=args.max_batch)
+        torch.cuda.synchronize()
+        tb = time.perf_counter()
+        index = getattr(obs.device, '_filter_index', None)
+        obs = obs.observe(q, global_model)
+        obs.device._filter_index = index                               # (the index of `known`, not of the store's own facts)
+        torch.cuda.synchronize()
+        t_forecast, t_observe = t_forecast + tb - ta, t_observe + time.perf_counter() - tb
+        for name in SETTINGS:
+            ranks[name].append(r[name])
+        loss.append(l)
+    ranks, loss = {name: np.concatenate(v) for name, v in ranks.items()}, np.concatenate(loss)
+    print('observed-history protocol as a forecast / observe loop, %s split of %s: %d quadruples at %d timestamps; setup %.2f s, '
+          'forecasts %.2f s, observes %.2f s (%.1f ms per timestamp)'
+          % (args.split, data_dir, len(evaluated), len(times), t1 - t0, t_forecast, t_observe, 1e3 * t_observe / max(len(times), 1)))
+    print('mean loss %.6f' % float(np.mean(loss)))
+    for name in SETTINGS:
+        m = U.rank_metrics(ranks[name])
+        print('%-14s MRR %.6f  MR %.3f  Hits@1 %.6f  Hits@3 %.6f  Hits@10 %.6f'
+              % (name, m['mrr'], m['mr'], m['hits@1'], m['hits@3'], m['hits@10']))
+    print(json.dumps({'protocol': 'observed', 'loop': 'forecast/observe', 'split': args.split, 'n': int(len(evaluated)),
+                      'metrics': {name: U.rank_metrics(ranks[name]) for name in SETTINGS}}))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('data_dir')
@@ -49,6 +104,8 @@ def main():
                     help='evaluate with histories up to H - 1 timestamps stale (blocks of H timestamps of the split)')
     ap.add_argument('--queries', default=None, metavar='FILE', help='TSV of open queries `s r o t` (-1: an absent side)')
     ap.add_argument('--k', type=int, default=10, help='predictions per open query (--queries)')
+    ap.add_argument('--observe-loop', action='store_true',
+                    help='forecast the split timestamp by timestamp, observing each timestamp on the device after its forecast')
     args = ap.parse_args()
     if args.horizon is not None and args.horizon < 1:
         raise SystemExit('--horizon must be >= 1')
@@ -83,6 +140,11 @@ def main():
     global_model.load_state_dict(load(found[0]))
     model.to(dev).eval()
     global_model.to(dev).eval()
+
+    if args.observe_loop:
+        if args.horizon is not None or args.queries is not None or args.events is not None or args.topk:
+            raise SystemExit('--observe-loop runs the plain metrics only')
+        return observe_loop(args, model, global_model, splits, num_ent, num_rels, data_dir)
 
     t0 = time.perf_counter()
     obs = ObservedStream(splits, num_ent, num_rels, args.seq_len)
