@@ -716,6 +716,40 @@ int renet_joint_rank_rows(const float* scores, int ld, int G, int C, int R, cons
                           const int32_t* count_t, int len_t, int32_t* counts, float* at_gold, int32_t* listed,
                           void* stream);
 
+/* Global choice of the generated events of a timestamp (reference model.py:229-258: the num_k best continuations over all
+ * sampled entities, an entity sampled m times counted m times; csrc/event_select.hip; the host statement is
+ * tests/event_select_statement.py).  One call takes the per-row top-k lists of one joint block of G entities ("groups") x
+ * R relation rows -- ent / val [G * R, k]: renet_topk_rows' out_idx / out_val (a row sorted by value descending, empty slots
+ * -1 / -inf), off [G * R]: renet_joint_row_offsets, g_ent / g_lprior / g_mult [G]: the group's entity id, log prior and
+ * multiplicity (>= 1; a smaller value counts as 1) -- and the winners carried from the blocks before it (in_*: [num_k]
+ * each, in_n[1] on the device, the layout of the outputs; all six NULL: none).
+ *   Candidates : slot j of row g * R + r with ent >= 0: value V = (val + off[g * R + r]) + g_lprior[g] (two IEEE fp32
+ *                additions in that order, never contracted), identity (g_ent[g], r, ent), weight g_mult[g]; a -inf value
+ *                is an ordinary candidate that sorts last.  The first min(in_n, num_k) carry entries are candidates too,
+ *                with the values and weights they carry.
+ *   Order      : V descending (float comparison: -0.0 and +0.0 tie), then carry entries in their stored order before block
+ *                candidates, then flat position (g * R + r) * k + j ascending.  With the groups in ascending entity order,
+ *                every entity in one block only, and renet_topk_rows' ties towards the lower column, that is (given
+ *                entity, relation, other entity) ascending: the result is a deterministic function of the inputs.
+ *   Output     : the shortest prefix of that order whose summed weight reaches num_k (all candidates if the total is
+ *                smaller), in that order: out_given / out_rel / out_other / out_val / out_mult [num_k], out_n[1] its length
+ *                (<= num_k, as weights are >= 1); the slots behind out_n hold -1, -1, -1, -inf, 0.  Selection composes:
+ *                the prefix over several blocks is the fold of this call over the blocks, each call's outputs the next
+ *                one's carry.  G == 0 selects among the carry alone: a carry this entry wrote comes back as it is.
+ * Only the first min(k, num_k) slots of a row are read (a row is sorted).  A NaN value sorts below -inf.  1 <= R, k, num_k
+ * <= 1024.  A weighted radix select over a 64-bit (value, place) key that is unique per candidate, then one workgroup
+ * sorts the at most num_k winners: no host synchronisation, integer atomics only, the same result from run to run.
+ * Outputs must not alias inputs.  workspace: renet_select_events_workspace bytes (0 for arguments the entry refuses),
+ * 8-byte aligned; too small, misaligned or NULL: RENET_ERR_WORKSPACE.  RENET_ERR_BADARG for G < 0, R, k or num_k out of
+ * range, a missing array, or a carry with only some of its six pointers; G * R * k beyond int32: RENET_ERR_UNSUPPORTED;
+ * every refusal comes before any launch. */
+size_t renet_select_events_workspace(int G, int R, int k, int num_k);
+int renet_select_events(const int32_t* ent, const float* val, const float* off, const int32_t* g_ent, const float* g_lprior,
+                        const int32_t* g_mult, int G, int R, int k, int num_k, const int32_t* in_given,
+                        const int32_t* in_rel, const int32_t* in_other, const float* in_val, const int32_t* in_mult,
+                        const int32_t* in_n, int32_t* out_given, int32_t* out_rel, int32_t* out_other, float* out_val,
+                        int32_t* out_mult, int32_t* out_n, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * DEVICE batch-graph builder for the merged training batch (both directions of train.py:136-137 as one batch of 2B
  * sequences: graph.build_batch_both; replaces utils.py:209-244 + 115-131 + dgl.batch and this library's own HOST

@@ -1588,28 +1588,40 @@ def _event_blocks(self, ch, name, q_rel, block_floats):
     sub-block: the p_base rows of its groups' steps + the q_rel broadcast, ONE recurrence over the R-fold sequences (ordered
     by sorted position, then relation: the lengths descend, the row order of _winners_pruned), the rows [ent | h | rel_r], one
     score GEMM, renet_joint_row_offsets."""
-    R, dev, H, N = self.num_rels, self.ent_embeds.device, self.h_dim, self.in_dim
+    d = ch.dirs[name]
+    per = _event_groups_per_block(self, block_floats)
+    for g0 in range(0, len(d.ent), per):
+        g1 = min(len(d.ent), g0 + per)
+        yield (g0, g1) + _event_block(self, ch, name, q_rel, np.arange(g0, g1))
+
+
+def _event_groups_per_block(self, block_floats):
+    return max(1, int(block_floats) // max(self.num_rels * self.in_dim, 1))
+
+
+def _event_block(self, ch, name, q_rel, sel):
+    """(B [m * R, N_ent], off [m * R]) of the groups sel [m] of one direction of a chunk -- ascending group indices, so that
+    the lengths descend; rows in sel's order, group-major."""
+    R, dev, H = self.num_rels, self.ent_embeds.device, self.h_dim
     d = ch.dirs[name]
     rel = self.rel_embeds[R:] if name == 'sub' else self.rel_embeds[:R]
     w_hh, b_hh = self.encoder.weight_hh_l0.contiguous(), self.encoder.bias_hh_l0.contiguous()
-    per = max(1, int(block_floats) // max(R * N, 1))
-    for g0 in range(0, len(d.ent), per):
-        g1 = min(len(d.ent), g0 + per)
-        m = g1 - g0
-        ln = ch.lens[d.sp[g0:g1]]                                   # descending
-        if ch.p_base is not None and ln[0] > 0:
-            k_t = [int(np.count_nonzero(ln > t)) for t in range(int(ln[0]))]
-            rows = np.concatenate([ch.step_off[t] + d.sp[g0:g0 + k] for t, k in enumerate(k_t)])
-            gi = (ch.p_base[G.h2d(rows, dev)].view(-1, 1, 3 * H) + q_rel.view(1, R, 3 * H)).reshape(-1, 3 * H)
-            off = ops.host_offsets(np.concatenate(([0], np.cumsum(k_t))) * R)              # every step R times as wide
-            hh, _ = K.gru_fwd(gi, off, H, w_hh, b_hh, out_rows=m * R)                      # [m * R, H]; rows past k_t[0] * R zero
-        else:
-            hh = torch.zeros(m * R, H, device=dev)
-        ent_rows = self.ent_embeds[G.h2d(d.ent[g0:g1], dev)]                                # [m, H]
-        feat = torch.cat((ent_rows.repeat_interleave(R, dim=0), hh[:m * R], rel.repeat(m, 1)), dim=1)
-        block = _linear_eval(self.linear, feat)                                             # [m * R, N_ent]
-        logits_r = _linear_eval(self.linear_r, torch.cat((ent_rows, ch.q_seq[G.h2d(d.seq[g0:g1], dev)]), dim=1))
-        yield g0, g1, block, K.joint_row_offsets(block, R, logits_r)
+    m = len(sel)
+    sp = d.sp[sel]
+    ln = ch.lens[sp]                                                # descending
+    if ch.p_base is not None and ln[0] > 0:
+        k_t = [int(np.count_nonzero(ln > t)) for t in range(int(ln[0]))]
+        rows = np.concatenate([ch.step_off[t] + sp[:k] for t, k in enumerate(k_t)])
+        gi = (ch.p_base[G.h2d(rows, dev)].view(-1, 1, 3 * H) + q_rel.view(1, R, 3 * H)).reshape(-1, 3 * H)
+        off = ops.host_offsets(np.concatenate(([0], np.cumsum(k_t))) * R)                  # every step R times as wide
+        hh, _ = K.gru_fwd(gi, off, H, w_hh, b_hh, out_rows=m * R)                          # [m * R, H]; rows past k_t[0] * R zero
+    else:
+        hh = torch.zeros(m * R, H, device=dev)
+    ent_rows = self.ent_embeds[G.h2d(d.ent[sel], dev)]                                      # [m, H]
+    feat = torch.cat((ent_rows.repeat_interleave(R, dim=0), hh[:m * R], rel.repeat(m, 1)), dim=1)
+    block = _linear_eval(self.linear, feat)                                                 # [m * R, N_ent]
+    logits_r = _linear_eval(self.linear_r, torch.cat((ent_rows, ch.q_seq[G.h2d(d.seq[sel], dev)]), dim=1))
+    return block, K.joint_row_offsets(block, R, logits_r)
 
 
 def _event_setup(self, obs, idx):
@@ -1881,6 +1893,144 @@ def _forecast_events(self, obs, ents, t, k=10, direction='ob', all_triplets=None
                                     setting, sides=(direction,))[direction]
 
 
+# =================================================================================================
+# Rollout horizon under the observed protocol (the reference's generate-in-between idea, model.py:222-328, on the resident
+# stream): the truth is observed every h timestamps, and the steps in between see the model's own generated facts --
+# ObservedStream.observe appends them to a chain that branches off the truth stream and is dropped after the block (the
+# old store stays valid).  Three protocols, three sets of numbers: this one, the stale-history horizon
+# (evaluate_forecast(as_of=horizon_as_of)) and the reference's multi-step state machine (evaluate_all_stream).
+# =================================================================================================
+def _generate_events_observed(self, obs, t, global_model, num_k=None, picks=None, block_floats=1 << 28):
+    """The facts the model generates for timestamp t from the resident stream obs (everything the model knows: t must lie
+    after its last timestamp, no as_of is taken): host int64 [m, 4], unique, sorted by (s, r, o), time column t, m <= 2 *
+    num_k (default self.num_k; <= 1024).  Per direction -- 'ob': the picked entities as subjects, pairs (r, o); 'sub': as
+    objects, pairs (r, s) -- prob = global_model.predict(t, obs.graph_dict, subject = direction is 'ob')[2]; the picked
+    entities are picks(t, direction, prob) (an int array / tensor of draws, repeats counting) or self.sample_entities(prob);
+    their joint blocks at t are forecast_events' (a QueryStore with relation column 0 and the other side absent: one encoder
+    chunk, one merged batch graph), taken in sub-blocks of at most block_floats floats over ASCENDING entities; per sub-block
+    renet_topk_rows gives every row's min(num_k, 1024) best (setting raw) and renet_select_events folds them into the
+    direction's winners: the num_k best continuations by V = (score + row offset) + log prob[entity], an entity drawn m
+    times counting m times (model.py:229-258), ties by (entity, relation, other entity) ascending.  Nothing is read back
+    inside the loops; ONE device-to-host copy brings both directions' winners, and their union is taken on the host (observe()
+    builds the facts' TimeGraph there anyway).  self.last_generate = {direction: {'entities', 'blocks', 'winners'}}."""
+    store = _observed_store(obs)
+    stream = getattr(store, 'obs', None)
+    if stream is None or not hasattr(stream, 'graph_dict'):
+        raise ValueError('generate_events_observed needs the resident ObservedStream (its graph_dict feeds the global model)')
+    t = int(t)
+    if len(stream.times) and t <= int(stream.times[-1]):
+        raise ValueError('generate_events_observed: t = %d does not lie after the stream\'s last timestamp %d'
+                         % (t, int(stream.times[-1])))
+    num_k = int(self.num_k if num_k is None else num_k)
+    R, dev = self.num_rels, self.ent_embeds.device
+    if not 1 <= num_k <= K.SELECT_EVENTS_MAX:
+        raise ValueError('generate_events_observed: num_k must lie in [1, %d]' % K.SELECT_EVENTS_MAX)
+    if R > K.SELECT_EVENTS_MAX:
+        raise ValueError('generate_events_observed takes at most %d relations' % K.SELECT_EVENTS_MAX)
+    per = _event_groups_per_block(self, block_floats)
+    sels, stats = {}, {}
+    with torch.no_grad():
+        q_rel = _event_q_rel(self)
+        for name in ('ob', 'sub'):
+            prob = global_model.predict(t, stream.graph_dict, subject=name == 'ob')[2]
+            drawn = picks(t, name, prob) if picks is not None else self.sample_entities(prob)
+            drawn = np.asarray(drawn.cpu() if isinstance(drawn, torch.Tensor) else drawn, dtype=np.int64).reshape(-1)
+            ents, mult = np.unique(drawn, return_counts=True)
+            if len(ents) == 0 or ents[0] < 0 or ents[-1] >= self.in_dim or len(ents) > K.SELECT_EVENTS_MAX:
+                raise ValueError('generate_events_observed: picks must give 1 .. %d distinct entities of [0, num_ent)'
+                                 % K.SELECT_EVENTS_MAX)
+            none, zero = np.full_like(ents, -1), np.zeros_like(ents)
+            quads = np.stack((ents, zero, none, np.full_like(ents, t)) if name == 'ob' else
+                             (none, zero, ents, np.full_like(ents, t)), axis=1)
+            qs = _query_store(store, quads)
+            lprior = torch.log(prob[G.h2d(ents, dev)])
+            mult_dev = G.h2d(mult.astype(np.int32), dev)
+            sel = sels[name] = ops.EventSelection(num_k, dev)
+            n_blocks = 0
+            ch, = _event_chunks(self, qs, np.arange(qs.n_quads))                           # <= 1024 queries: one chunk
+            d = ch.dirs[name]
+            by_ent = np.argsort(d.ent, kind='stable')                                      # group indices, entity ascending
+            assert np.array_equal(d.ent[by_ent], ents)
+            for a in range(0, len(ents), per):
+                groups = np.sort(by_ent[a:a + per])                                        # ascending group index: lengths descend
+                block, off = _event_block(self, ch, name, q_rel[name], groups)
+                idx, val, _, _ = K.topk_rows(block, min(num_k, 1024), want_logp=False)     # [m * R, k] each
+                # the block's rows back into ascending entity order
+                back = np.argsort(d.ent[groups], kind='stable')
+                rows = G.h2d((back[:, None] * R + np.arange(R)[None, :]).reshape(-1), dev)
+                sel.add(idx[rows].contiguous(), val[rows].contiguous(), off[rows].contiguous(),
+                        G.h2d(ents[a:a + per].astype(np.int32), dev), lprior[a:a + per].contiguous(),
+                        mult_dev[a:a + per].contiguous())
+                n_blocks += 1
+            stats[name] = {'entities': int(len(ents)), 'blocks': n_blocks}
+    won = ops.EventSelection.results([sels['ob'], sels['sub']])
+    facts = []
+    for name, (given, rel, other, _, _) in zip(('ob', 'sub'), won):
+        stats[name]['winners'] = int(len(given))
+        facts.append(np.stack((given, rel, other) if name == 'ob' else (other, rel, given), axis=1).astype(np.int64))
+    facts = np.unique(np.concatenate(facts), axis=0)
+    self.last_generate = stats
+    return np.concatenate((facts, np.full((len(facts), 1), t, dtype=np.int64)), axis=1)
+
+
+def _evaluate_rollout(self, obs, quads, h, global_model, all_triplets=None, max_batch=4096, picks=None,
+                      block_floats=1 << 28):
+    """evaluate_forecast of the labelled, time-sorted quads under the ROLLOUT horizon h >= 1: the timestamps of quads are cut
+    into blocks of h consecutive ones (horizon_as_of's rule); inside a block the first timestamp is forecast from the truth
+    stream -- obs (resident, ending before quads[0, 3]) plus the true facts of the earlier blocks -- and every later one from
+    that stream plus the facts generate_events_observed gave for the block's timestamps before it, appended with
+    ObservedStream.observe; after the block its true facts are observed and the generated chain is dropped.  h = 1 is the
+    forecast / observe loop.  all_triplets: what the filtered settings filter by (None: obs.allq and quads together);
+    generated facts never enter a filter, and the filter index is built once and handed from store to store.  picks: as in
+    generate_events_observed.  -> (ranks, loss) in evaluate_forecast's layout, in quads order; self.last_rollout lists, per
+    generated timestamp, {'t', 'generated', 'true'}: the facts generated and how many of them are true facts of t."""
+    h = int(h)
+    if h < 1:
+        raise ValueError('horizon must be >= 1')
+    store = _observed_store(obs)
+    truth = getattr(store, 'obs', None)
+    if truth is None or not hasattr(truth, 'observe'):
+        raise ValueError('evaluate_rollout needs the resident ObservedStream')
+    quads = np.asarray(quads.cpu() if isinstance(quads, torch.Tensor) else quads, dtype=np.int64).reshape(-1, 4)
+    if len(quads) == 0 or np.any(np.diff(quads[:, 3]) < 0):
+        raise ValueError('evaluate_rollout takes labelled quadruples sorted by time')
+    if len(truth.times) and int(truth.times[-1]) >= quads[0, 3]:
+        raise ValueError('evaluate_rollout: the stream must end before the first evaluated timestamp')
+    known = all_triplets if all_triplets is not None else np.concatenate((truth.allq, quads))
+
+    def observed(stream, facts):
+        index = getattr(stream.device, '_filter_index', None)
+        new = stream.observe(facts, global_model)
+        new.device._filter_index = index                                                   # (the index of `known`)
+        return new
+
+    times, first = np.unique(quads[:, 3], return_index=True)
+    ends = list(first[1:]) + [len(quads)]
+    ranks, loss, log = {}, [], []
+    for b0 in range(0, len(times), h):
+        b1 = min(b0 + h, len(times))
+        cur = truth
+        for j in range(b0, b1):
+            q = quads[first[j]:ends[j]]
+            r, l = _evaluate_forecast(self, cur, q, all_triplets=known, max_batch=max_batch)
+            for name, v in r.items():
+                ranks.setdefault(name, []).append(v)
+            loss.append(l)
+            if j + 1 < b1:
+                gen = _generate_events_observed(self, cur, int(times[j]), global_model, picks=picks, block_floats=block_floats)
+                true = {tuple(x) for x in q[:, :3].tolist()}
+                log.append({'t': int(times[j]), 'generated': int(len(gen)),
+                            'true': int(sum(tuple(x) in true for x in gen[:, :3].tolist()))})
+                if len(gen):
+                    cur = observed(cur, gen)
+        if b1 < len(times):                                                                # (the chain `cur` is dropped here)
+            truth = observed(truth, quads[first[b0]:ends[b1 - 1]])
+    self.last_rollout = log
+    return {name: np.concatenate(v) for name, v in ranks.items()}, np.concatenate(loss)
+
+
+RENet.generate_events_observed = _moded(_generate_events_observed)
+RENet.evaluate_rollout = _moded(_evaluate_rollout)
 RENet.forecast_scores = _moded(_forecast_scores)
 RENet.forecast_topk = _moded(_forecast_topk)
 RENet.evaluate_forecast = _moded(_evaluate_forecast)

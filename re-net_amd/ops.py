@@ -1023,3 +1023,42 @@ def host_offsets(step_off):
     """int array -> ctypes int32 array kept alive by the caller (the GRU entry points read it on the host)."""
     arr = np.ascontiguousarray(step_off, dtype=np.int32)
     return (ctypes.c_int32 * len(arr))(*arr.tolist())
+
+
+class EventSelection(object):
+    """The running global choice of one direction's generated events (K.select_events folded over the sub-blocks of a
+    timestamp): owns the carry -- the winners so far, device tensors that nothing reads back until result() -- and the
+    kernel's workspace, which every add() reuses (calls are ordered on one stream)."""
+
+    def __init__(self, num_k, device):
+        self.num_k, self.device = int(num_k), device
+        if not 1 <= self.num_k <= K.SELECT_EVENTS_MAX:
+            raise ValueError('num_k must lie in [1, %d] (renet_select_events)' % K.SELECT_EVENTS_MAX)
+        self.carry = None
+        self.workspace = torch.empty(max(K.lib().renet_select_events_workspace(1, 1, 1, self.num_k) // 8, 1), device=device,
+                                     dtype=torch.int64)
+
+    def add(self, ent, val, off, g_ent, g_lprior, g_mult):
+        """One sub-block: topk_rows' (idx, val) [G * R, k], joint_row_offsets' off [G * R], and per group the entity, its
+        log prior and its multiplicity."""
+        self.carry = K.select_events(ent, val, off, g_ent, g_lprior, g_mult, self.num_k, self.carry, self.workspace)
+
+    def _rows(self):
+        c = self.carry                                   # [6, num_k] int32: the fp32 values as their bit patterns
+        return torch.stack((c[0], c[1], c[2], c[3].view(torch.int32), c[4], c[5].expand(self.num_k)))
+
+    @staticmethod
+    def results(selections):
+        """Per selection (given, rel, other, val, mult) as host arrays cut to the winners; ONE device-to-host copy for all
+        of them (a selection nothing was added to gives empty arrays)."""
+        live = [s for s in selections if s.carry is not None]
+        back = iter(torch.cat([s._rows() for s in live]).cpu().numpy().reshape(len(live), 6, -1)) if live else iter(())
+        out = []
+        for s in selections:
+            if s.carry is None:
+                out.append(tuple(np.zeros(0, dtype=t) for t in (np.int32, np.int32, np.int32, np.float32, np.int32)))
+                continue
+            a = next(back)
+            n = int(a[5, 0])
+            out.append((a[0, :n], a[1, :n], a[2, :n], a[3, :n].copy().view(np.float32), a[4, :n]))
+        return out

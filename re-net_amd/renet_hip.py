@@ -160,6 +160,8 @@ _SIGNATURES = {
     'renet_joint_rank_rows': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                       c_void_p, c_void_p, c_void_p]),
+    'renet_select_events_workspace': (c_size_t, [c_int, c_int, c_int, c_int]),
+    'renet_select_events': (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_void_p] * 12 + [c_void_p, c_size_t, c_void_p]),
     'renet_topk_workspace': (c_size_t, [c_int]),
     'renet_topk_positive': (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
                                     c_void_p]),
@@ -1662,6 +1664,50 @@ def joint_row_offsets(scores, num_rels, logits_r):
                                          _block_ld(logits_r), off.data_ptr(), _stream()), 'joint_row_offsets')
     _timed_end(t0, 'joint_row_offsets', nbytes=float(rows * c * 4))
     return off
+
+
+SELECT_EVENTS_MAX = 1024               # renet_select_events: R, k and num_k at most this
+
+
+def select_events(ent, val, off, g_ent, g_lprior, g_mult, num_k, carry=None, workspace=None):
+    """renet_select_events: the global choice of the generated events over one block and the winners carried so far.
+    ent int32 / val fp32 [G * R, k] (topk_rows' idx / val), off fp32 [G * R] (joint_row_offsets), g_ent int32 / g_lprior fp32 /
+    g_mult int32 [G] (G = 0: the six may be None); carry: None or an earlier result -> (given, rel, other int32 [num_k], val
+    fp32 [num_k], mult int32 [num_k], n int32 [1]), fresh device tensors: the shortest prefix, by (V descending, carry first,
+    flat position), whose summed multiplicity reaches num_k, V = (val + off[row]) + g_lprior[g] in fp32; the slots behind n
+    hold -1, -1, -1, -inf, 0.  workspace: an int64 device tensor to use (None: allocated here).  Nothing is read back."""
+    num_k = int(num_k)
+    if g_ent is None:
+        g, r, k = 0, 1, 1
+        if carry is None:
+            raise RenetHipError('select_events: no block and no carry')
+        dev = carry[0].device
+    else:
+        g = int(g_ent.numel())
+        rows, k = (int(x) for x in ent.shape)
+        r = rows // max(g, 1)
+        dev = g_ent.device
+        if ent.dim() != 2 or g < 1 or rows != g * r or tuple(val.shape) != (rows, k) or off.numel() != rows or \
+                g_lprior.numel() != g or g_mult.numel() != g:
+            raise RenetHipError('select_events: shape mismatch')
+    if carry is not None and (len(carry) != 6 or any(int(c.numel()) != num_k for c in carry[:5]) or carry[5].numel() != 1):
+        raise RenetHipError('select_events: a carry is an earlier result for the same num_k')
+    nbytes = lib().renet_select_events_workspace(g, r, k, num_k)
+    if workspace is None or workspace.numel() * 8 < nbytes:
+        workspace = torch.empty(max(nbytes // 8, 1), device=dev, dtype=torch.int64)
+    n_out = max(num_k, 0)
+    out = tuple(torch.empty(n_out, device=dev, dtype=torch.int32) for _ in range(3)) + \
+        (torch.empty(n_out, device=dev, dtype=torch.float32), torch.empty(n_out, device=dev, dtype=torch.int32),
+         torch.empty(1, device=dev, dtype=torch.int32))
+    ptr = lambda c, j: None if c is None else (_f32(c[j], 'carry') if j == 3 else _i32(c[j], 'carry'))
+    blk = [None] * 6 if g == 0 else [_i32(ent, 'ent'), _f32(val, 'val'), _f32(off, 'off'), _i32(g_ent, 'g_ent'),
+                                     _f32(g_lprior, 'g_lprior'), _i32(g_mult, 'g_mult')]
+    t0 = _timed()
+    _check(lib().renet_select_events(*blk, g, r, k, num_k, *[ptr(carry, j) for j in range(6)],
+                                     *[ptr(out, j) for j in range(6)], workspace.data_ptr(), workspace.numel() * 8,
+                                     _stream()), 'select_events')
+    _timed_end(t0, 'select_events', nbytes=float(g * r * min(k, max(num_k, 1)) * 8 * 7))
+    return out
 
 
 def joint_rank_rows(scores, num_rels, off, group, gold_r, gold_c, cols_a=None, start_a=None, count_a=None, cols_t=None,

@@ -7,6 +7,7 @@ protocol under which RE-GCN, xERTE and TITer report the time-aware filter.  NOT 
     python tools/run_observed_eval.py DATA_DIR --n-hidden H --seq-len L [--split valid|test] [--topk K] [--events [K]]
                                       [--model-dir models/<DS>] [--maxpool 1] [--max-batch 4096] [--gpu 0]
                                       [--horizon H] [--queries FILE [--k K]] [--observe-loop]
+                                      [--rollout H [--num-k K]]
 
 --horizon H evaluates with STALE histories (RENet.evaluate_forecast with ObservedStream.horizon_as_of): the split's timestamps
 are cut into blocks of H, and every query forecasts from the facts before the first timestamp of its block; nothing is
@@ -20,6 +21,14 @@ of t or later is in it), then observed (ObservedStream.observe: appended on the 
 The filtered settings filter by the whole dataset, as the plain pass does.  Every timestamp is a batch graph of its own
 here, and a row depends on what shares its batch graph: the metrics are those of the plain pass asked timestamp by timestamp,
 close to but not bit for bit those of the plain pass over the whole split.  The times of the two halves are printed apart.
+
+--rollout H evaluates under the ROLLOUT horizon (RENet.evaluate_rollout): the stream starts with the facts before the split,
+as --observe-loop; the split's timestamps are cut into blocks of H; the first timestamp of a block is forecast from the true
+facts before it, every later one from those plus the facts the model GENERATED for the block's earlier timestamps
+(RENet.generate_events_observed, appended with ObservedStream.observe); the truth is observed after every block.  Its
+numbers are neither those of --horizon H (nothing generated) nor the reference's multi-step numbers (test.py: per-entity
+caches, no observed truth at all): three protocols, three sets of numbers.  Exclusive with --horizon, --observe-loop,
+--queries and --events.
 
 --events adds the EVENT forecasts (RENet.evaluate_events_observed): MRR / Hits of the gold (relation, entity) pair among all
 pairs of the given entity, and of the gold relation given both endpoints, in the three settings; with K also the K most
@@ -87,6 +96,43 @@ def observe_loop(args, model, global_model, splits, num_ent, num_rels, data_dir)
                       'metrics': {name: U.rank_metrics(ranks[name]) for name in SETTINGS}}))
 
 
+def rollout_loop(args, model, global_model, splits, num_ent, num_rels, data_dir):
+    """--rollout H: RENet.evaluate_rollout over the split, from the facts before it."""
+    import numpy as np
+    import torch
+    import utils as U
+    from model import SETTINGS
+    from preprocess import ObservedStream
+    present = [q for q in splits if q is not None]
+    known = np.concatenate(present)                                    # what the filtered settings filter by, as the plain pass
+    k = [n for n, q in zip(('train', 'valid', 'test'), splits) if q is not None].index(args.split)
+    evaluated = present[k]
+    start = present[:k] + [np.zeros((0, 4), dtype=np.int64)]
+    if len(start) < 2:
+        raise SystemExit('nothing lies before the %s split' % args.split)
+    t0 = time.perf_counter()
+    obs = ObservedStream(start, num_ent, num_rels, args.seq_len)
+    obs.resident(model, global_model)
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    model.num_k = args.num_k
+    ranks, loss = model.evaluate_rollout(obs, evaluated, args.rollout, global_model, all_triplets=known, max_batch=args.max_batch)
+    torch.cuda.synchronize()
+    t2 = time.perf_counter()
+    log = model.last_rollout
+    print('observed-history protocol, ROLLOUT horizon H = %d, %s split of %s: %d quadruples at %d timestamps; setup %.2f s, '
+          'pass %.2f s; %d generated timestamps, %d generated facts of which %d true'
+          % (args.rollout, args.split, data_dir, len(evaluated), len(np.unique(evaluated[:, 3])), t1 - t0, t2 - t1, len(log),
+             sum(e['generated'] for e in log), sum(e['true'] for e in log)))
+    print('mean loss %.6f' % float(np.mean(loss)))
+    for name in SETTINGS:
+        m = U.rank_metrics(ranks[name])
+        print('%-14s MRR %.6f  MR %.3f  Hits@1 %.6f  Hits@3 %.6f  Hits@10 %.6f'
+              % (name, m['mrr'], m['mr'], m['hits@1'], m['hits@3'], m['hits@10']))
+    print(json.dumps({'horizon': args.rollout, 'protocol': 'observed', 'loop': 'rollout', 'split': args.split,
+                      'n': int(len(evaluated)), 'metrics': {name: U.rank_metrics(ranks[name]) for name in SETTINGS}}))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('data_dir')
@@ -106,9 +152,17 @@ def main():
     ap.add_argument('--k', type=int, default=10, help='predictions per open query (--queries)')
     ap.add_argument('--observe-loop', action='store_true',
                     help='forecast the split timestamp by timestamp, observing each timestamp on the device after its forecast')
+    ap.add_argument('--rollout', type=int, default=None, metavar='H',
+                    help='rollout horizon: observe the truth every H timestamps, feed generated facts to the steps in between')
+    ap.add_argument('--num-k', type=int, default=1000, help='continuations kept per direction and generated timestamp (--rollout)')
     args = ap.parse_args()
     if args.horizon is not None and args.horizon < 1:
         raise SystemExit('--horizon must be >= 1')
+    if args.rollout is not None:
+        if args.rollout < 1:
+            raise SystemExit('--rollout must be >= 1')
+        if args.horizon is not None or args.observe_loop or args.queries is not None or args.events is not None:
+            raise SystemExit('--rollout is exclusive with --horizon, --observe-loop, --queries and --events')
 
     os.environ.setdefault('TORCH_FORCE_NO_WEIGHTS_ONLY_LOAD', '1')      # (the drivers' checkpoints hold numpy arrays)
     import numpy as np
@@ -145,6 +199,8 @@ def main():
         if args.horizon is not None or args.queries is not None or args.events is not None or args.topk:
             raise SystemExit('--observe-loop runs the plain metrics only')
         return observe_loop(args, model, global_model, splits, num_ent, num_rels, data_dir)
+    if args.rollout is not None:
+        return rollout_loop(args, model, global_model, splits, num_ent, num_rels, data_dir)
 
     t0 = time.perf_counter()
     obs = ObservedStream(splits, num_ent, num_rels, args.seq_len)
