@@ -9,7 +9,8 @@
 //   on v_mfma_f32_32x32x16_f16 with two fp32 accumulators per output element (the 2^-11 is applied once, in the
 //   epilogue; the dropped pair a2 b2 2^-22 is <= 2^-22 |a b|): every product is accurate to ~2^-21 (worst case; the
 //   errors are unbiased and average out along k -- a K-long dot product comes out within a small multiple of what fp32
-//   products with fp32 accumulation give, tests/test_gpu_parity.py).  f16 x f16 products are exact in fp32.  THREE
+//   products with fp32 accumulation give; both statements are held against fp64 in tests/test_gpu_gemm_products.py, the
+//   single products on magnitudes within one binade of the tensor's largest).  f16 x f16 products are exact in fp32.  THREE
 //   matrix instructions per fragment pair where the bf16x6 split (24 significant bits, worst case 2^-23) needs six,
 //   two LDS planes per operand instead of three: the bf16 split spends 16 of a plane's bits on fp32's exponent range,
 //   which a GEMM operand does not need per ELEMENT once the tensor's magnitude is factored out.

@@ -5,7 +5,8 @@
 // optimizer step).  The k-loop then contains no conversion at all: no v_cvt / v_sub, no ds_write -- the resource the
 // in-loop split is bound by (a SIMD's conversion VALU work and its partner's MFMAs serialise, the matrix
 // pipe idles half of every k-tile).  An operand element is split ONCE per step instead of once per output tile that
-// reads it (the logits GEMM re-split `feat` 180 times and the weight 8 times).
+// reads it (the logits GEMM re-split `feat` 180 times and the weight 8 times).  The arithmetic of the 128-row, the 256-row
+// and the persistent form against fp64 (single products, units, integers): tests/test_gpu_gemm_products.py.
 //
 // PLANE FORMAT "T16" (renet_t16_off in common.h; tools/p6_layout_sim.py is its executable specification): a plane of a matrix
 // [Rp, Cp] (multiples of 256) is stored as 16 x 16 tiles of 512 bytes, tile (tr, tc) at ((tr * Cp / 16) + tc) * 256

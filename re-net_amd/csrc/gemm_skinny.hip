@@ -13,7 +13,8 @@
 //     with float4 loads, split it on the way into LDS (three planes, [row][k], odd 16-byte row stride), and every
 //     wave reads the SAME A fragments (one ds_read_b128 per plane and k-step) against its own B registers;
 //   * bf16x6 arithmetic as in gemm_split.hip (x = x1 + x2 + x3, six term pairs on v_mfma_f32_32x32x16_bf16, fp32
-//     accumulate, smallest terms first); even and odd k-steps accumulate into two independent chains.
+//     accumulate, smallest terms first); even and odd k-steps accumulate into two independent chains.  Both K variants
+//     against fp64 (single products, units, integers): tests/test_gpu_gemm_products.py.
 // Workgroups are persistent over row tiles (tile = blockIdx.x, += gridDim.x).  Matrix work per 32-row tile and wave:
 // 78 MFMAs (K = 208); a 23 033-row product is 720 tiles, < 3 per CU.
 #include "common.h"

@@ -6,8 +6,9 @@
 //        a1 b1 + (a1 b2 + a2 b1) + (a1 b3 + a2 b2 + a3 b1)
 //   each on v_mfma_f32_32x32x16_bf16 with fp32 accumulation.  bf16 x bf16 products are exact in fp32;
 //   the dropped pairs (a2 b3, a3 b2, a3 b3) are <= 2^-23 |a b|, i.e. at the fp32 rounding level, so the
-//   result is an fp32-class GEMM (measured against fp64 in tests/test_gpu_parity.py next to the
-//   v_mfma_f32_32x32x2_f32 kernel of gemm.hip) -- while the matrix pipe runs 16x faster per product:
+//   result is an fp32-class GEMM (every kernel here against fp64 in tests/test_gpu_gemm_products.py: single products
+//   within 2^-22, which no five of the six pairs keep, dense products in units of the dot product's own fp32 bound next to
+//   the v_mfma_f32_32x32x2_f32 kernel of gemm.hip, integers exactly) -- while the matrix pipe runs 16x faster per product:
 //   6 bf16 MFMAs replace 16/6 = 2.67x their time in f32-input MFMAs.
 //
 // Two k-loop structures share the tile (128x128x32, 4 waves 2x2, each wave 2x2 MFMA tiles of 32x32) and the

@@ -3,43 +3,13 @@ tensor scale from a magnitude bound, two binary16 planes per operand, three exac
 fp32, cross terms scaled by 2^-11 once.  Checks the error claims the header makes, independently of any GPU: every
 element is represented to 2^-22 relative (two 11-bit significands) at any tensor magnitude, GEMM results stay in the
 class of plain fp32 products, a bound 2^10 too large only costs binades, elements below 2^-29 max |x| keep an absolute
-error of 2^-39 max |x|.  (The GPU tests compare the kernel itself with fp64 and with
-the exact-fp32 MFMA kernel: tests/test_gpu_parity.py.)"""
+error of 2^-39 max |x|.  (The arithmetic itself lives in tests/gemm_statement.py;
+the GPU tests compare the kernel itself with fp64: tests/test_gpu_gemm_products.py, tests/test_gpu_parity.py.)"""
 import numpy as np
 import pytest
 
 
-def scale_of(bound):
-    """2^(15 - e) for bound = m 2^e, m in [0.5, 1)  (h3_scale_of)."""
-    if not np.isfinite(bound) or bound <= 0:
-        return 2.0 ** 126
-    _, e = np.frexp(np.float32(bound))
-    return float(2.0 ** min(max(15 - int(e), -126), 126))
-
-
-def split(x, s):
-    xs = (x.astype(np.float32) * np.float32(s)).astype(np.float32)
-    h1 = xs.astype(np.float16)
-    h2 = ((xs - h1.astype(np.float32)) * np.float32(2048.0)).astype(np.float16)
-    return h1, h2
-
-
-def f16x3_matmul(a, b, bound_a=None, bound_b=None):
-    """a [M, K] @ b [N, K]^T as the kernel computes it (fp32 accumulation by numpy's float32 matmul)."""
-    sa = scale_of(np.abs(a).max() if bound_a is None else bound_a)
-    sb = scale_of(np.abs(b).max() if bound_b is None else bound_b)
-    a1, a2 = split(a, sa)
-    b1, b2 = split(b, sb)
-    f = lambda h: h.astype(np.float32)                                        # noqa: E731
-    main = f(a1) @ f(b1).T
-    corr = f(a1) @ f(b2).T + f(a2) @ f(b1).T
-    return ((main + corr * np.float32(2.0 ** -11)).astype(np.float64) / sa) / sb
-
-
-def units(a, b, c):
-    ref = a.astype(np.float64) @ b.astype(np.float64).T
-    unit = (np.abs(a).astype(np.float64) @ np.abs(b).astype(np.float64).T) * 2.0 ** -24
-    return np.abs(c - ref) / unit
+from gemm_statement import scale_of, split, f16x3_matmul, units         # noqa: F401  (moved to tests/gemm_statement.py)
 
 
 @pytest.mark.parametrize('sa,sb', [(1.0, 1.0), (3e-9, 7e4), (5e7, 2e-6), (1e-20, 1e-12), (1e15, 1e10)])
