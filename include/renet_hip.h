@@ -516,6 +516,16 @@ int renet_concat3_bwd(const float* dfeat, int B, int D, int parts, float drop_p,
 int renet_dropout(const float* x, size_t n, float drop_p, uint64_t seed, float* y, void* stream);
 int renet_softmax_ce(const float* logits, const int32_t* target, int B, int C, int ld,
                      float grad_scale, float* row_loss, float* dlogits, void* stream);
+/* Softmax cross-entropy against SPARSE SOFT targets (the global model's loss, global_model.py:52-55, with the target
+ * distribution of row b given as the entries k in [tgt_ptr[b], tgt_ptr[b + 1]): columns tgt_col[k] -- distinct, ascending,
+ * in [0, C) -- with weights tgt_w[k] >= 0 that need NOT sum to 1).  With W = sum_k tgt_w[k] and p = softmax(logits[b, :]):
+ *   row_loss[b]   = W * logsumexp(logits[b, :]) - sum_k tgt_w[k] * logits[b, tgt_col[k]]
+ *   dlogits[b, c] = grad_scale * (W * p_c - w_c)          (w_c = the weight of column c, 0 if it is not a target)
+ * dlogits may be NULL (loss only) or alias logits (in place).  An empty row gives loss 0 and a zero gradient; a -inf logit
+ * gives gradient 0 in its column.  ld >= C is the row stride (elements) of logits and dlogits; nothing outside the
+ * [B, C] block is touched.  No atomics: the result is a function of the inputs alone.  (csrc/soft_ce.hip) */
+int renet_soft_ce_sparse(const float* logits, int B, int C, int ld, const int32_t* tgt_ptr, const int32_t* tgt_col,
+                         const float* tgt_w, float grad_scale, float* row_loss, float* dlogits, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Per-graph readout of the global model (Aggregator.py:58-61 dgl.max_nodes / mean_nodes):

@@ -75,5 +75,22 @@ class RENet_global(nn.Module):
         out[last] = self.predict(last + int(time_unit), graph_dict)[0].detach()
         return out
 
+    @_moded
+    def learn_observed(self, obs, times, optimizer, subject=None, grad_norm=1.0):
+        """ONE optimisation step of the global model on the timestamps `times` of a RESIDENT preprocess.ObservedStream
+        (extension of the reference API): forward()'s loss -- aggregator.forward -> encoder_global -> Linear -> soft
+        cross-entropy, the row of t predicted from the <= seq_len graphs before t -- with the targets taken from the stream's
+        own facts: row t is the counts of the subjects (objects) among the facts AT t divided by the number of facts at t.
+        That is the clean per-timestamp distribution, NOT utils.get_true_distribution's bucketing (utils.py:292-324 counts
+        the first fact of a timestamp in the previous timestamp's row and leaves the last row un-normalised).  The targets
+        are built on the host as CSR lists from obs.graph_dict (online.stream_targets), uploaded once per call, and the
+        loss and its gradient come from the sparse-target kernel (ops.SoftCESparseFn: no dense [B, N_ent] float64 target
+        matrix crosses the bus, no float64 log_softmax).  subject=True / False: one head, paired with the distributions as
+        forward() pairs them (linear_s against the objects'); None: both heads, the sum of the two means.  optimizer: a
+        parallel.HipAdam of this model or a torch.optim.Optimizer (clip_grad_norm_(grad_norm), step(), zero_grad(), as
+        pretrain.py:84-87).  The resident table is stale afterwards: obs.refresh_global(self).  -> the loss, a Python float."""
+        import online
+        return online.global_learn_observed(self, obs, times, optimizer, subject, grad_norm)
+
     def update_global_emb(self, t, graph_dict):
         pass

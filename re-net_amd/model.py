@@ -2067,3 +2067,5 @@ RENet.evaluate_all_batch = _moded(_evaluate_all_batch)
 RENet.evaluate_all_stream = _moded(_evaluate_all_stream)
 RENet.predict_topk_batch = _moded(_predict_topk_batch)
 RENet.predict_topk_stream = _moded(_predict_topk_stream)
+
+import online  # noqa: E402,F401  (binds RENet.learn_observed / RENet.evaluate_online: the online-learning protocol)

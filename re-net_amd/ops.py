@@ -1019,6 +1019,69 @@ class LinearFn(Function):
         return (K.gemm(g, weight), K.gemm(g, x, ta=True), K.colsum(g))
 
 
+class SparseTargets(object):
+    """Soft target distributions of B rows in CSR form on the device (renet_soft_ce_sparse): `ptr` [B + 1] and `col` [nnz]
+    (int32; per row distinct and ascending, in [0, num_cols)), `w` [nnz] (fp32, >= 0; a row need not sum to 1).  Built from
+    host arrays, validated there, and uploaded in ONE copy."""
+
+    def __init__(self, ptr, col, w, num_cols, device):
+        ptr = np.ascontiguousarray(ptr, dtype=np.int64).reshape(-1)
+        col = np.ascontiguousarray(col, dtype=np.int64).reshape(-1)
+        w = np.ascontiguousarray(w, dtype=np.float32).reshape(-1)
+        if len(ptr) < 1 or ptr[0] != 0 or ptr[-1] != len(col) or len(w) != len(col) or np.any(np.diff(ptr) < 0) or \
+                len(col) >= 2 ** 31:
+            raise ValueError('sparse targets: ptr / col / w do not describe a CSR matrix')
+        if len(col):
+            inner = np.ones(len(col), dtype=bool)
+            inner[ptr[:-1][np.diff(ptr) > 0]] = False                  # (the first entry of every non-empty row)
+            if col.min() < 0 or col.max() >= int(num_cols) or np.any(np.diff(col)[inner[1:]] <= 0):
+                raise ValueError('sparse targets: the columns of a row must be distinct, ascending and inside the row')
+            if not (w >= 0).all():
+                raise ValueError('sparse targets: weights must be >= 0')
+        self.rows, self.num_cols, self.nnz = len(ptr) - 1, int(num_cols), len(col)
+        flat = np.concatenate((ptr.astype(np.int32), col.astype(np.int32), w.view(np.int32)))
+        up = torch.from_numpy(flat).to(device, non_blocking=True)
+        self.ptr, self.col = up[:len(ptr)], up[len(ptr):len(ptr) + len(col)]
+        self.w = up[len(ptr) + len(col):].view(torch.float32)
+
+    def rows_slice(self, a, b):
+        """The targets of rows [a, b) as a VIEW of the same device arrays (ptr keeps its offsets into col / w)."""
+        t = SparseTargets.__new__(SparseTargets)
+        t.rows, t.num_cols, t.nnz = int(b) - int(a), self.num_cols, self.nnz
+        t.ptr, t.col, t.w = self.ptr[a:b + 1], self.col, self.w
+        return t
+
+
+class SoftCESparseFn(Function):
+    """scale * sum_b ( W_b logsumexp(logits[b]) - sum_k w_k logits[b, col_k] ): utils.soft_cross_entropy (global_model.py:53)
+    for sparse soft targets with scale = 1 / B, on the fused kernel (csrc/soft_ce.hip).  The logits are OVERWRITTEN with their
+    gradient scale * (W softmax - w) when one is needed -- hand in the result of LinearFn, whose backward takes it from there
+    (it keeps no copy of its output) -- unless inplace=False, which works on a copy."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, scale, inplace=True):
+        if logits.dim() != 2 or logits.shape[0] != targets.rows or logits.shape[1] != targets.num_cols:
+            raise ValueError('SoftCESparseFn: logits %s against targets [%d, %d]' % (tuple(logits.shape), targets.rows,
+                                                                                   targets.num_cols))
+        need_grad = ctx.needs_input_grad[0]
+        buf = logits.detach()
+        if not buf.is_contiguous():
+            buf = buf.contiguous()                                     # (a copy of its own already)
+        elif need_grad and not inplace:
+            buf = buf.clone()
+        row_loss = K.soft_ce_sparse(buf, targets.ptr, targets.col, targets.w, float(scale), need_grad)
+        if need_grad:
+            ctx.dlogits, ctx.consumed = buf, False
+        return row_loss.sum() * float(scale)
+
+    @staticmethod
+    def backward(ctx, g):
+        _consume_ce_gradient(ctx)
+        dl, ctx.dlogits = ctx.dlogits, None
+        K.scale_by_device_scalar(dl, _c(g.reshape(1)))                 # (the upstream scalar, from device memory: no sync)
+        return dl, None, None, None
+
+
 def host_offsets(step_off):
     """int array -> ctypes int32 array kept alive by the caller (the GRU entry points read it on the host)."""
     arr = np.ascontiguousarray(step_off, dtype=np.int32)

@@ -307,7 +307,7 @@ class ObservedStream(object):
         last one predict(last + time unit) (get_global_emb's own rule), and a row of an earlier timestamp reads no appended
         graph.  Needs an earlier resident() (ValueError); the old stream and its store stay valid.  Equal to
         extended(quads).resident(model, global_model) bit for bit, PROVIDED the global model's weights have not changed since
-        the rows of the earlier timestamps were computed -- after a weight update call resident() instead."""
+        the rows of the earlier timestamps were computed -- after a weight update call refresh_global() (or resident()) first."""
         import torch
         if self.device is None:
             raise ValueError('observe() appends to a resident stream: call resident() first')
@@ -324,6 +324,16 @@ class ObservedStream(object):
                         rows[t] = global_model.predict(nxt, new.graph_dict)[0].detach()
         new.device = self.device.appended(quads, rows, _obs=new)
         return new
+
+    def refresh_global(self, global_model):
+        """After an update of the global model's weights: a NEW stream whose resident store shares every table of this one's
+        (quadruples, history indices, graph store, filter index) but carries a new `glob`, recomputed batched on the device
+        (online.global_table_batched: the RGCN layers once per timestamp instead of once per window position, one packed
+        encoder launch per <= 1024 windows instead of one predict() per timestamp).  Keys and rows are those of
+        global_table(global_model) -- rows to GEMM rounding, the batched GEMMs see other M -- so the result stands for
+        resident() without the host rebuild and the upload.  Needs an earlier resident(); this stream and its store stay valid."""
+        import online
+        return online.refresh_global(self, global_model)
 
     def global_table(self, global_model):
         """{t: embedding} over ALL timestamps of the stream, from the global model as it stands and this stream's own

@@ -146,6 +146,8 @@ _SIGNATURES = {
     'renet_dropout': (c_int, [c_void_p, c_size_t, c_float, c_u64, c_void_p, c_void_p]),
     'renet_softmax_ce': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p,
                                  c_void_p]),
+    'renet_soft_ce_sparse': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_float, c_void_p,
+                                     c_void_p, c_void_p]),
     'renet_joint_softmax': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     'renet_rank_rows': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                 c_void_p, c_void_p]),
@@ -340,7 +342,7 @@ def _timed_end(t0, name, flops=0.0, nbytes=0.0, tag=None):
 GLUE = ('softmax_ce_planes', 'gather_rows', 'segment_add', 'segment_add2', 'compose_table_items', 'rgcn_bwd_prep', 'colsum',
         'scale_by_device_scalar', 'seq_assemble_fwd', 'seq_assemble_fwd_bf16', 'softmax_ce_bf16', 'seq_assemble_bwd',
         'concat3_fwd', 'concat3_bwd', 'dropout', 'softmax_ce', 'adam_step', 'segment_pool_fwd', 'segment_pool_bwd',
-        'pack_bf16_glue')
+        'pack_bf16_glue', 'soft_ce_sparse')
 _glue_saved = {}
 
 
@@ -1455,6 +1457,24 @@ def softmax_ce(logits, target, grad_scale, want_grad, row_loss=None):
     _check(lib().renet_softmax_ce(logits.data_ptr(), _i32(target), b, c, _ld(logits), float(grad_scale),
                                   _f32(row_loss), logits.data_ptr() if want_grad else None, _stream()),
            'softmax_ce')
+    return row_loss
+
+
+def soft_ce_sparse(logits, tgt_ptr, tgt_col, tgt_w, grad_scale, want_grad, row_loss=None):
+    """renet_soft_ce_sparse on logits [B, C] (fp32, unit inner stride) with the CSR soft targets tgt_ptr [B + 1] (int32),
+    tgt_col [nnz] (int32; per row distinct, ascending) and tgt_w [nnz] (fp32, >= 0; a row need not sum to 1): returns
+    row_loss[B] = W logsumexp(row) - sum_k w_k row[col_k] (written into `row_loss` when given); if want_grad, logits is
+    OVERWRITTEN with grad_scale * (W softmax(row) - w)."""
+    if not (logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2):
+        raise RenetHipError('soft_ce_sparse needs a 2-D float32 device tensor')
+    b, c = logits.shape
+    if tgt_ptr.numel() != b + 1 or tgt_col.numel() != tgt_w.numel():
+        raise RenetHipError('soft_ce_sparse: shape mismatch')
+    if row_loss is None:
+        row_loss = torch.empty(b, device=logits.device, dtype=torch.float32)
+    _check(lib().renet_soft_ce_sparse(logits.data_ptr(), b, c, _ld(logits), _i32(tgt_ptr), _i32(tgt_col), _f32(tgt_w),
+                                      float(grad_scale), _f32(row_loss), logits.data_ptr() if want_grad else None,
+                                      _stream()), 'soft_ce_sparse')
     return row_loss
 
 

@@ -8,6 +8,7 @@ protocol under which RE-GCN, xERTE and TITer report the time-aware filter.  NOT 
                                       [--model-dir models/<DS>] [--maxpool 1] [--max-batch 4096] [--gpu 0]
                                       [--horizon H] [--queries FILE [--k K]] [--observe-loop]
                                       [--rollout H [--num-k K]]
+                                      [--online [STEPS] [--replay N] [--online-global] [--lr LR]]
 
 --horizon H evaluates with STALE histories (RENet.evaluate_forecast with ObservedStream.horizon_as_of): the split's timestamps
 are cut into blocks of H, and every query forecasts from the facts before the first timestamp of its block; nothing is
@@ -29,6 +30,13 @@ facts before it, every later one from those plus the facts the model GENERATED f
 numbers are neither those of --horizon H (nothing generated) nor the reference's multi-step numbers (test.py: per-entity
 caches, no observed truth at all): three protocols, three sets of numbers.  Exclusive with --horizon, --observe-loop,
 --queries and --events.
+
+--online [STEPS] evaluates with ONLINE LEARNING (RENet.evaluate_online): the forecast / observe loop of --observe-loop, and
+after every observed timestamp STEPS training steps (default 1; parallel.HipAdam, --lr) on that timestamp's facts plus those
+of the --replay timestamps before it; with --online-global the global model takes a step on the timestamp as well and the
+resident global table is recomputed (ObservedStream.refresh_global).  The weights that rank timestamp t have seen every
+evaluated timestamp before t: a FOURTH protocol, whose numbers must not be mixed with the static observed ones, --horizon,
+--rollout or the reference's multi-step numbers.  The checkpoints are not written back.
 
 --events adds the EVENT forecasts (RENet.evaluate_events_observed): MRR / Hits of the gold (relation, entity) pair among all
 pairs of the given entity, and of the gold relation given both endpoints, in the three settings; with K also the K most
@@ -133,6 +141,53 @@ def rollout_loop(args, model, global_model, splits, num_ent, num_rels, data_dir)
                       'n': int(len(evaluated)), 'metrics': {name: U.rank_metrics(ranks[name]) for name in SETTINGS}}))
 
 
+def online_loop(args, model, global_model, splits, num_ent, num_rels, data_dir):
+    """--online [STEPS]: RENet.evaluate_online over the split, from the facts before it."""
+    import numpy as np
+    import torch
+    import parallel
+    import utils as U
+    from model import SETTINGS
+    from preprocess import ObservedStream
+    present = [q for q in splits if q is not None]
+    known = np.concatenate(present)                                    # what the filtered settings filter by, as the plain pass
+    k = [n for n, q in zip(('train', 'valid', 'test'), splits) if q is not None].index(args.split)
+    evaluated = present[k]
+    start = present[:k] + [np.zeros((0, 4), dtype=np.int64)]
+    if len(start) < 2:
+        raise SystemExit('nothing lies before the %s split' % args.split)
+    t0 = time.perf_counter()
+    obs = ObservedStream(start, num_ent, num_rels, args.seq_len)
+    obs.resident(model, global_model)
+    opt = parallel.HipAdam(model, lr=args.lr, weight_decay=1e-5, max_norm=1.0)
+    gopt = parallel.HipAdam(global_model, lr=args.lr, weight_decay=1e-5, max_norm=1.0) if args.online_global else None
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    ranks, loss, log = model.evaluate_online(obs, evaluated, global_model, opt, steps=args.online, replay=args.replay,
+                                             global_optimizer=gopt, all_triplets=known, max_batch=args.max_batch)
+    torch.cuda.synchronize()
+    t2 = time.perf_counter()
+    n_t = len(log)
+    print('observed-history protocol, ONLINE learning (%d step(s) per timestamp, replay %d, global model %s, lr %g), %s split of '
+          '%s: %d quadruples at %d timestamps; setup %.2f s, pass %.2f s (%.1f ms per timestamp)'
+          % (args.online, args.replay, 'learning' if gopt is not None else 'fixed', args.lr, args.split, data_dir, len(evaluated),
+             n_t, t1 - t0, t2 - t1, 1e3 * (t2 - t1) / max(n_t, 1)))
+    print('the weights that rank timestamp t have been trained on every evaluated timestamp before t: these numbers are not '
+          'those of the static observed, stale-horizon, rollout or multi-step protocols')
+    step_losses = [x for e in log for x in e['losses']]
+    if step_losses:
+        print('mean learn-step loss %.6f (first timestamp %.6f, last %.6f)'
+              % (float(np.mean(step_losses)), float(np.mean(log[0]['losses'])), float(np.mean(log[-1]['losses']))))
+    print('mean loss %.6f' % float(np.mean(loss)))
+    for name in SETTINGS:
+        m = U.rank_metrics(ranks[name])
+        print('%-14s MRR %.6f  MR %.3f  Hits@1 %.6f  Hits@3 %.6f  Hits@10 %.6f'
+              % (name, m['mrr'], m['mr'], m['hits@1'], m['hits@3'], m['hits@10']))
+    print(json.dumps({'protocol': 'observed', 'loop': 'online', 'steps': args.online, 'replay': args.replay,
+                      'global_model_learns': gopt is not None, 'lr': args.lr, 'split': args.split, 'n': int(len(evaluated)),
+                      'metrics': {name: U.rank_metrics(ranks[name]) for name in SETTINGS}}))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('data_dir')
@@ -155,7 +210,19 @@ def main():
     ap.add_argument('--rollout', type=int, default=None, metavar='H',
                     help='rollout horizon: observe the truth every H timestamps, feed generated facts to the steps in between')
     ap.add_argument('--num-k', type=int, default=1000, help='continuations kept per direction and generated timestamp (--rollout)')
+    ap.add_argument('--online', type=int, nargs='?', const=1, default=None, metavar='STEPS',
+                    help='online learning: after every observed timestamp, STEPS training steps on its facts (default 1)')
+    ap.add_argument('--replay', type=int, default=0, help='earlier timestamps whose facts join every learn step (--online)')
+    ap.add_argument('--online-global', action='store_true',
+                    help='the global model learns too: one step per timestamp, then the resident table is refreshed (--online)')
+    ap.add_argument('--lr', type=float, default=1e-3, help='learning rate of the online steps (--online)')
     args = ap.parse_args()
+    if args.online is not None:
+        if args.online < 0 or args.replay < 0:
+            raise SystemExit('--online and --replay must be >= 0')
+        if args.horizon is not None or args.observe_loop or args.queries is not None or args.events is not None or \
+                args.rollout is not None or args.topk:
+            raise SystemExit('--online is exclusive with --horizon, --observe-loop, --rollout, --queries, --events and --topk')
     if args.horizon is not None and args.horizon < 1:
         raise SystemExit('--horizon must be >= 1')
     if args.rollout is not None:
@@ -201,6 +268,8 @@ def main():
         return observe_loop(args, model, global_model, splits, num_ent, num_rels, data_dir)
     if args.rollout is not None:
         return rollout_loop(args, model, global_model, splits, num_ent, num_rels, data_dir)
+    if args.online is not None:
+        return online_loop(args, model, global_model, splits, num_ent, num_rels, data_dir)
 
     t0 = time.perf_counter()
     obs = ObservedStream(splits, num_ent, num_rels, args.seq_len)
