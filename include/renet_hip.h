@@ -857,6 +857,48 @@ int renet_store_append(const int32_t* ent_ptr, const int32_t* snap_t, const int3
 int renet_append_i32(const int32_t* old, int n_old, const int32_t* add, int n_add, int32_t* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * RECURRENCE PRIOR on the resident stream (csrc/recurrence.hip): "what did (entity, relation) connect to before, how often,
+ * how recently", as a non-learned baseline and as a copy term mixed into the model's scores.
+ *
+ * PAIR TABLES of one role (device int32 [n_facts] each): p_rel, p_other (the partner: o for role 0, s for role 1) and p_t
+ * over ALL facts, sorted by (entity, relation, partner, time).  The facts of entity e are the index range
+ * [snap_ptr[ent_ptr[e]], snap_ptr[ent_ptr[e + 1]]) of that role's history index (RenetStoreDev / renet_store_append): the
+ * same range as there, another order inside it.  Duplicate facts stay.  Host statement: preprocess.PairIndex.
+ *
+ * renet_pair_append: the tables after m new facts were appended, WITHOUT a sort of the old ones (host statement:
+ * preprocess.PairIndex.appended, array for array; the result equals the tables of the longer stream bit for bit).  Inputs:
+ * the old tables [n]; ent_ptr / snap_ptr of the old index and ent_ptr_new / snap_ptr_new of the longer one (outputs of
+ * renet_store_append) with their snapshot counts; the new facts new_ent / new_rel / new_other / new_t [m], sorted by
+ * (entity, relation, partner, time).  Outputs: the caller's fresh p_rel_out / p_other_out / p_t_out [n + m].  One thread per
+ * old and per new fact, a binary search each inside one entity's range; no atomics, no read-back, no workspace; the old
+ * tables are only read.  Negative sizes or a missing array: RENET_ERR_BADARG; n + m beyond int32: RENET_ERR_UNSUPPORTED.
+ *
+ * renet_recurrence_mix_rows: ONE direction per launch.  Row i is the query (ent[i], rel[i], t[i]) with histories as of
+ * as_of[i] <= t[i] (device int32 [n]); logits [n, C] with row stride ld (NULL: uniform rows; never written, and not
+ * overlapping out); out [n, C] contiguous.  With the sums over the facts (ent, rel, o, t') of the tables with t' < as_of:
+ *     w[o]   = sum of 2^(-(t - t') * inv_half_life)          (inv_half_life = 0: plain counts)
+ *     W      = sum over o of w[o]
+ *     a_i    = alpha if W > 0 else 0      (no history of (ent, rel), or an entity outside [0, num_ent): the prior abstains)
+ *     out[o] = log((1 - a_i) * softmax(logits_i)[o] + a_i * w[o] / W)
+ * every sum and the logsumexp in fp64, one rounding to fp32 per output, in an order fixed by the table's content: the same
+ * bits from run to run, no floating-point atomics.  0 <= alpha < 1, so every output is finite, and a row of out is a
+ * normalised log-probability row: renet_rank_rows3 and renet_topk_rows(_wide) read it as they read logits, their row_loss /
+ * logp being -log p_mix[gold] / log p_mix.  alpha = 0 gives log_softmax(logits).  A partner outside [0, C) is not addressed.
+ * stats / stats_w (both or neither): int32 [n, 2] = (distinct partners seen before as_of, facts counted) and fp32 W [n].
+ * C in [1, RENET_RECURRENCE_MAX_C]; alpha outside [0, 1), a negative or non-finite inv_half_life, n < 0, ld < C or a missing
+ * array: RENET_ERR_BADARG before any launch; n == 0 is a no-op.  One workgroup per row; no workspace. */
+#define RENET_RECURRENCE_MAX_C (1 << 20)
+int renet_pair_append(const int32_t* p_rel, const int32_t* p_other, const int32_t* p_t, int n, const int32_t* ent_ptr,
+                      const int32_t* snap_ptr, int n_snaps, const int32_t* ent_ptr_new, const int32_t* snap_ptr_new,
+                      int n_snaps_new, int num_ent, const int32_t* new_ent, const int32_t* new_rel, const int32_t* new_other,
+                      const int32_t* new_t, int m, int32_t* p_rel_out, int32_t* p_other_out, int32_t* p_t_out, void* stream);
+int renet_recurrence_mix_rows(const int32_t* ent, const int32_t* rel, const int32_t* t, const int32_t* as_of, int n,
+                              const int32_t* p_rel, const int32_t* p_other, const int32_t* p_t, int n_facts,
+                              const int32_t* ent_ptr, const int32_t* snap_ptr, int n_snaps, int num_ent, const float* logits,
+                              int ld, int C, float alpha, float inv_half_life, float* out, int32_t* stats, float* stats_w,
+                              void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * DEVICE builder for the FULL-GRAPH batches of the global model (graph.build_full_graphs; reference Aggregator.py:44-55 /
  * 87-98: dgl.batch of the whole graphs of a list of timestamps).  Resident: the per-timestamp node lists and the facts with
  * LOCAL endpoints (graph.TimeGraph.ent / ls / r / lo, concatenated in graph_dict order).  tidx_dev[G] (device int32,

@@ -186,6 +186,24 @@ class ObservedStore(DeviceStore):
         ts = sorted(int(t) for t in global_emb.keys())
         self._glob_times = np.asarray(ts, dtype=np.int64)               # (host copy of t['glob_times']: appended() cuts by it)
         self.glob = torch.stack([torch.as_tensor(global_emb[t]).detach().reshape(h_dim).float() for t in ts]).to(device)
+        self._pair = {}                                                 # pair_tables(), once asked for
+
+    def pair_tables(self):
+        """The resident PAIR TABLES of the recurrence prior: per role (0: subject runs, 1: object runs) the int32 device
+        tensors (p_rel, p_other, p_t) of preprocess.PairIndex over this store's facts -- the same fact runs as the history
+        index of the role (snap_ptr[ent_ptr]), sorted inside a run by (relation, partner, time).  Built on first use from the
+        host quadruples, uploaded once and cached; a store that appended() makes from one that has them gets them from
+        renet_pair_append instead.  The holder is shared by the stores that share this store's tables (refresh_global's
+        copy, QueryStore)."""
+        if 'tables' not in self._pair:
+            import preprocess
+            _check_int32('relations', self.quads[:, 1])
+            tabs = []
+            for role in (0, 1):
+                pi = preprocess.PairIndex(self.quads, role, self.num_ent)
+                tabs.append(tuple(_i32(a, self.device) for a in (pi.p_rel, pi.p_other, pi.p_t)))
+            self._pair['tables'] = tuple(tabs)
+        return self._pair['tables']
 
     def queries(self, quads, as_of=None, stream=None):
         """The QueryStore of the queries `quads` [n, 4] = (s, r, o, t) on top of this store: histories as of `as_of` (None:
@@ -257,6 +275,18 @@ class ObservedStore(DeviceStore):
             out, tot = K.store_append([ot[f] for f in names], q_ent, self.num_ent, self.history_len, role[r], caps[r])
             t.update(zip(names, out))
             totals.append(tot)
+        new._pair = {}
+        if 'tables' in self._pair:
+            # the pair tables ride along: the new facts sorted per role by (entity, relation, partner, time), one more
+            # upload, one renet_pair_append per role over the run pointers just made.  A store that never asked for a prior
+            # has no tables and runs none of this.
+            _check_int32('relations', quads[:, 1])
+            keys = [np.stack((quads[:, c], quads[:, 1], quads[:, oc], quads[:, 3])) for c, oc in ((0, 2), (2, 0))]
+            keys = [k[:, np.lexsort(k[::-1])] for k in keys]
+            pk = torch.from_numpy(np.ascontiguousarray(np.stack(keys), dtype=np.int32)).to(dev, non_blocking=True)
+            new._pair['tables'] = tuple(
+                K.pair_append(self._pair['tables'][r], ot['ent_ptr%d' % r], ot['snap_ptr%d' % r], t['ent_ptr%d' % r],
+                              t['snap_ptr%d' % r], self.num_ent, pk[r]) for r in (0, 1))
         t['q_s'], t['q_r'], t['q_o'] = K.append_i32(ot['q_s'], n_s), K.append_i32(ot['q_r'], n_r), K.append_i32(ot['q_o'], n_o)
         t['trip_s'], t['trip_r'], t['trip_o'] = (K.append_i32(ot['trip_s'], n_s), K.append_i32(ot['trip_r'], n_r),
                                                  K.append_i32(ot['trip_o'], n_o))
@@ -446,6 +476,10 @@ class QueryStore(ListBatchStore):
         if self._host is None:
             self._host = self._quads_dev.cpu().numpy().astype(np.int64)
         return self._host
+
+    def pair_tables(self):
+        """The base store's pair tables (ObservedStore.pair_tables): the queries add no facts."""
+        return self.base.pair_tables()
 
     def sides_present(self):
         """(any subject present, any object present): a side that no query has needs no rows at all."""

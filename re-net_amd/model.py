@@ -1436,13 +1436,23 @@ def _observed_scores(self, obs, idx):
         return _linear_eval(self.linear, feat_sub), _linear_eval(self.linear, feat_ob)
 
 
+def _prior_rows(prior, store, idx):
+    """The recurrence.QueryRows of the rows idx of `store` for the `prior=` keyword of the observed family; None without a
+    prior (nothing is imported, built or launched then)."""
+    if prior is None:
+        return None
+    import recurrence
+    recurrence._checked(prior)
+    return recurrence.QueryRows(store, idx)
+
+
 def _ranks_of(counts):
     """counts int [2 k, ...] = (greater, equal) per setting -> k float64 rank arrays (ties averaged, model.py:368-376)."""
     c = counts.cpu().numpy().astype(np.float64)
     return [c[2 * k] + (c[2 * k + 1] - 1.0) / 2 + 1 for k in range(len(c) // 2)]
 
 
-def _evaluate_observed(self, obs, idx, all_triplets=None, max_batch=4096, relation=False):
+def _evaluate_observed(self, obs, idx, all_triplets=None, max_batch=4096, relation=False, prior=None):
     """Raw, filtered and time-aware filtered ranks of the stream positions idx under OBSERVED histories (extension of the
     reference API): ({'raw': r, 'filtered': r, 'time_filtered': r}, loss[len]), every r float64 [len, 2] = (rank_sub,
     rank_ob) as utils.rank_metrics takes it, loss the sum of the two directions' entity cross-entropies per row.  idx may
@@ -1456,10 +1466,13 @@ def _evaluate_observed(self, obs, idx, all_triplets=None, max_batch=4096, relati
     batch, as evaluate_all_batch.  A pass is repeatable in place and leaves the multi-step state untouched.
     relation=True: a third result {'rank': [len, 2], 'loss': [len, 2], 'entity_loss': [len, 2]} -- raw rank and row loss
     of the gold relation under linear_r (model.py:98-100; the head trained at weight 0.1), column 0 from the subject=False
-    pass ([ent[o] | o_q]), column 1 from subject=True ([ent[s] | s_q]), and the entity loss split the same way."""
+    pass ([ent[o] | o_q]), column 1 from subject=True ([ent[s] | s_q]), and the entity loss split the same way.
+    prior: a recurrence.RecurrencePrior (None: today's path, launch for launch) -- every entity score matrix goes through
+    one renet_recurrence_mix_rows launch before it is ranked; ranks and loss are then those of the mixed distribution."""
     store = _observed_store(obs)
     idx = _observed_positions(store, idx)
     dev, n = self.ent_embeds.device, len(idx)
+    mix_rows = _prior_rows(prior, store, idx)
     max_batch = max(1, int(max_batch))
     tr = store.quads[idx]
     s, r, o, t = tr[:, 0], tr[:, 1], tr[:, 2], tr[:, 3]
@@ -1476,6 +1489,8 @@ def _evaluate_observed(self, obs, idx, all_triplets=None, max_batch=4096, relati
         for c, d, (feat_ob, feat_sub, featr_ob, featr_sub) in _observed_cuts(_observed_chunks(self, store, idx, relation), max_batch):
             for col, side, feat, featr, lab, base in ((0, 's', feat_sub, featr_sub, up[8], 0), (1, 'o', feat_ob, featr_ob, up[9], 4)):
                 pred = _linear_eval(self.linear, feat)
+                if mix_rows is not None:
+                    pred = mix_rows.mix(prior, 'sub' if side == 's' else 'ob', pred, c, d)
                 cnt, ls = K.rank_rows3(pred, lab[c:d], cols[side][0], up[base][c:d], up[base + 1][c:d],
                                        cols[side][1], up[base + 2][c:d], up[base + 3][c:d], want_loss=True)
                 counts[:, c:d, col] = cnt
@@ -1810,26 +1825,35 @@ def _forecast_rows(self, qs):
     return feat_ob, feat_sub
 
 
-def _forecast_scores(self, obs, queries, as_of=None):
+def _forecast_scores(self, obs, queries, as_of=None, prior=None):
     """observed_scores for arbitrary queries: (sub_pred [n, N_ent], ob_pred [n, N_ent]), ob_pred[i] the logits of the
     objects of (s_i, r_i, ?, t_i) from the history of s_i before as_of, sub_pred[i] those of the subjects of (?, r_i, o_i,
     t_i).  For queries that are stream facts, forecast_scores(obs, obs.allq[idx]) is observed_scores(obs, idx) bit for bit.
     An absent side has an empty sequence, and the rows that would need it as the GIVEN entity are not computed: sub_pred is
     None when no query has an object (ob_pred: a subject); when only some lack it, their rows of that matrix are undefined.
-    A batch whose histories are all empty takes the zero-state rows of _observed_features without an encoder launch."""
+    A batch whose histories are all empty takes the zero-state rows of _observed_features without an encoder launch.
+    prior: a recurrence.RecurrencePrior -- the matrices are then the mixed log-probabilities (recurrence.py), the prior cut
+    at the same as_of as the histories."""
     qs = _query_store(obs, queries, as_of)
     has_s, has_o = qs.sides_present()
+    mix_rows = _prior_rows(prior, qs, np.arange(qs.n_quads))
     with torch.no_grad():
         feat_ob, feat_sub = _forecast_rows(self, qs)
-        return (_linear_eval(self.linear, feat_sub) if has_o else None, _linear_eval(self.linear, feat_ob) if has_s else None)
+        sub_pred = _linear_eval(self.linear, feat_sub) if has_o else None
+        ob_pred = _linear_eval(self.linear, feat_ob) if has_s else None
+        if mix_rows is not None:
+            sub_pred = None if sub_pred is None else mix_rows.mix(prior, 'sub', sub_pred)
+            ob_pred = None if ob_pred is None else mix_rows.mix(prior, 'ob', ob_pred)
+        return sub_pred, ob_pred
 
 
-def _forecast_topk(self, obs, queries, k=10, all_triplets=None, setting='raw', as_of=None, sides=('sub', 'ob')):
+def _forecast_topk(self, obs, queries, k=10, all_triplets=None, setting='raw', as_of=None, sides=('sub', 'ob'), prior=None):
     """predict_topk_observed for arbitrary queries, without gold: {side: (idx, score, logp, n_valid)} as device tensors for
     the sides asked for ('ob': the objects of (s, r, ?, t), 'sub': the subjects of (?, r, o, t)); a side left out costs no
     score GEMM.  setting / all_triplets as there (None: the base stream's facts, never the queries); the filter keys are the
     queries' own (s, r[, t]) / (o, r[, t]) -- a timestamp the facts do not hold gives empty time-aware lists.  With
-    setting='raw' and queries that are a device tensor no query content is read back to the host."""
+    setting='raw' and queries that are a device tensor no query content is read back to the host.
+    prior: a recurrence.RecurrencePrior -- the k best of the mixed distribution, score = logp = its log-probability."""
     if setting not in SETTINGS:
         raise ValueError('setting must be one of %s, not %r' % (', '.join(SETTINGS), setting))
     sides = tuple(sides)
@@ -1843,6 +1867,9 @@ def _forecast_topk(self, obs, queries, k=10, all_triplets=None, setting='raw', a
         dev = feat_ob.device
         # the score GEMMs are enqueued first: the host lookups of the filtered settings run while the device computes them
         preds = {name: _linear_eval(self.linear, feat) for name, feat in (('sub', feat_sub), ('ob', feat_ob)) if name in sides}
+        if prior is not None:
+            mix_rows = _prior_rows(prior, qs, np.arange(qs.n_quads))
+            preds = {name: mix_rows.mix(prior, name, pred) for name, pred in preds.items()}
         for name, side, key_col in (('sub', 's', 2), ('ob', 'o', 0)):
             if name not in sides:
                 continue
@@ -1855,17 +1882,18 @@ def _forecast_topk(self, obs, queries, k=10, all_triplets=None, setting='raw', a
     return out
 
 
-def _evaluate_forecast(self, obs, queries, as_of=None, all_triplets=None, max_batch=4096, relation=False):
+def _evaluate_forecast(self, obs, queries, as_of=None, all_triplets=None, max_batch=4096, relation=False, prior=None):
     """evaluate_observed for LABELLED queries (both sides present; the gold entities are the query's own s and o), with
     histories as of `as_of`: the same results in the same layout.  evaluate_forecast(obs, obs.allq[idx]) equals
     evaluate_observed(obs, idx) exactly; with as_of = obs.horizon_as_of(idx, h) it is the horizon-h stale-history evaluation
-    (its numbers are not those of h = 1).  all_triplets None: the base stream's facts."""
+    (its numbers are not those of h = 1).  all_triplets None: the base stream's facts.  prior: as in evaluate_observed; its
+    as_of is the one that cuts the histories -- a stale-history query gets a stale prior."""
     qs = _query_store(obs, queries, as_of)
     ents = qs.quads[:, [0, 2]]
     if ents.min() < 0 or ents.max() >= qs.num_ent:
         raise ValueError('evaluate_forecast takes labelled queries: both subject and object present')
     return _evaluate_observed(self, qs, np.arange(qs.n_quads), all_triplets if all_triplets is not None else qs.facts,
-                              max_batch, relation)
+                              max_batch, relation, prior)
 
 
 def _forecast_events(self, obs, ents, t, k=10, direction='ob', all_triplets=None, setting='raw', as_of=None):

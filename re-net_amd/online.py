@@ -227,7 +227,7 @@ def refresh_global(stream, global_model):
 
 # ---- RENet.evaluate_online ---------------------------------------------------------------------------------------------
 def _evaluate_online(self, obs, quads, global_model, optimizer, steps=1, replay=0, global_optimizer=None, all_triplets=None,
-                     max_batch=4096, batch_size=1024, grad_norm=1.0):
+                     max_batch=4096, batch_size=1024, grad_norm=1.0, prior=None):
     """The forecast / observe / LEARN loop over the labelled, time-sorted quads on the resident stream obs (ending before
     quads[0, 3]).  Per timestamp t of quads, in this order: (1) its facts are ranked with evaluate_forecast on the stream as
     it stands -- nothing of t has been seen, by the stream or by the weights; (2) they are observed (ObservedStream.observe);
@@ -238,7 +238,9 @@ def _evaluate_online(self, obs, quads, global_model, optimizer, steps=1, replay=
     {'t', 'losses', 'global_loss'} per timestamp.  self.last_online is the stream after the last timestamp (len(obs) +
     len(quads) facts).  With steps = 0 and no global_optimizer the ranks are those of evaluate_rollout(obs, quads, 1, ...) bit
     for bit.  all_triplets: as there.  These are ONLINE numbers -- a protocol of their own, not comparable with the static
-    single-step, stale-horizon, rollout or multi-step ones."""
+    single-step, stale-horizon, rollout or multi-step ones.
+    prior: a recurrence.RecurrencePrior for the forecast half (evaluate_forecast's keyword); the pair tables it reads are
+    built at the first timestamp and ride through observe() by the device append.  Learning is not touched by it."""
     store = M._observed_store(obs)
     cur = getattr(store, 'obs', None)
     if cur is None or not hasattr(cur, 'observe'):
@@ -260,7 +262,7 @@ def _evaluate_online(self, obs, quads, global_model, optimizer, steps=1, replay=
     try:
         for j, t in enumerate(times):
             q = quads[first[j]:ends[j]]
-            r, l = M._evaluate_forecast(self, cur, q, all_triplets=known, max_batch=max_batch)
+            r, l = M._evaluate_forecast(self, cur, q, all_triplets=known, max_batch=max_batch, prior=prior)
             for name, v in r.items():
                 ranks.setdefault(name, []).append(v)
             loss.append(l)

@@ -181,6 +181,135 @@ class HistoryIndex(object):
         return hist, hist_t
 
 
+def _role_index(role):
+    """0 / 's': the entity is the subject, the partner the object; 1 / 'o': the other way round."""
+    if role in (0, 's'):
+        return 0
+    if role in (1, 'o'):
+        return 1
+    raise ValueError("role must be 0 / 's' or 1 / 'o'")
+
+
+class PairIndex(object):
+    """The RELATION-KEYED view of one role's facts, for the recurrence prior ("what did (entity, relation) connect to
+    before, how often, how recently"): p_rel, p_other (the partner: o for role 0 / 's', s for role 1 / 'o') and p_t over
+    ALL facts, sorted by (entity, relation, partner, time).  The fact run of entity e is [run_ptr[e], run_ptr[e + 1]) --
+    the same index range as in the HistoryIndex of that role, run_ptr = snap_ptr[ent_ptr]; the resident copy keeps no
+    pointer array of its own.  Duplicate quadruples stay and count as facts.  Equal keys are indistinguishable in the three
+    arrays, so the tables are a function of the MULTISET of facts: no file-order tie rule exists.  The host statement of
+    the resident pair tables (gpu_builder.ObservedStore.pair_tables), of renet_pair_append (appended) and, with
+    tests/recurrence_statement.py, of renet_recurrence_mix_rows (prior_rows)."""
+
+    def __init__(self, quads, role, num_ent):
+        q = np.asarray(quads, dtype=np.int64).reshape(-1, 4)
+        self.role, self.num_ent = _role_index(role), int(num_ent)
+        ent, other = (q[:, 0], q[:, 2]) if self.role == 0 else (q[:, 2], q[:, 0])
+        if len(q) and (int(ent.min()) < 0 or int(ent.max()) >= self.num_ent):
+            raise ValueError('entity id outside [0, num_ent)')
+        order = np.lexsort((q[:, 3], other, q[:, 1], ent))
+        self.p_rel, self.p_other, self.p_t = q[order, 1], other[order], q[order, 3]
+        self.run_ptr = np.searchsorted(ent[order], np.arange(self.num_ent + 1)).astype(np.int64)
+
+    def __len__(self):
+        return len(self.p_rel)
+
+    def _keys_of(self, q):
+        ent, other = (q[:, 0], q[:, 2]) if self.role == 0 else (q[:, 2], q[:, 0])
+        return ent, q[:, 1], other, q[:, 3]
+
+    def sorted_new(self, new_quads):
+        """int64 [4, m] = (entity, relation, partner, time) of new_quads sorted by that key: what renet_pair_append takes."""
+        q = np.asarray(new_quads, dtype=np.int64).reshape(-1, 4)
+        ent, rel, other, t = self._keys_of(q)
+        if len(q) and (int(ent.min()) < 0 or int(ent.max()) >= self.num_ent):
+            raise ValueError('entity id outside [0, num_ent)')
+        order = np.lexsort((t, other, rel, ent))
+        return np.stack((ent[order], rel[order], other[order], t[order]))
+
+    def appended(self, new_quads):
+        """The tables of the stream with new_quads [m, 4] appended, WITHOUT a sort of the old facts: the host statement of
+        renet_pair_append (csrc/recurrence.hip), rank by rank.  With the new facts of entity e sorted by key:
+          old fact j of e's run  -> (new run start of e) + (j - old run start) + #{new facts of e with key <  key_j}
+          i-th new fact of e     -> (new run start of e) + i                   + #{old facts of e with key <= key_i}
+        Equal to PairIndex(old ++ new) array for array (the new facts may carry any timestamps: the tables hold no order
+        between facts but the key's)."""
+        ne, nr, no, nt = self.sorted_new(new_quads)
+        n, m, N = len(self), len(ne), self.num_ent
+        add = np.bincount(ne, minlength=N) if m else np.zeros(N, dtype=np.int64)
+        new_ptr = np.concatenate(([0], np.cumsum(add))).astype(np.int64)      # the new facts of e: [new_ptr[e], new_ptr[e + 1])
+        run2 = self.run_ptr + new_ptr
+        out = PairIndex.__new__(PairIndex)
+        out.role, out.num_ent, out.run_ptr = self.role, N, run2
+        rel2, other2, t2 = (np.empty(n + m, dtype=np.int64) for _ in range(3))
+        key_lt = lambda a, b: (a[0] < b[0]) or (a[0] == b[0] and (a[1] < b[1] or (a[1] == b[1] and a[2] < b[2])))
+        old_ent = np.repeat(np.arange(N, dtype=np.int64), np.diff(self.run_ptr))
+        for j in range(n):
+            e = old_ent[j]
+            key = (self.p_rel[j], self.p_other[j], self.p_t[j])
+            lo, hi = new_ptr[e], new_ptr[e + 1]
+            while lo < hi:                                                      # first new fact of e with key >= key_j
+                mid = (lo + hi) // 2
+                if key_lt((nr[mid], no[mid], nt[mid]), key):
+                    lo = mid + 1
+                else:
+                    hi = mid
+            p = run2[e] + (j - self.run_ptr[e]) + (lo - new_ptr[e])
+            rel2[p], other2[p], t2[p] = key
+        for i in range(m):
+            e = ne[i]
+            key = (nr[i], no[i], nt[i])
+            lo, hi = self.run_ptr[e], self.run_ptr[e + 1]
+            while lo < hi:                                                      # first old fact of e with key > key_i
+                mid = (lo + hi) // 2
+                if key_lt(key, (self.p_rel[mid], self.p_other[mid], self.p_t[mid])):
+                    hi = mid
+                else:
+                    lo = mid + 1
+            p = run2[e] + (i - new_ptr[e]) + (lo - self.run_ptr[e])
+            rel2[p], other2[p], t2[p] = key
+        out.p_rel, out.p_other, out.p_t = rel2, other2, t2
+        return out
+
+    def sub_run(self, ent, rel):
+        """[a, b) of the facts of (ent, rel): two searches over p_rel inside the entity's run; (0, 0) for an entity outside
+        [0, num_ent)."""
+        if ent < 0 or ent >= self.num_ent:
+            return 0, 0
+        lo, hi = int(self.run_ptr[ent]), int(self.run_ptr[ent + 1])
+        a = lo + int(np.searchsorted(self.p_rel[lo:hi], rel, side='left'))
+        b = lo + int(np.searchsorted(self.p_rel[lo:hi], rel, side='right'))
+        return a, b
+
+    def prior_rows(self, ent, rel, t, as_of, half_life=None, inv_half_life=None):
+        """The recurrence statistic of the queries (ent, rel, t) [n] with histories as of as_of (<= t): CSR lists (ptr int64
+        [n + 1], col int64, w float64), row i holding, in ascending partner order, every partner o of a fact (ent_i, rel_i,
+        o, t') with t' < as_of_i and w[o] = sum over those facts of 2^(-(t_i - t') * inv_half_life).  half_life None (or
+        inv_half_life 0): plain counts.  inv_half_life, when given, is used as it stands (the device takes it as fp32:
+        recurrence.RecurrencePrior.inv_half_life); else it is 1 / half_life."""
+        ent, rel, t = (np.asarray(x, dtype=np.int64).reshape(-1) for x in (ent, rel, t))
+        as_of = np.broadcast_to(np.asarray(as_of, dtype=np.int64).reshape(-1), ent.shape)
+        ihl = float(inv_half_life) if inv_half_life is not None else (0.0 if half_life is None else 1.0 / float(half_life))
+        ptr, col, w = [0], [], []
+        for i in range(len(ent)):
+            a, b = self.sub_run(int(ent[i]), int(rel[i]))
+            seen = self.p_t[a:b] < as_of[i]
+            o, tp = self.p_other[a:b][seen], self.p_t[a:b][seen]
+            if len(o):
+                cols, inv = np.unique(o, return_inverse=True)
+                col.append(cols)
+                w.append(np.bincount(inv, weights=np.exp2(-(t[i] - tp).astype(np.float64) * ihl), minlength=len(cols)))
+            ptr.append(ptr[-1] + (len(col[-1]) if len(o) else 0))
+        return (np.asarray(ptr, dtype=np.int64), np.concatenate(col) if col else np.zeros(0, dtype=np.int64),
+                np.concatenate(w) if w else np.zeros(0, dtype=np.float64))
+
+    def prior_stats(self, ent, rel, t, as_of):
+        """int64 [n, 2] = (distinct partners seen before as_of, facts counted) of every query: the integers
+        renet_recurrence_mix_rows reports."""
+        ptr, col, w = self.prior_rows(ent, rel, t, as_of)
+        facts = [int(round(w[a:b].sum())) for a, b in zip(ptr[:-1], ptr[1:])]
+        return np.stack((np.diff(ptr), np.asarray(facts, dtype=np.int64)), axis=1).reshape(-1, 2)
+
+
 def build_graph_dict(quads, num_rels):
     """get_history_graph.py:137-140: {t: TimeGraph}, ascending time."""
     quads = np.asarray(quads, dtype=np.int64)

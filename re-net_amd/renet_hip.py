@@ -176,6 +176,10 @@ _SIGNATURES = {
     'renet_store_append': (c_int, [c_void_p] * 7 + [c_int] * 4 + [c_void_p] * 4 + [c_int, c_int] + [c_void_p] * 8
                            + [c_size_t, c_void_p]),
     'renet_append_i32': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    'renet_pair_append': (c_int, [c_void_p] * 3 + [c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int]
+                          + [c_void_p] * 4 + [c_int] + [c_void_p] * 4),
+    'renet_recurrence_mix_rows': (c_int, [c_void_p] * 4 + [c_int] + [c_void_p] * 3 + [c_int, c_void_p, c_void_p, c_int, c_int,
+                                          c_void_p, c_int, c_int, c_float, c_float] + [c_void_p] * 4),
     'renet_build_full_graphs_workspace': (c_size_t, [c_void_p, c_int, c_int, c_int]),
     'renet_build_full_graphs': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t,
                                         c_void_p]),
@@ -1663,6 +1667,75 @@ def append_i32(old, add, n_old=None):
     _check(lib().renet_append_i32(_i32(old) if n_old else None, n_old, _i32(add) if n_add else None, n_add,
                                   out.data_ptr(), _stream()), 'append_i32')
     return out
+
+
+def pair_append(old, ent_ptr, snap_ptr, ent_ptr_new, snap_ptr_new, num_ent, new):
+    """renet_pair_append: the pair tables of ONE role after the facts `new` were appended.  old = (p_rel, p_other, p_t) [n];
+    ent_ptr / snap_ptr of the old history index and ent_ptr_new / snap_ptr_new of the longer one (store_append's outputs);
+    new = int32 [4, m]: the new facts' entity, relation, partner and time, sorted by that key -> (p_rel, p_other, p_t)
+    [n + m], freshly allocated.  Equal to preprocess.PairIndex.appended array for array.  On the current stream; nothing is
+    read back; the old tables stay valid."""
+    p_rel, p_other, p_t = old
+    num_ent, n = int(num_ent), int(p_rel.numel())
+    if not (new.dim() == 2 and new.shape[0] == 4):
+        raise RenetHipError('pair_append: new must be [4, m]')
+    m = int(new.shape[1])
+    if p_other.numel() != n or p_t.numel() != n or ent_ptr.numel() != num_ent + 1 or ent_ptr_new.numel() != num_ent + 1:
+        raise RenetHipError('pair_append: the old tables do not fit num_ent / their own lengths')
+    out = tuple(torch.empty(n + m, device=ent_ptr.device, dtype=torch.int32) for _ in range(3))
+    t0 = _timed()
+    _check(lib().renet_pair_append(*[_i32(a, 'pair table') if n else None for a in old], n, _i32(ent_ptr, 'ent_ptr'),
+                                   _i32(snap_ptr, 'snap_ptr'), int(snap_ptr.numel()) - 1, _i32(ent_ptr_new, 'ent_ptr'),
+                                   _i32(snap_ptr_new, 'snap_ptr'), int(snap_ptr_new.numel()) - 1, num_ent,
+                                   *[_i32(new[k], 'new') if m else None for k in range(4)], m,
+                                   *[a.data_ptr() for a in out], _stream()), 'pair_append')
+    _timed_end(t0, 'pair_append', nbytes=float((2 * n + m) * 12))
+    return out
+
+
+RECURRENCE_MAX_C = 1 << 20              # RENET_RECURRENCE_MAX_C of include/renet_hip.h
+
+
+def recurrence_mix_rows(ent, rel, t, as_of, tables, ent_ptr, snap_ptr, num_ent, logits, alpha, inv_half_life=0.0,
+                        num_cols=None, want_stats=False):
+    """renet_recurrence_mix_rows, one direction: out [n, C] (fp32, fresh) with
+        out[i, o] = log((1 - a_i) softmax(logits[i])[o] + a_i w_i[o] / W_i)
+    for the queries (ent, rel, t, as_of) (int32 device [n], as_of <= t), w_i[o] the 2^(-(t - t') inv_half_life)-weighted
+    count of the facts (ent_i, rel_i, o, t' < as_of_i) of the role's pair tables `tables` = (p_rel, p_other, p_t), W_i their
+    sum and a_i = alpha where W_i > 0, else 0.  logits [n, C] (fp32, unit inner stride; not written) or None: uniform rows of
+    num_cols columns.  ent_ptr / snap_ptr: the role's resident history index.  0 <= alpha < 1.  A row of out is a normalised
+    log-probability row: rank_rows3 and topk_rows read it as they read logits.  want_stats: -> (out, stats int32 [n, 2] =
+    (distinct partners, facts counted), W fp32 [n])."""
+    n = int(ent.numel())
+    if any(int(a.numel()) != n for a in (rel, t, as_of)):
+        raise RenetHipError('recurrence_mix_rows: ent, rel, t and as_of must have one entry per row')
+    if logits is not None:
+        if not (logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1):
+            raise RenetHipError('recurrence_mix_rows needs a 2-D float32 device tensor with unit inner stride')
+        if logits.shape[0] != n or (num_cols is not None and int(num_cols) != logits.shape[1]):
+            raise RenetHipError('recurrence_mix_rows: shape mismatch')
+        c, ld = int(logits.shape[1]), (max(_ld(logits), logits.shape[1]) if n == 1 else _ld(logits))
+    else:
+        if num_cols is None:
+            raise RenetHipError('recurrence_mix_rows: uniform rows need num_cols')
+        c, ld = int(num_cols), int(num_cols)
+    p_rel, p_other, p_t = tables
+    nf = int(p_rel.numel())
+    if p_other.numel() != nf or p_t.numel() != nf or ent_ptr.numel() != int(num_ent) + 1:
+        raise RenetHipError('recurrence_mix_rows: the pair tables do not fit num_ent / their own lengths')
+    dev = ent.device
+    out = torch.empty(n, c, device=dev, dtype=torch.float32)
+    stats = torch.empty(n, 2, device=dev, dtype=torch.int32) if want_stats else None
+    wsum = torch.empty(n, device=dev, dtype=torch.float32) if want_stats else None
+    t0 = _timed()
+    _check(lib().renet_recurrence_mix_rows(_i32(ent, 'ent'), _i32(rel, 'rel'), _i32(t, 't'), _i32(as_of, 'as_of'), n,
+                                           *[_i32(a, 'pair table') if nf else None for a in tables], nf,
+                                           _i32(ent_ptr, 'ent_ptr'), _i32(snap_ptr, 'snap_ptr'), int(snap_ptr.numel()) - 1,
+                                           int(num_ent), None if logits is None else logits.data_ptr(), ld, c, float(alpha),
+                                           float(inv_half_life), out.data_ptr(), _i32(stats), _f32(wsum), _stream()),
+           'recurrence_mix_rows')
+    _timed_end(t0, 'recurrence_mix_rows', nbytes=float(n * c * (4 if logits is None else 12)))
+    return (out, stats, wsum) if want_stats else out
 
 
 def joint_row_offsets(scores, num_rels, logits_r):

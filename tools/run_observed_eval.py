@@ -9,6 +9,7 @@ protocol under which RE-GCN, xERTE and TITer report the time-aware filter.  NOT 
                                       [--horizon H] [--queries FILE [--k K]] [--observe-loop]
                                       [--rollout H [--num-k K]]
                                       [--online [STEPS] [--replay N] [--online-global] [--lr LR]]
+                                      [--recurrence ALPHA [--half-life H]]
 
 --horizon H evaluates with STALE histories (RENet.evaluate_forecast with ObservedStream.horizon_as_of): the split's timestamps
 are cut into blocks of H, and every query forecasts from the facts before the first timestamp of its block; nothing is
@@ -37,6 +38,12 @@ of the --replay timestamps before it; with --online-global the global model take
 resident global table is recomputed (ObservedStream.refresh_global).  The weights that rank timestamp t have seen every
 evaluated timestamp before t: a FOURTH protocol, whose numbers must not be mixed with the static observed ones, --horizon,
 --rollout or the reference's multi-step numbers.  The checkpoints are not written back.
+
+--recurrence ALPHA [--half-life H] adds the RECURRENCE PRIOR (re-net_amd/recurrence.py) to the plain pass (and to --horizon):
+after the model's own metrics it prints the model-free BASELINE alone -- how often, and with --half-life how recently, (s, r)
+connected to each object before the query's as-of time, ranked under the same histories, filters and tie rule -- and the
+model MIXED with the prior at weight ALPHA, each labelled as such.  The baseline is a protocol-matched yardstick: report it
+with its ALPHA and half-life (in the dataset's raw timestamp units), beside model numbers of the same protocol only.
 
 --events adds the EVENT forecasts (RENet.evaluate_events_observed): MRR / Hits of the gold (relation, entity) pair among all
 pairs of the given entity, and of the gold relation given both endpoints, in the three settings; with K also the K most
@@ -216,7 +223,18 @@ def main():
     ap.add_argument('--online-global', action='store_true',
                     help='the global model learns too: one step per timestamp, then the resident table is refreshed (--online)')
     ap.add_argument('--lr', type=float, default=1e-3, help='learning rate of the online steps (--online)')
+    ap.add_argument('--recurrence', type=float, default=None, metavar='ALPHA',
+                    help='also print the recurrence baseline alone and the model mixed with it at weight ALPHA in [0, 1)')
+    ap.add_argument('--half-life', type=float, default=None, metavar='H',
+                    help='half-life of the recurrence prior in raw timestamp units (default: frequency only)')
     args = ap.parse_args()
+    if args.recurrence is not None:
+        if not 0.0 <= args.recurrence < 1.0 or (args.half_life is not None and args.half_life <= 0):
+            raise SystemExit('--recurrence takes ALPHA in [0, 1), --half-life a positive H')
+        if args.observe_loop or args.rollout is not None or args.online is not None or args.queries is not None:
+            raise SystemExit('--recurrence goes with the plain pass and --horizon only')
+    elif args.half_life is not None:
+        raise SystemExit('--half-life belongs to --recurrence')
     if args.online is not None:
         if args.online < 0 or args.replay < 0:
             raise SystemExit('--online and --replay must be >= 0')
@@ -310,6 +328,31 @@ def main():
     if args.horizon is not None:
         record['horizon'] = args.horizon
     print(json.dumps(record))
+    if args.recurrence is not None:
+        import recurrence
+        prior = recurrence.RecurrencePrior(args.recurrence, args.half_life)
+        as_of = None if args.horizon is None else obs.horizon_as_of(idx, args.horizon)
+        t3 = time.perf_counter()
+        base_ranks, base_loss = recurrence.evaluate(obs, obs.allq[idx], prior, as_of=as_of, max_batch=args.max_batch)
+        torch.cuda.synchronize()
+        t4 = time.perf_counter()
+        mix_ranks, mix_loss = model.evaluate_forecast(obs, obs.allq[idx], as_of=as_of, max_batch=args.max_batch, prior=prior)
+        torch.cuda.synchronize()
+        t5 = time.perf_counter()
+        for label, rk, ls, dt in (('RECURRENCE BASELINE ALONE (no model)', base_ranks, base_loss, t4 - t3),
+                                  ('MODEL MIXED WITH THE RECURRENCE PRIOR', mix_ranks, mix_loss, t5 - t4)):
+            print('%s, alpha %g, half-life %s: pass %.2f s (%.0f quadruples/s), mean loss %.6f'
+                  % (label, prior.alpha, 'none (frequency only)' if prior.half_life is None else '%g' % prior.half_life, dt,
+                     len(idx) / max(dt, 1e-9), float(np.mean(ls))))
+            for name in SETTINGS:
+                m = U.rank_metrics(rk[name])
+                print('%-14s MRR %.6f  MR %.3f  Hits@1 %.6f  Hits@3 %.6f  Hits@10 %.6f'
+                      % (name, m['mrr'], m['mr'], m['hits@1'], m['hits@3'], m['hits@10']))
+        print('(the unmixed model is the block above; all three share the protocol, the filters and the tie rule)')
+        extra = dict(record, recurrence={'alpha': prior.alpha, 'half_life': prior.half_life},
+                     baseline={name: U.rank_metrics(base_ranks[name]) for name in SETTINGS},
+                     mixed={name: U.rank_metrics(mix_ranks[name]) for name in SETTINGS})
+        print(json.dumps(extra))
     if args.events is not None:
         t3 = time.perf_counter()
         ev = model.evaluate_events_observed(obs, idx)
