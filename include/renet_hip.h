@@ -977,9 +977,12 @@ int renet_build_batch_grouped(const RenetGroupedStoreDev* store, const int32_t* 
  *                          is recorded when the entity head's weight / bias gradients are complete (early all-reduce bucket),
  *                          ev_gru_done (optional) when both encoders' parameter gradients are (the middle bucket)
  *   both return the number of C-ABI launches they issued in *n_launches (optional).
- *   RENET_STEP_BATCH (environment, read once; default 6): bit 2 = the head's and the sequence assembly's segmented adds as one
- *   renet_segment_add_multi launch, bit 4 = the W_hh splits issued early on the side stream (renet_gru_split_weights); 0 = one
- *   launch per sum, the splits inside the GRU calls.  Same bits of every result either way.
+ *   RENET_STEP_BATCH (environment, read once; default 22; renet_step_batch_mask() returns it): bit 2 = the head's and the
+ *   sequence assembly's segmented adds as one renet_segment_add_multi launch, bit 4 = the W_hh splits issued early on the
+ *   side stream (renet_gru_split_weights), bit 16 = a stale head weight (lin_w_stale; lin_w_planes is then the buffer
+ *   renet_step_forward fills) is packed on the side stream beside the forward recurrence instead of at the top of the main
+ *   stream; bits 1 and 8 are not assigned; 0 = one launch per sum, the splits inside the GRU calls.  Same bits of every
+ *   result either way.
  * fp32-class default mode only (bf16x6 GEMMs, bf16x6 recurrences); tensors below 2 GiB. */
 typedef struct { const int32_t *order, *seg_ptr, *target; int num_segments; } RenetSegPlan;
 typedef struct {
@@ -997,6 +1000,7 @@ typedef struct {
     const void* lin_w_planes;                  /* optional: renet_pack_planes(lin_w); NULL = the in-loop-split head */
     size_t lin_w_plane;                        /*   elements per plane */
     int lin_w_ld;                              /*   Cp of the planes */
+    int lin_w_stale;                           /* != 0: the planes are older than lin_w; renet_step_forward packs them */
 } RenetStepModel;
 typedef struct {
     int N, E, nA, S, B, L, n_items;            /* nodes, edges, rows of layer 2, packed rows, sequences, steps, items */
@@ -1024,6 +1028,7 @@ int renet_step_forward(const RenetStepModel* m, const RenetStepBatch* b, const R
                        int* n_launches);
 int renet_step_backward(const RenetStepModel* m, const RenetStepBatch* b, const RenetStepRun* r, const float* g,
                         int defer_side, void* ev_head_done, void* ev_gru_done, int* n_launches);
+int renet_step_batch_mask(void);
 /* x[0..n) += y[0..n) (the two heads' gradients wrt the same gathered rows ent[s], model.py:89,98, before ONE scatter-add) */
 int renet_add_inplace(float* x, const float* y, size_t n, void* stream);
 /* x[0..n) = 0 as an ordinary kernel launch (the zero-initialised scatter-add targets of the backward pass: hipMemsetAsync goes

@@ -11,6 +11,8 @@
 // gradients (tests/test_gpu_step_plan.py).  Two groups of small launches are issued in a batched form that carries the same
 // sums in the same order (RENET_STEP_BATCH below; tests/test_gpu_backward_batching.py, profiles/backward_batching.md): the
 // segmented adds of the head and of the sequence assembly as ONE launch, the W_hh fragment splits early on the side stream.
+// The planes of a stale head weight are packed by the list itself, on the side stream beside the forward recurrence
+// (tests/test_gpu_step_reductions.py, profiles/step_reductions.md).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdint>
@@ -74,15 +76,21 @@ struct Lay {
 
 bool use_planes(const RenetStepModel& m) { return m.lin_w_planes != nullptr; }
 
-// RENET_STEP_BATCH: which of the batched forms of the small launches the list uses (default 6 = both; 0 = one launch per
-// sum and the W_hh splits inside the GRU calls; the bits exist for A/B timing and for tests against that list):
+// RENET_STEP_BATCH: which of the batched forms of the small launches the list uses (default 22 = all; 0 = one launch per
+// sum and the W_hh splits inside the GRU calls; the bits exist for A/B timing and for tests against that list; 6 is the list
+// of profiles/backward_batching.md):
+//   1  not assigned (accepted and ignored).  The four GRU bias gradients as one multi-job column sum that reads dGh's copied
+//      r / z columns once were built twice and measured inside the noise both times, so they are not in the tree
+//      (profiles/backward_batching.md section 5, profiles/step_reductions.md section 3)
 //   2  the head's and the sequence assembly's segmented adds as ONE renet_segment_add_multi call
 //   4  the W_hh fragment splits issued early on the side stream (renet_gru_split_weights), the recurrences presplit
-// (Bit 1 is not assigned: the four GRU bias column sums as one pair of launches measured no gain of their own and are not
-// in the tree, profiles/backward_batching.md section 5.)
-enum { kBatchSegAdd = 2, kBatchSplit = 4 };
+//   8  not assigned (accepted and ignored).  Layer 1's entity reduction with its zero pass folded in was built and measured
+//      inside the noise of the step (profiles/step_reductions.md section 3)
+//  16  a stale head weight (RenetStepModel.lin_w_stale) is packed on the side stream beside the forward recurrence; without
+//      the bit the list packs it as its first launch on the main stream
+enum { kBatchSegAdd = 2, kBatchSplit = 4, kBatchPack = 16 };
 int step_batch() {
-    static const int v = renet_env_int("RENET_STEP_BATCH", 6, 0, 7);
+    static const int v = renet_env_int("RENET_STEP_BATCH", 22, 0, 31);
     return v;
 }
 
@@ -258,6 +266,13 @@ int renet_step_forward(const RenetStepModel* mp, const RenetStepBatch* bp, const
     // The W_hh planes of the recurrence depend on nothing in the step but the weights: split them now, as the first launch of
     // the side stream.  The fork orders it behind everything the caller enqueued on the main stream (the optimizer's update
     // of W_hh, the last reader of the workspace block); the join in front of the recurrence covers it.
+    // A stale head weight's planes are read first by the logits GEMM, ~0.5 ms into the step.  Packed here they are the first
+    // launch of the main stream with nothing beside them; with kBatchPack the pack waits for the fork in front of the forward
+    // recurrence (whose bound is each CU's L2 -> L1 path, with HBM nearly idle and the side stream empty).
+    const bool pack_w = use_planes(m) && m.lin_w_stale;
+    const bool pack_side = pack_w && (step_batch() & kBatchPack) && s.two();
+    hipEvent_t ev_pack = nullptr;
+    if (pack_w && !pack_side) CK(renet_pack_planes(m.lin_w, NE, 3 * D, 3 * D, 0, const_cast<void*>(m.lin_w_planes), s.main));
     bool presplit = false;
     if (step_batch() & kBatchSplit) {
         s.fork();
@@ -285,6 +300,16 @@ int renet_step_forward(const RenetStepModel* mp, const RenetStepBatch* bp, const
     CK(gemm(s.side, wss, L.gemm_ws_bytes, 0, 1, S, 3 * D, 3 * D, F(L.Xr), 3 * D, m.wih_r, 3 * D, 0.f, F(L.gi1), 3 * D, m.bih_r));
     CK(gemm(s.main, wsm, L.gemm_ws_bytes, 0, 1, S, 3 * D, 4 * D, F(L.X), 4 * D, m.wih, 4 * D, 0.f, F(L.gi0), 3 * D, m.bih));
     s.join();
+    if (pack_side) {
+        // behind the join: the side stream is empty from here to the relation head.  The fork orders the pack behind the last
+        // reader of the old planes (the previous step's head GEMMs, on the main stream); ev_pack is what the logits GEMM waits for
+        s.fork();
+        CK(renet_pack_planes(m.lin_w, NE, 3 * D, 3 * D, 0, const_cast<void*>(m.lin_w_planes), s.side));
+        ev_pack = step_event(s.next_ev++ & 7);
+        if (!ev_pack) return (int)hipErrorOutOfMemory;
+        const hipError_t e = hipEventRecord(ev_pack, s.side);
+        if (e != hipSuccess) return (int)e;
+    }
     {
         const float* gi[2] = {F(L.gi0), F(L.gi1)};
         const int32_t* so[2] = {b.step_off_host, b.step_off_host};
@@ -308,6 +333,10 @@ int renet_step_forward(const RenetStepModel* mp, const RenetStepBatch* bp, const
         // ONE split of feat, with the ones column the weight-gradient GEMM wants (its bias column): the logits GEMM reads
         // the same planes with K = 3D -- the ones meet the zero k padding of the weight's planes and add exactly 0
         CK(renet_pack_planes(F(L.feat1), B, 3 * D, 3 * D, 1, W + L.featp1, s.main));
+        if (ev_pack) {
+            const hipError_t e = hipStreamWaitEvent(s.main, ev_pack, 0);
+            if (e != hipSuccess) return (int)e;
+        }
         const int sk = auto_split_k_planes(B, NE, 3 * D);
         CK(renet_gemm_planes(0, 0, B, NE, 3 * D, 1.f, nullptr, W + L.featp1, (int)L.featp1_ld, L.featp1_plane, m.lin_w_planes,
                              m.lin_w_ld, m.lin_w_plane, 0.f, F(L.logits), (int)L.logits_ld, m.lin_b, nullptr, sk,
@@ -495,5 +524,7 @@ int renet_step_backward(const RenetStepModel* mp, const RenetStepBatch* bp, cons
     if (n_launches) *n_launches = launches;
     return s.rc;
 }
+
+int renet_step_batch_mask(void) { return step_batch(); }
 
 }  // extern "C"

@@ -41,6 +41,7 @@ _SIGNATURES = {
     'renet_segment_add2': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
                                    c_void_p]),
     'renet_segment_add_multi': (c_int, [c_int, c_void_p, c_int, c_void_p]),
+    'renet_step_batch_mask': (c_int, []),
     'renet_gru_split_weights': (c_int, [c_int, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     'renet_gru_fwd_layouts_presplit': (c_int, _GRU_FWD_LAYOUTS_ARGS),
     'renet_gru_bwd_layouts_presplit': (c_int, _GRU_BWD_LAYOUTS_ARGS),
@@ -885,6 +886,21 @@ def weight_planes(w):
     all when the optimizer kernel wrote them (note_weight_planes) -- anything else on every call."""
     rec = _registered(w, whole=True)
     return _derived(rec, 'planes', w, lambda: pack_planes(w)) if rec is not None else pack_planes(w)
+
+
+def weight_planes_or_buffer(w):
+    """For a consumer that can pack for itself (the C launch list, step_plan): (planes, stale) of a registered weight, or None
+    for any other tensor.  stale = the cache holds nothing for the weight as it is now: `planes` is then an UNWRITTEN buffer,
+    and the consumer reports it with note_weight_planes(w, planes) once its pack is enqueued."""
+    rec = _registered(w, whole=True)
+    if rec is None:
+        return None
+    ent = rec.planes
+    if ent is not None and ent[0] == _weight_stamp(w):
+        if ent[2] is not None:
+            ent[2].wait(w.device)
+        return ent[1], False
+    return planes_empty(w.shape[0], w.shape[1], w.device), True
 
 
 def note_weight_planes(w, mat):

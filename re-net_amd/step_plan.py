@@ -51,7 +51,7 @@ _PARAMS = ('ent', 'rel', 'w1', 'loop1', 'w2', 'loop2', 'wih', 'whh', 'bih', 'bhh
 class StepModelC(ctypes.Structure):
     _fields_ = [('D', _I), ('num_ent', _I), ('T', _I), ('C2', _I), ('drop_p', ctypes.c_float)] + \
                [(n, _P) for n in _PARAMS] + [('g_' + n, _P) for n in _PARAMS] + \
-               [('glob', _P), ('lin_w_planes', _P), ('lin_w_plane', ctypes.c_size_t), ('lin_w_ld', _I)]
+               [('glob', _P), ('lin_w_planes', _P), ('lin_w_plane', ctypes.c_size_t), ('lin_w_ld', _I), ('lin_w_stale', _I)]
 
 
 _BATCH_INTS = ('N', 'E', 'nA', 'S', 'B', 'L', 'n_items', 'n_groups', 'n_groups_out', 'n_heavy', 'n_heavy_out', 'n_chunks',
@@ -228,11 +228,17 @@ class StepFn(Function):
             s_r2 = ops.next_seed(graph_site=True) if p > 0 else 0
             s_x, s_xr = (ops.next_seed(), ops.next_seed()) if p > 0 else (0, 0)
         s_h1, s_h2 = (ops.next_seed(), ops.next_seed()) if p > 0 else (0, 0)
-        planes = K.weight_planes(params[14]) if K.use_planes(params[14], params[14].shape[0]) else None
+        lib = K.lib()
+        planes, stale = None, False
+        if K.use_planes(params[14], params[14].shape[0]):
+            # RENET_STEP_BATCH bit 16: planes older than the weight (an optimizer update since they were packed) are packed by
+            # the list itself, on its side stream beside the forward recurrence; the cache is then marked current below
+            own = K.weight_planes_or_buffer(params[14]) if lib.renet_step_batch_mask() & 16 else None
+            planes, stale = own if own is not None else (K.weight_planes(params[14]), False)
         m = _model_struct(net, params, planes)
+        m.lin_w_stale = int(stale)
         m.glob = K._f32(g.glob, 'global embeddings')
         b = _batch_struct(prep)
-        lib = K.lib()
         nbytes = lib.renet_step_workspace(ctypes.addressof(m), ctypes.addressof(b))
         if nbytes == 0:
             raise K.RenetHipError('renet_step_workspace rejected the model / batch')
@@ -247,6 +253,10 @@ class StepFn(Function):
         nl = ctypes.c_int(0)
         K._check(lib.renet_step_forward(ctypes.addressof(m), ctypes.addressof(b), ctypes.addressof(r), rl.data_ptr(),
                                         ctypes.addressof(nl)), 'renet_step_forward')
+        if stale:
+            # (the main stream has waited for the pack in front of the logits GEMM: the guard recorded here covers it)
+            K.note_weight_planes(params[14], planes)
+            m.lin_w_stale = 0
         ctx.net, ctx.prep, ctx.m, ctx.b, ctx.r, ctx.ws, ctx.planes = net, prep, m, b, r, ws, planes
         ctx.consumed = False
         ctx.launches = nl.value
