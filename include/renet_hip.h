@@ -356,6 +356,15 @@ int renet_gemm_planes(int a_tr, int b_tr, int M, int N, int K, float alpha, cons
  * Replaces F.cross_entropy's backward (model.py:91,100) as renet_softmax_ce does. */
 int renet_softmax_ce_planes(const float* logits, const int32_t* target, int B, int C, int ld, float grad_scale,
                             float* row_loss, void* dl_planes, size_t plane, int ld16, int rows16, void* stream);
+/* renet_softmax_ce_planes for the loss THROUGH THE COPY MIX (renet_mix_ce below states it): the same planes -- T16 layout,
+ * three-term RNE split, zeroed columns [C, ld16) and rows [B, ceil16(B)), the same row-to-workgroup map, the logits left
+ * untouched -- of (softmax - onehot) * (grad_scale * s_b), with row_loss and d_a as there.  The four-row writer for aligned
+ * C >= 2048 (ld16 <= 24576), the generic writer otherwise; RENET_SOFTMAX_ROWS is not read.  a_row = 0 gives the planes and
+ * losses of renet_softmax_ce_planes bit for bit.  A missing array, ld < C or a planes buffer that does not fit:
+ * RENET_ERR_BADARG before any launch. */
+int renet_mix_ce_planes(const float* logits, const int32_t* target, const float* a_row, const float* q_row, int B, int C,
+                        int ld, float grad_scale, float* row_loss, void* dl_planes, size_t plane, int ld16, int rows16,
+                        float* d_a, void* stream);
 
 /* column sums: out[n] = beta * out[n] + sum_m X[m,n]  (bias gradients; beta = 1 accumulates straight into
  * an existing .grad); two deterministic passes over row groups, `workspace` = renet_colsum_workspace(M, N)
@@ -516,6 +525,19 @@ int renet_concat3_bwd(const float* dfeat, int B, int D, int parts, float drop_p,
 int renet_dropout(const float* x, size_t n, float drop_p, uint64_t seed, float* y, void* stream);
 int renet_softmax_ce(const float* logits, const int32_t* target, int B, int C, int ld,
                      float grad_scale, float* row_loss, float* dlogits, void* stream);
+/* renet_softmax_ce for the loss THROUGH THE COPY MIX of the recurrence prior (renet_recurrence_mix_rows): per row b the gate
+ * a_row[b] in [0, 1) and the prior's mass on the gold column q_row[b] = w[target] / W (renet_recurrence_gold_rows), device
+ * fp32 [B].  The caller has zeroed a_row where the prior abstains; the kernel trusts it.  With p = softmax(logits[b, :]),
+ * g = target[b]:
+ *     m = (1 - a) p_g + a q,   row_loss[b] = -log m,   s_b = (1 - a) p_g / m  in [0, 1]
+ *     dlogits[b, c] = (p_c - [c == g]) * (grad_scale * s_b)          (NULL: not written; may alias logits)
+ *     d_a[b]        = grad_scale * (p_g - q) / m                     (NULL: not written)
+ * Where a == 0 or q == 0: s_b = 1 exactly -- the gradient row of renet_softmax_ce bit for bit -- row_loss = (logsumexp - x_g)
+ * - log1p(-a), and p_g, which may underflow to 0, is not divided by: d_a = grad_scale * (p_g - q) / ((1 - a) p_g), 0 where
+ * p_g == 0.  The same kernels as renet_softmax_ce (their MIX instances, chosen by the same widths), fp32 arithmetic; the
+ * per-row scalars cost no pass over the row.  A missing array or ld < C: RENET_ERR_BADARG before any launch. */
+int renet_mix_ce(const float* logits, const int32_t* target, const float* a_row, const float* q_row, int B, int C, int ld,
+                 float grad_scale, float* row_loss, float* dlogits, float* d_a, void* stream);
 /* Softmax cross-entropy against SPARSE SOFT targets (the global model's loss, global_model.py:52-55, with the target
  * distribution of row b given as the entries k in [tgt_ptr[b], tgt_ptr[b + 1]): columns tgt_col[k] -- distinct, ascending,
  * in [0, C) -- with weights tgt_w[k] >= 0 that need NOT sum to 1).  With W = sum_k tgt_w[k] and p = softmax(logits[b, :]):
@@ -886,7 +908,21 @@ int renet_append_i32(const int32_t* old, int n_old, const int32_t* add, int n_ad
  * logp being -log p_mix[gold] / log p_mix.  alpha = 0 gives log_softmax(logits).  A partner outside [0, C) is not addressed.
  * stats / stats_w (both or neither): int32 [n, 2] = (distinct partners seen before as_of, facts counted) and fp32 W [n].
  * C in [1, RENET_RECURRENCE_MAX_C]; alpha outside [0, 1), a negative or non-finite inv_half_life, n < 0, ld < C or a missing
- * array: RENET_ERR_BADARG before any launch; n == 0 is a no-op.  One workgroup per row; no workspace. */
+ * array: RENET_ERR_BADARG before any launch; n == 0 is a no-op.  One workgroup per row; no workspace.
+ *
+ * renet_recurrence_mix_rows_gated: the same kernel body with ONE GATE PER ROW, alpha_row[i] (device fp32 [n], each in [0, 1):
+ * the caller's to keep, the entry cannot read it) in the place of alpha -- what a learned per-relation gate is evaluated
+ * with.  a_i = alpha_row[i] if W > 0 else 0: a row without history abstains whatever its gate.  A constant alpha_row gives
+ * the bits of renet_recurrence_mix_rows.  Refusals as there, and a missing alpha_row.
+ *
+ * renet_recurrence_gold_rows: what the LOSS through the mix needs of the prior (renet_mix_ce): for row i and the column
+ * gold[i] (device int32 [n]),
+ *     W[i] = the W of renet_recurrence_mix_rows -- the same strided pass and reduction tree: its stats_w bit for bit
+ *     q[i] = fp32(w[gold[i]] / W[i]), both sums in fp64; the gold partner's group is found by binary searches, its counted
+ *            facts are those with t' < as_of
+ * q = 0 and W = 0 where the pair has no history before as_of or the entity lies outside [0, num_ent); q = 0 where gold lies
+ * outside [0, C) or has no counted fact.  One workgroup per row, two floats out, no atomics, no workspace; refusals as for
+ * renet_recurrence_mix_rows. */
 #define RENET_RECURRENCE_MAX_C (1 << 20)
 int renet_pair_append(const int32_t* p_rel, const int32_t* p_other, const int32_t* p_t, int n, const int32_t* ent_ptr,
                       const int32_t* snap_ptr, int n_snaps, const int32_t* ent_ptr_new, const int32_t* snap_ptr_new,
@@ -897,6 +933,15 @@ int renet_recurrence_mix_rows(const int32_t* ent, const int32_t* rel, const int3
                               const int32_t* ent_ptr, const int32_t* snap_ptr, int n_snaps, int num_ent, const float* logits,
                               int ld, int C, float alpha, float inv_half_life, float* out, int32_t* stats, float* stats_w,
                               void* stream);
+int renet_recurrence_mix_rows_gated(const int32_t* ent, const int32_t* rel, const int32_t* t, const int32_t* as_of, int n,
+                                    const int32_t* p_rel, const int32_t* p_other, const int32_t* p_t, int n_facts,
+                                    const int32_t* ent_ptr, const int32_t* snap_ptr, int n_snaps, int num_ent,
+                                    const float* logits, int ld, int C, const float* alpha_row, float inv_half_life,
+                                    float* out, int32_t* stats, float* stats_w, void* stream);
+int renet_recurrence_gold_rows(const int32_t* ent, const int32_t* rel, const int32_t* t, const int32_t* as_of,
+                               const int32_t* gold, int n, const int32_t* p_rel, const int32_t* p_other, const int32_t* p_t,
+                               int n_facts, const int32_t* ent_ptr, const int32_t* snap_ptr, int n_snaps, int num_ent, int C,
+                               float inv_half_life, float* q, float* W, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * DEVICE builder for the FULL-GRAPH batches of the global model (graph.build_full_graphs; reference Aggregator.py:44-55 /

@@ -2,7 +2,10 @@
 //   renet_pair_append         keeps the relation-keyed view of one role's fact runs sorted under an append
 //                             (host statement: preprocess.PairIndex.appended, array for array)
 //   renet_recurrence_mix_rows turns that view into normalised log-probability rows, mixed with the model's logits
-//                             (host statement: preprocess.PairIndex.prior_rows + tests/recurrence_statement.py mix_rows)
+//                             (host statement: preprocess.PairIndex.prior_rows + tests/recurrence_statement.py mix_rows);
+//                             renet_recurrence_mix_rows_gated is the same kernel body with one gate per row
+//   renet_recurrence_gold_rows the prior mass of ONE column per row, q = w[gold] / W, and W: what the loss through the mix
+//                             needs of the prior (host statement: tests/copy_gate_statement.py gold_rows)
 //
 // PAIR TABLES.  Per role the facts of entity e are the index range run(e) = [snap_ptr[ent_ptr[e]], snap_ptr[ent_ptr[e + 1]])
 // of the resident history index (renet_store_append keeps it contiguous).  The pair tables p_rel / p_other / p_t hold the
@@ -157,12 +160,29 @@ __device__ __forceinline__ double rc_weight(int t, int tp, double ihl) { return 
 
 __device__ __forceinline__ float rc_dense(float l, double shift) { return (float)((double)l - shift); }
 
+// the (e, r) sub-run [a, b) of the pair tables; empty for an entity outside [0, num_ent)
+__device__ __forceinline__ void rc_pair_run(const int32_t* __restrict__ p_rel, int n_facts, const int32_t* __restrict__ ent_ptr,
+                                            const int32_t* __restrict__ snap_ptr, int n_snaps, int num_ent, int e, int r,
+                                            int& a, int& b) {
+    a = 0;
+    b = 0;
+    if (e >= 0 && e < num_ent && n_facts > 0) {
+        const int ra = rc_run(ent_ptr, snap_ptr, n_snaps, n_facts, e);
+        const int rb = max(ra, rc_run(ent_ptr, snap_ptr, n_snaps, n_facts, e + 1));
+        a = rc_lower(p_rel, ra, rb, r);
+        b = r == 0x7fffffff ? rb : rc_lower(p_rel, a, rb, r + 1);
+    }
+}
+
+// GATED: the gate of row i is alpha_row[i] instead of the launch's scalar; everything else is one body
+template <bool GATED>
 __global__ __launch_bounds__(RC_THREADS) void recurrence_mix_rows_kernel(
     const int32_t* __restrict__ q_ent, const int32_t* __restrict__ q_rel, const int32_t* __restrict__ q_t,
     const int32_t* __restrict__ q_as_of, const int32_t* __restrict__ p_rel, const int32_t* __restrict__ p_other,
     const int32_t* __restrict__ p_t, int n_facts, const int32_t* __restrict__ ent_ptr, const int32_t* __restrict__ snap_ptr,
-    int n_snaps, int num_ent, const float* __restrict__ logits, int ld, int C, float alpha, float inv_half_life,
-    float* __restrict__ out, int32_t* __restrict__ stats, float* __restrict__ stats_w) {
+    int n_snaps, int num_ent, const float* __restrict__ logits, int ld, int C, float alpha,
+    const float* __restrict__ alpha_row, float inv_half_life, float* __restrict__ out, int32_t* __restrict__ stats,
+    float* __restrict__ stats_w) {
     __shared__ float s_m[RC_WAVES];
     __shared__ double s_s[RC_WAVES], s_w[RC_WAVES];
     __shared__ int s_np[RC_WAVES], s_nf[RC_WAVES];
@@ -173,13 +193,8 @@ __global__ __launch_bounds__(RC_THREADS) void recurrence_mix_rows_kernel(
     const double ihl = (double)inv_half_life;
 
     // 1. the (e, r) sub-run [a, b)
-    int a = 0, b = 0;
-    if (e >= 0 && e < num_ent && n_facts > 0) {
-        const int ra = rc_run(ent_ptr, snap_ptr, n_snaps, n_facts, e);
-        const int rb = max(ra, rc_run(ent_ptr, snap_ptr, n_snaps, n_facts, e + 1));
-        a = rc_lower(p_rel, ra, rb, r);
-        b = r == 0x7fffffff ? rb : rc_lower(p_rel, a, rb, r + 1);
-    }
+    int a, b;
+    rc_pair_run(p_rel, n_facts, ent_ptr, snap_ptr, n_snaps, num_ent, e, r, a, b);
 
     // 2. this thread's share of W and of the counts
     double w_sum = 0.0;
@@ -247,7 +262,7 @@ __global__ __launch_bounds__(RC_THREADS) void recurrence_mix_rows_kernel(
         NF += s_nf[w];
     }
     const double lse = x ? log(S) + (double)M : log((double)C);
-    const double al = W > 0.0 ? (double)alpha : 0.0;
+    const double al = W > 0.0 ? (double)(GATED ? alpha_row[row] : alpha) : 0.0;
     if (tid == 0 && stats) {
         stats[2 * (size_t)row] = NP;
         stats[2 * (size_t)row + 1] = NF;
@@ -319,6 +334,56 @@ __global__ __launch_bounds__(RC_THREADS) void recurrence_mix_rows_kernel(
     }
 }
 
+// ---- the gold column's prior mass ---------------------------------------------------------------------------------------
+// One workgroup per row, the mix kernel's steps 1 and 2 and its reduction tree for W (the same operations in the same order:
+// W here is stats_w there, bit for bit), and beside them the gold partner's group [k, cut) -- contiguous, ascending in time,
+// three binary searches -- summed in the same strided shares through the same tree.  Two floats out per row, nothing else.
+__global__ __launch_bounds__(RC_THREADS) void recurrence_gold_rows_kernel(
+    const int32_t* __restrict__ q_ent, const int32_t* __restrict__ q_rel, const int32_t* __restrict__ q_t,
+    const int32_t* __restrict__ q_as_of, const int32_t* __restrict__ q_gold, const int32_t* __restrict__ p_rel,
+    const int32_t* __restrict__ p_other, const int32_t* __restrict__ p_t, int n_facts, const int32_t* __restrict__ ent_ptr,
+    const int32_t* __restrict__ snap_ptr, int n_snaps, int num_ent, int C, float inv_half_life, float* __restrict__ q_out,
+    float* __restrict__ w_out) {
+    __shared__ double s_w[RC_WAVES], s_g[RC_WAVES];
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int e = q_ent[row], r = q_rel[row], t = q_t[row], as_of = q_as_of[row], g = q_gold[row];
+    const double ihl = (double)inv_half_life;
+    int a, b;
+    rc_pair_run(p_rel, n_facts, ent_ptr, snap_ptr, n_snaps, num_ent, e, r, a, b);
+    double w_sum = 0.0;
+    for (int k = a + tid; k < b; k += RC_THREADS) {
+        const int tp = p_t[k];
+        if (tp >= as_of) continue;
+        w_sum += rc_weight(t, tp, ihl);
+    }
+    double g_sum = 0.0;
+    if (g >= 0 && g < C && a < b) {                                       // (uniform over the workgroup)
+        const int k0 = rc_lower(p_other, a, b, g);
+        const int cut = rc_lower(p_t, k0, rc_lower(p_other, k0, b, g + 1), as_of);
+        for (int j = k0 + tid; j < cut; j += RC_THREADS) g_sum += rc_weight(t, p_t[j], ihl);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        w_sum += __shfl_xor(w_sum, o);
+        g_sum += __shfl_xor(g_sum, o);
+    }
+    if (lane == 0) {
+        s_w[wave] = w_sum;
+        s_g[wave] = g_sum;
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    double W = 0.0, G = 0.0;
+#pragma unroll
+    for (int w = 0; w < RC_WAVES; ++w) {
+        W += s_w[w];
+        G += s_g[w];
+    }
+    w_out[row] = (float)W;
+    q_out[row] = W > 0.0 ? (float)(G / W) : 0.f;
+}
+
 inline int rc_blocks(long long n) { return (int)((n + RC_THREADS - 1) / RC_THREADS); }
 
 }  // namespace
@@ -351,21 +416,62 @@ extern "C" int renet_pair_append(const int32_t* p_rel, const int32_t* p_other, c
     return RENET_OK;
 }
 
-extern "C" int renet_recurrence_mix_rows(const int32_t* ent, const int32_t* rel, const int32_t* t, const int32_t* as_of, int n,
-                                         const int32_t* p_rel, const int32_t* p_other, const int32_t* p_t, int n_facts,
-                                         const int32_t* ent_ptr, const int32_t* snap_ptr, int n_snaps, int num_ent,
-                                         const float* logits, int ld, int C, float alpha, float inv_half_life, float* out,
-                                         int32_t* stats, float* stats_w, void* stream) {
+static int recurrence_mix_front(const int32_t* ent, const int32_t* rel, const int32_t* t, const int32_t* as_of, int n,
+                                const int32_t* p_rel, const int32_t* p_other, const int32_t* p_t, int n_facts,
+                                const int32_t* ent_ptr, const int32_t* snap_ptr, int n_snaps, int num_ent, const float* logits,
+                                int ld, int C, float alpha, const float* alpha_row, bool gated, float inv_half_life, float* out,
+                                int32_t* stats, float* stats_w, void* stream) {
     if (n < 0 || C < 1 || C > RENET_RECURRENCE_MAX_C || n_facts < 0 || n_snaps < 0 || num_ent < 0) return RENET_ERR_BADARG;
     if (!(alpha >= 0.f && alpha < 1.f) || !(inv_half_life >= 0.f) || !(inv_half_life <= FLT_MAX)) return RENET_ERR_BADARG;
     if (logits && ld < C) return RENET_ERR_BADARG;
     if ((stats == nullptr) != (stats_w == nullptr)) return RENET_ERR_BADARG;
     if (n == 0) return RENET_OK;
-    if (!ent || !rel || !t || !as_of || !out || !ent_ptr || !snap_ptr) return RENET_ERR_BADARG;
+    if (!ent || !rel || !t || !as_of || !out || !ent_ptr || !snap_ptr || (gated && !alpha_row)) return RENET_ERR_BADARG;
     if (n_facts > 0 && (!p_rel || !p_other || !p_t)) return RENET_ERR_BADARG;
-    RENET_LAUNCH(recurrence_mix_rows_kernel, dim3(n), dim3(RC_THREADS), 0, (hipStream_t)stream, ent, rel, t, as_of, p_rel,
-                 p_other, p_t, n_facts, ent_ptr, snap_ptr, n_snaps, num_ent, logits, ld, C, alpha, inv_half_life, out, stats,
-                 stats_w);
+    if (gated)
+        RENET_LAUNCH(recurrence_mix_rows_kernel<true>, dim3(n), dim3(RC_THREADS), 0, (hipStream_t)stream, ent, rel, t, as_of,
+                     p_rel, p_other, p_t, n_facts, ent_ptr, snap_ptr, n_snaps, num_ent, logits, ld, C, alpha, alpha_row,
+                     inv_half_life, out, stats, stats_w);
+    else
+        RENET_LAUNCH(recurrence_mix_rows_kernel<false>, dim3(n), dim3(RC_THREADS), 0, (hipStream_t)stream, ent, rel, t, as_of,
+                     p_rel, p_other, p_t, n_facts, ent_ptr, snap_ptr, n_snaps, num_ent, logits, ld, C, alpha, alpha_row,
+                     inv_half_life, out, stats, stats_w);
+    RENET_LAUNCH_CHECK();
+    return RENET_OK;
+}
+
+extern "C" int renet_recurrence_mix_rows(const int32_t* ent, const int32_t* rel, const int32_t* t, const int32_t* as_of, int n,
+                                         const int32_t* p_rel, const int32_t* p_other, const int32_t* p_t, int n_facts,
+                                         const int32_t* ent_ptr, const int32_t* snap_ptr, int n_snaps, int num_ent,
+                                         const float* logits, int ld, int C, float alpha, float inv_half_life, float* out,
+                                         int32_t* stats, float* stats_w, void* stream) {
+    return recurrence_mix_front(ent, rel, t, as_of, n, p_rel, p_other, p_t, n_facts, ent_ptr, snap_ptr, n_snaps, num_ent, logits,
+                                ld, C, alpha, nullptr, false, inv_half_life, out, stats, stats_w, stream);
+}
+
+// alpha_row is DEVICE memory: its range [0, 1) is the caller's to keep (renet_hip.recurrence_mix_rows_gated checks it where
+// the gate is built); a NaN or a gate >= 1 gives a non-finite row, never an address
+extern "C" int renet_recurrence_mix_rows_gated(const int32_t* ent, const int32_t* rel, const int32_t* t, const int32_t* as_of,
+                                               int n, const int32_t* p_rel, const int32_t* p_other, const int32_t* p_t,
+                                               int n_facts, const int32_t* ent_ptr, const int32_t* snap_ptr, int n_snaps,
+                                               int num_ent, const float* logits, int ld, int C, const float* alpha_row,
+                                               float inv_half_life, float* out, int32_t* stats, float* stats_w, void* stream) {
+    return recurrence_mix_front(ent, rel, t, as_of, n, p_rel, p_other, p_t, n_facts, ent_ptr, snap_ptr, n_snaps, num_ent, logits,
+                                ld, C, 0.f, alpha_row, true, inv_half_life, out, stats, stats_w, stream);
+}
+
+extern "C" int renet_recurrence_gold_rows(const int32_t* ent, const int32_t* rel, const int32_t* t, const int32_t* as_of,
+                                          const int32_t* gold, int n, const int32_t* p_rel, const int32_t* p_other,
+                                          const int32_t* p_t, int n_facts, const int32_t* ent_ptr, const int32_t* snap_ptr,
+                                          int n_snaps, int num_ent, int C, float inv_half_life, float* q, float* W,
+                                          void* stream) {
+    if (n < 0 || C < 1 || C > RENET_RECURRENCE_MAX_C || n_facts < 0 || n_snaps < 0 || num_ent < 0) return RENET_ERR_BADARG;
+    if (!(inv_half_life >= 0.f) || !(inv_half_life <= FLT_MAX)) return RENET_ERR_BADARG;
+    if (n == 0) return RENET_OK;
+    if (!ent || !rel || !t || !as_of || !gold || !q || !W || !ent_ptr || !snap_ptr) return RENET_ERR_BADARG;
+    if (n_facts > 0 && (!p_rel || !p_other || !p_t)) return RENET_ERR_BADARG;
+    RENET_LAUNCH(recurrence_gold_rows_kernel, dim3(n), dim3(RC_THREADS), 0, (hipStream_t)stream, ent, rel, t, as_of, gold, p_rel,
+                 p_other, p_t, n_facts, ent_ptr, snap_ptr, n_snaps, num_ent, C, inv_half_life, q, W);
     RENET_LAUNCH_CHECK();
     return RENET_OK;
 }

@@ -197,15 +197,43 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// ---- the loss through the copy mix (renet_mix_ce, renet_mix_ce_planes) ----------------------------------------------
+// With p = softmax(row), gold column g, gate a in [0, 1) and the prior's mass on the gold column q = w[g] / W:
+//     m = (1 - a) p_g + a q,   L = -log m,   dL/dlogits[c] = s (p_c - [c == g]),  s = (1 - a) p_g / m,   dL/da = (p_g - q) / m
+// -- the CE gradient times ONE scalar per row.  Every writer below has a MIX instance: its `false` instance is the kernel as
+// it was, its `true` instance takes the row's (a, q) once its maximum and sum exist and scales the row by grad_scale * s.
+// Where a == 0 or q == 0 the copy term adds nothing: s = 1 exactly (the CE gradient bit for bit), L = CE - log1p(-a), and
+// p_g -- which may have underflowed to 0 -- is not divided by.
+struct MixRow {
+    float loss, s, d_a;
+};
+__device__ __forceinline__ MixRow mix_row(float a, float q, float xt, float m, float sum, float grad_scale) {
+    const float pg = expf(xt - m) / sum;
+    MixRow o;
+    if (a == 0.f || q == 0.f) {
+        o.loss = (logf(sum) + m - xt) - log1pf(-a);
+        o.s = 1.f;
+        o.d_a = pg > 0.f ? grad_scale * (pg - q) / ((1.f - a) * pg) : 0.f;
+    } else {
+        const float mm = (1.f - a) * pg + a * q;
+        o.loss = -logf(mm);
+        o.s = (1.f - a) * pg / mm;
+        o.d_a = grad_scale * (pg - q) / mm;
+    }
+    return o;
+}
+
 // `dlogits` may ALIAS `logits` (the training path turns the logits into their gradient in place): neither pointer
 // may be __restrict__ -- with it hipcc is free to sink thread 0's read of x[target] below the barrier, past other
 // waves' stores to the same row (seen as a rare wrong LOSS with correct gradients).
 // dl16 (optional, instead of dlogits): the gradient as bf16 (RNE) into a matrix with row stride ld16 (elements), the
 // columns [C, C16) of every row written as zeros (C16 = C rounded up to 64: the k padding a bf16-storage GEMM reads).
+template <bool MIX>
 __global__ __launch_bounds__(256) void softmax_ce_kernel(const float* logits,
                                                          const int32_t* __restrict__ target, int C, int ld,
                                                          float grad_scale, float* __restrict__ row_loss,
-                                                         float* dlogits, __bf16* __restrict__ dl16, int ld16) {
+                                                         float* dlogits, __bf16* __restrict__ dl16, int ld16, const float* __restrict__ a_row,
+    const float* __restrict__ q_row, float* __restrict__ d_a) {
     __shared__ float red[4];
     const int b = blockIdx.x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -230,7 +258,16 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const float* logits,
     // wrong LOSS with correct gradients
     asm volatile("" : "+v"(xt) :: "memory");
     __syncthreads();
-    if (threadIdx.x == 0) row_loss[b] = logf(s) + m - xt;
+    if constexpr (MIX) {
+        const MixRow mx = mix_row(a_row[b], q_row[b], xt, m, s, grad_scale);
+        if (threadIdx.x == 0) {
+            row_loss[b] = mx.loss;
+            if (d_a) d_a[b] = mx.d_a;
+        }
+        grad_scale *= mx.s;
+    } else {
+        if (threadIdx.x == 0) row_loss[b] = logf(s) + m - xt;
+    }
     if (dlogits) {
         float* dx = dlogits + (size_t)b * ld;
         const float inv = 1.f / s;
@@ -254,11 +291,13 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const float* logits,
 // so the load of one row overlaps the exp / store of another (the LDS kernel below runs its phases back to back, one
 // row per CU at a time).  In place (dlogits == logits) is safe by construction: a thread reads all of its own columns
 // before it writes any, and nobody else touches them.
-template <int NQ>
+template <int NQ, bool MIX>
 __global__ __launch_bounds__(512, 4) void softmax_ce_reg_kernel(const float* logits, const int32_t* __restrict__ target,
                                                                 int C, int ld, float grad_scale,
-                                                                float* __restrict__ row_loss, float* dlogits) {
+                                                                float* __restrict__ row_loss, float* dlogits, const float* __restrict__ a_row,
+    const float* __restrict__ q_row, float* __restrict__ d_a) {
     __shared__ float red_m[8], red_s[8];
+    __shared__ float red_xt;                            // MIX: the gold logit, from its owner to the whole workgroup
     const int b = blockIdx.x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int t = target[b];
@@ -284,6 +323,9 @@ __global__ __launch_bounds__(512, 4) void softmax_ce_reg_kernel(const float* log
     }
     m = wave_max(m);
     if (lane == 0) red_m[wave] = m;
+    if constexpr (MIX) {
+        if (mine) red_xt = xt;
+    }
     __syncthreads();
     m = red_m[0];
 #pragma unroll
@@ -302,7 +344,16 @@ __global__ __launch_bounds__(512, 4) void softmax_ce_reg_kernel(const float* log
     s = 0.f;
 #pragma unroll
     for (int w = 0; w < 8; ++w) s += red_s[w];
-    if (mine) row_loss[b] = logf(s) + m - xt;                                   // the owner of column t
+    if constexpr (MIX) {
+        const MixRow mx = mix_row(a_row[b], q_row[b], red_xt, m, s, grad_scale);
+        if (mine) {
+            row_loss[b] = mx.loss;
+            if (d_a) d_a[b] = mx.d_a;
+        }
+        grad_scale *= mx.s;
+    } else {
+        if (mine) row_loss[b] = logf(s) + m - xt;                               // the owner of column t
+    }
     if (dlogits) {
         const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc(dlogits + (size_t)b * ld, (short)0, C * 4,
                                                                              0x00020000);
@@ -319,10 +370,12 @@ __global__ __launch_bounds__(512, 4) void softmax_ce_reg_kernel(const float* log
 // re-read the row from the fabric (all 1024 rows are in flight at once, 94 MB against 32 MB of L2); here the row is
 // read ONCE by 1024 threads (16 waves keep enough loads in flight for one workgroup per CU) and the max / sum / write
 // passes run out of LDS.
+template <bool MIX>
 __global__ __launch_bounds__(1024) void softmax_ce_lds_kernel(const float* logits,
                                                               const int32_t* __restrict__ target, int C, int ld,
                                                               float grad_scale, float* __restrict__ row_loss,
-                                                              float* dlogits, __bf16* __restrict__ dl16, int ld16) {
+                                                              float* dlogits, __bf16* __restrict__ dl16, int ld16, const float* __restrict__ a_row,
+    const float* __restrict__ q_row, float* __restrict__ d_a) {
     extern __shared__ float row[];
     __shared__ float red[16];
     const int b = blockIdx.x;
@@ -369,7 +422,16 @@ __global__ __launch_bounds__(1024) void softmax_ce_lds_kernel(const float* logit
     s = 0.f;
 #pragma unroll
     for (int w = 0; w < 16; ++w) s += red[w];
-    if (threadIdx.x == 0) row_loss[b] = logf(s) + m - xt;
+    if constexpr (MIX) {
+        const MixRow mx = mix_row(a_row[b], q_row[b], xt, m, s, grad_scale);
+        if (threadIdx.x == 0) {
+            row_loss[b] = mx.loss;
+            if (d_a) d_a[b] = mx.d_a;
+        }
+        grad_scale *= mx.s;
+    } else {
+        if (threadIdx.x == 0) row_loss[b] = logf(s) + m - xt;
+    }
     if (dlogits) {
         float* dx = dlogits + (size_t)b * ld;
         const float inv = 1.f / s;
@@ -423,12 +485,14 @@ __device__ __forceinline__ void split3_f4(float4 v, sq_u32x2 (&out)[3]) {
 constexpr int SP4_STRIDE = 144;                         // bytes between two tiles' 128-byte blocks in the staging buffer
 constexpr int SP4_PLANE = 128 * SP4_STRIDE;             // one plane of a slab
 
-template <int NQ4>
+template <int NQ4, bool MIX>
 __global__ __launch_bounds__(512) void softmax_ce_planes4_kernel(const float* __restrict__ logits,
                                                                  const int32_t* __restrict__ target, int B, int C, int ld,
                                                                  float grad_scale, float* __restrict__ row_loss,
-                                                                 __bf16* __restrict__ P, size_t plane, int ld16) {
+                                                                 __bf16* __restrict__ P, size_t plane, int ld16, const float* __restrict__ a_row,
+    const float* __restrict__ q_row, float* __restrict__ d_a) {
     __shared__ float red_m[8][4], red_s[8][4];
+    __shared__ float red_xt[4];                         // MIX: the gold logits, from their owners to the whole workgroup
     __shared__ __attribute__((aligned(16))) char stage[3 * SP4_PLANE];
     // block L -> XCD L & 7: the four quads of a tile row take consecutive slots of one XCD (see softmax_ce_planes_kernel)
     const int L = (int)blockIdx.x;
@@ -471,6 +535,9 @@ __global__ __launch_bounds__(512) void softmax_ce_planes4_kernel(const float* __
         }
         m[r] = wave_max(m[r]);
         if (lane == 0) red_m[wave][r] = m[r];
+        if constexpr (MIX) {
+            if (mine) red_xt[r] = xt[r];
+        }
     }
     __syncthreads();
     float s[4];
@@ -492,7 +559,7 @@ __global__ __launch_bounds__(512) void softmax_ce_planes4_kernel(const float* __
         if (lane == 0) red_s[wave][r] = acc;
     }
     __syncthreads();
-    float inv[4];
+    float inv[4], one[4];                               // (one: the gold column's share, grad_scale [* the row's mix scalar])
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         float acc = 0.f;
@@ -500,8 +567,19 @@ __global__ __launch_bounds__(512) void softmax_ce_planes4_kernel(const float* __
         for (int w = 0; w < 8; ++w) acc += red_s[w][r];
         s[r] = acc;
         const bool live = b0 + r < B;
-        if (live && tid == ((tgt[r] >> 2) & 511)) row_loss[b0 + r] = logf(acc) + m[r] - xt[r];
-        inv[r] = live ? grad_scale / acc : 0.f;         // (a dead row: zeros)
+        one[r] = grad_scale;
+        if constexpr (MIX) {
+            const int b = min(b0 + r, B - 1);
+            const MixRow mx = mix_row(a_row[b], q_row[b], red_xt[r], m[r], acc, grad_scale);
+            if (live && tid == ((tgt[r] >> 2) & 511)) {
+                row_loss[b0 + r] = mx.loss;
+                if (d_a) d_a[b0 + r] = mx.d_a;
+            }
+            one[r] = grad_scale * mx.s;
+        } else {
+            if (live && tid == ((tgt[r] >> 2) & 511)) row_loss[b0 + r] = logf(acc) + m[r] - xt[r];
+        }
+        inv[r] = live ? one[r] / acc : 0.f;             // (a dead row: zeros)
     }
     // store phase.  T16 (common.h): rows 4 quad + r of tile column tc are the 128-byte block (quad ^ (tc & 1)) of the tile,
     // row r at r * 32, its 8-column halves swapped when quad >= 2.
@@ -522,8 +600,8 @@ __global__ __launch_bounds__(512) void softmax_ce_planes4_kernel(const float* __
             const int tg = tgt[r] >> 2, tc = tgt[r] & 3;
             float4 o = make_float4(v[r][q].x * inv[r], v[r][q].y * inv[r], v[r][q].z * inv[r], v[r][q].w * inv[r]);
             if (tid == (tg & 511) && q == (tg >> 9) && b0 + r < B) {
-                const float one = grad_scale;
-                if (tc == 0) o.x -= one; else if (tc == 1) o.y -= one; else if (tc == 2) o.z -= one; else o.w -= one;
+                const float on = one[r];
+                if (tc == 0) o.x -= on; else if (tc == 1) o.y -= on; else if (tc == 2) o.z -= on; else o.w -= on;
             }
             sq_u32x2 pk[3];
             split3_f4(o, pk);
@@ -639,10 +717,12 @@ __global__ __launch_bounds__(512, 4) void softmax_ce_planes_kernel(const float* 
 }
 
 // any width / alignment: three passes over the row (the structure of softmax_ce_kernel), planes out
+template <bool MIX>
 __global__ __launch_bounds__(256) void softmax_ce_planes_generic_kernel(const float* __restrict__ logits,
                                                                         const int32_t* __restrict__ target, int C, int ld,
                                                                         float grad_scale, float* __restrict__ row_loss,
-                                                                        __bf16* __restrict__ P, size_t plane, int ld16) {
+                                                                        __bf16* __restrict__ P, size_t plane, int ld16, const float* __restrict__ a_row,
+    const float* __restrict__ q_row, float* __restrict__ d_a) {
     __shared__ float red[4];
     const int b = blockIdx.x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -661,7 +741,16 @@ __global__ __launch_bounds__(256) void softmax_ce_planes_generic_kernel(const fl
     __syncthreads();
     s = (red[0] + red[1]) + (red[2] + red[3]);
     const int t = target[b];
-    if (threadIdx.x == 0) row_loss[b] = logf(s) + m - x[t];
+    if constexpr (MIX) {
+        const MixRow mx = mix_row(a_row[b], q_row[b], x[t], m, s, grad_scale);
+        if (threadIdx.x == 0) {
+            row_loss[b] = mx.loss;
+            if (d_a) d_a[b] = mx.d_a;
+        }
+        grad_scale *= mx.s;
+    } else {
+        if (threadIdx.x == 0) row_loss[b] = logf(s) + m - x[t];
+    }
     const float inv = 1.f / s;
     const int tcn = ld16 >> 4;
     for (int c = threadIdx.x; c < ld16; c += 256) {
@@ -898,10 +987,22 @@ int renet_dropout(const float* x, size_t n, float drop_p, uint64_t seed, float* 
 
 static int softmax_ce_impl(const float* logits, const int32_t* target, int B, int C, int ld, float grad_scale,
                            float* row_loss, float* dlogits, __bf16* dl16, int ld16, void* stream);
+extern "C++" {
+template <bool MIX>
+static int softmax_ce_front(const float* logits, const int32_t* target, int B, int C, int ld, float grad_scale,
+                            float* row_loss, float* dlogits, __bf16* dl16, int ld16, const float* a_row, const float* q_row,
+                            float* d_a, void* stream);
+}
 
 int renet_softmax_ce(const float* logits, const int32_t* target, int B, int C, int ld,
                      float grad_scale, float* row_loss, float* dlogits, void* stream) {
     return softmax_ce_impl(logits, target, B, C, ld, grad_scale, row_loss, dlogits, nullptr, 0, stream);
+}
+
+int renet_mix_ce(const float* logits, const int32_t* target, const float* a_row, const float* q_row, int B, int C, int ld,
+                 float grad_scale, float* row_loss, float* dlogits, float* d_a, void* stream) {
+    if (!logits || !target || !a_row || !q_row || !row_loss) return RENET_ERR_BADARG;
+    return softmax_ce_front<true>(logits, target, B, C, ld, grad_scale, row_loss, dlogits, nullptr, 0, a_row, q_row, d_a, stream);
 }
 
 int renet_softmax_ce_bf16(const float* logits, const int32_t* target, int B, int C, int ld, float grad_scale,
@@ -918,35 +1019,47 @@ int renet_softmax_ce_bf16(const float* logits, const int32_t* target, int B, int
 
 static int softmax_ce_impl(const float* logits, const int32_t* target, int B, int C, int ld, float grad_scale,
                            float* row_loss, float* dlogits, __bf16* dl16, int ld16, void* stream) {
+    return softmax_ce_front<false>(logits, target, B, C, ld, grad_scale, row_loss, dlogits, dl16, ld16, nullptr, nullptr,
+                                   nullptr, stream);
+}
+
+extern "C++" {
+// one choice of kernel for the CE and for the loss through the mix: the MIX instance of the kernel the CE would take
+template <bool MIX>
+static int softmax_ce_front(const float* logits, const int32_t* target, int B, int C, int ld, float grad_scale,
+                            float* row_loss, float* dlogits, __bf16* dl16, int ld16, const float* a_row, const float* q_row,
+                            float* d_a, void* stream) {
     if (B < 0 || C <= 0 || ld < C) return RENET_ERR_BADARG;
     if (B == 0) return RENET_OK;
     const size_t lds = (size_t)C * sizeof(float);
     if (!dl16 && C >= 4096 && C <= 48 * 512) {
         const dim3 grid(B), blk(512);
         hipStream_t st = (hipStream_t)stream;
-        if (C <= 16 * 512) RENET_LAUNCH((softmax_ce_reg_kernel<16>), grid, blk, 0, st, logits, target, C, ld, grad_scale, row_loss, dlogits);
-        else if (C <= 32 * 512) RENET_LAUNCH((softmax_ce_reg_kernel<32>), grid, blk, 0, st, logits, target, C, ld, grad_scale, row_loss, dlogits);
-        else RENET_LAUNCH((softmax_ce_reg_kernel<48>), grid, blk, 0, st, logits, target, C, ld, grad_scale, row_loss, dlogits);
+        if (C <= 16 * 512) RENET_LAUNCH((softmax_ce_reg_kernel<16, MIX>), grid, blk, 0, st, logits, target, C, ld, grad_scale, row_loss, dlogits, a_row, q_row, d_a);
+        else if (C <= 32 * 512) RENET_LAUNCH((softmax_ce_reg_kernel<32, MIX>), grid, blk, 0, st, logits, target, C, ld, grad_scale, row_loss, dlogits, a_row, q_row, d_a);
+        else RENET_LAUNCH((softmax_ce_reg_kernel<48, MIX>), grid, blk, 0, st, logits, target, C, ld, grad_scale, row_loss, dlogits, a_row, q_row, d_a);
     } else if (lds <= 128 * 1024 && C >= 4096) {
         static bool attr_set = false;      // benign race: the attribute is idempotent
         if (!attr_set) {
-            hipError_t e = hipFuncSetAttribute((const void*)softmax_ce_lds_kernel,
+            hipError_t e = hipFuncSetAttribute((const void*)softmax_ce_lds_kernel<MIX>,
                                                hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
             if (e != hipSuccess) return (int)e;
             attr_set = true;
         }
-        RENET_LAUNCH(softmax_ce_lds_kernel, dim3(B), dim3(1024), lds, (hipStream_t)stream, logits, target, C, ld,
-                     grad_scale, row_loss, dlogits, dl16, ld16);
+        RENET_LAUNCH(softmax_ce_lds_kernel<MIX>, dim3(B), dim3(1024), lds, (hipStream_t)stream, logits, target, C, ld,
+                     grad_scale, row_loss, dlogits, dl16, ld16, a_row, q_row, d_a);
     } else {
-        RENET_LAUNCH(softmax_ce_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, logits, target, C, ld,
-                     grad_scale, row_loss, dlogits, dl16, ld16);
+        RENET_LAUNCH(softmax_ce_kernel<MIX>, dim3(B), dim3(256), 0, (hipStream_t)stream, logits, target, C, ld,
+                     grad_scale, row_loss, dlogits, dl16, ld16, a_row, q_row, d_a);
     }
     RENET_LAUNCH_CHECK();
     return RENET_OK;
 }
 
-int renet_softmax_ce_planes(const float* logits, const int32_t* target, int B, int C, int ld, float grad_scale,
-                            float* row_loss, void* dl_planes, size_t plane, int ld16, int rows16, void* stream) {
+template <bool MIX>
+static int softmax_ce_planes_front(const float* logits, const int32_t* target, int B, int C, int ld, float grad_scale,
+                                   float* row_loss, void* dl_planes, size_t plane, int ld16, int rows16, const float* a_row,
+                                   const float* q_row, float* d_a, void* stream) {
     if (B < 0 || C <= 0 || ld < C || !dl_planes || ld16 < C || (ld16 & 15) || rows16 < ((B + 15) & ~15)) return RENET_ERR_BADARG;
     if (plane < (size_t)rows16 * ld16) return RENET_ERR_BADARG;
     if (B == 0) return RENET_OK;
@@ -963,26 +1076,43 @@ int renet_softmax_ce_planes(const float* logits, const int32_t* target, int B, i
     }
     const bool aligned = (ld & 3) == 0 && (reinterpret_cast<uintptr_t>(logits) & 15) == 0 &&
                          (reinterpret_cast<uintptr_t>(dl_planes) & 7) == 0 && (plane & 3) == 0;
-    // RENET_SOFTMAX_ROWS=1: one row per workgroup (the first planes writer), for A/B runs
-    static const bool rows4 = !renet_env_flag("RENET_SOFTMAX_ROWS", false);
+    // RENET_SOFTMAX_ROWS=1: one row per workgroup (the first planes writer), for A/B runs; it has no mix form, the mix
+    // entry does not read the switch
+    static const bool rows4 = MIX || !renet_env_flag("RENET_SOFTMAX_ROWS", false);
     if (aligned && rows4 && C >= 2048 && ld16 <= 12 * 2048 && (reinterpret_cast<uintptr_t>(dl_planes) & 15) == 0 &&
         (plane & 7) == 0) {
         const int quads = (B + 3) / 4;
         const dim3 grid((unsigned)((quads + 31) & ~31)), blk(512);   // whole groups of 8 XCDs x 4 quads
-        if (ld16 <= 4 * 2048) RENET_LAUNCH((softmax_ce_planes4_kernel<4>), grid, blk, 0, st, logits, target, B, C, ld, grad_scale, row_loss, P, plane, ld16);
-        else if (ld16 <= 8 * 2048) RENET_LAUNCH((softmax_ce_planes4_kernel<8>), grid, blk, 0, st, logits, target, B, C, ld, grad_scale, row_loss, P, plane, ld16);
-        else RENET_LAUNCH((softmax_ce_planes4_kernel<12>), grid, blk, 0, st, logits, target, B, C, ld, grad_scale, row_loss, P, plane, ld16);
-    } else if (aligned && C >= 2048 && ld16 <= 12 * 2048) {
+        if (ld16 <= 4 * 2048) RENET_LAUNCH((softmax_ce_planes4_kernel<4, MIX>), grid, blk, 0, st, logits, target, B, C, ld, grad_scale, row_loss, P, plane, ld16, a_row, q_row, d_a);
+        else if (ld16 <= 8 * 2048) RENET_LAUNCH((softmax_ce_planes4_kernel<8, MIX>), grid, blk, 0, st, logits, target, B, C, ld, grad_scale, row_loss, P, plane, ld16, a_row, q_row, d_a);
+        else RENET_LAUNCH((softmax_ce_planes4_kernel<12, MIX>), grid, blk, 0, st, logits, target, B, C, ld, grad_scale, row_loss, P, plane, ld16, a_row, q_row, d_a);
+    } else if (!MIX && aligned && C >= 2048 && ld16 <= 12 * 2048) {
         const dim3 grid((unsigned)((B + 127) & ~127)), blk(512);     // whole groups of 8 XCDs x 16 rows (see the kernel)
         if (ld16 <= 4 * 2048) RENET_LAUNCH((softmax_ce_planes_kernel<4>), grid, blk, 0, st, logits, target, B, C, ld, grad_scale, row_loss, P, plane, ld16);
         else if (ld16 <= 8 * 2048) RENET_LAUNCH((softmax_ce_planes_kernel<8>), grid, blk, 0, st, logits, target, B, C, ld, grad_scale, row_loss, P, plane, ld16);
         else RENET_LAUNCH((softmax_ce_planes_kernel<12>), grid, blk, 0, st, logits, target, B, C, ld, grad_scale, row_loss, P, plane, ld16);
     } else {
-        RENET_LAUNCH(softmax_ce_planes_generic_kernel, dim3(B), dim3(256), 0, st, logits, target, C, ld, grad_scale,
-                     row_loss, P, plane, ld16);
+        RENET_LAUNCH(softmax_ce_planes_generic_kernel<MIX>, dim3(B), dim3(256), 0, st, logits, target, C, ld, grad_scale,
+                     row_loss, P, plane, ld16, a_row, q_row, d_a);
     }
     RENET_LAUNCH_CHECK();
     return RENET_OK;
+}
+
+}  // extern "C++"
+
+int renet_softmax_ce_planes(const float* logits, const int32_t* target, int B, int C, int ld, float grad_scale,
+                            float* row_loss, void* dl_planes, size_t plane, int ld16, int rows16, void* stream) {
+    return softmax_ce_planes_front<false>(logits, target, B, C, ld, grad_scale, row_loss, dl_planes, plane, ld16, rows16,
+                                          nullptr, nullptr, nullptr, stream);
+}
+
+int renet_mix_ce_planes(const float* logits, const int32_t* target, const float* a_row, const float* q_row, int B, int C,
+                        int ld, float grad_scale, float* row_loss, void* dl_planes, size_t plane, int ld16, int rows16,
+                        float* d_a, void* stream) {
+    if (!logits || !target || !a_row || !q_row || !row_loss) return RENET_ERR_BADARG;
+    return softmax_ce_planes_front<true>(logits, target, B, C, ld, grad_scale, row_loss, dl_planes, plane, ld16, rows16, a_row,
+                                         q_row, d_a, stream);
 }
 
 int renet_zero(float* x, size_t n, void* stream) {

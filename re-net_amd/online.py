@@ -83,7 +83,7 @@ def _train_step(module, optimizer, loss_fn, grad_norm, head_passes=1):
 
 
 # ---- RENet.learn_observed ----------------------------------------------------------------------------------------------
-def _learn_observed(self, obs, idx, optimizer, steps=1, batch_size=1024, grad_norm=1.0):
+def _learn_observed(self, obs, idx, optimizer, steps=1, batch_size=1024, grad_norm=1.0, prior=None, gate_optimizer=None):
     """Training steps on the stream positions idx of a resident stream (preprocess.ObservedStream after resident() /
     observe(), or its gpu_builder.ObservedStore): the positions are cut into batches of batch_size <= gpu_builder.MAX_BOTH in
     the given order, and each batch is ONE merged two-direction step in train mode -- prepare_both_device ->
@@ -91,8 +91,22 @@ def _learn_observed(self, obs, idx, optimizer, steps=1, batch_size=1024, grad_no
     backward -> optimizer -- under the true histories of the stream, with the stream's own global-embedding table.  `steps`
     passes over the batches.  optimizer: a parallel.HipAdam of this model, or any torch.optim.Optimizer over its parameters
     (clip_grad_norm_(grad_norm), step(), zero_grad()).  The model's train / eval mode is restored afterwards.
-    -> the batch losses (Python floats, steps * ceil(len(idx) / batch_size) of them; read back once, at the end)."""
+    -> the batch losses (Python floats, steps * ceil(len(idx) / batch_size) of them; read back once, at the end).
+    prior (None: today's path, launch for launch): the entity head's loss goes THROUGH THE COPY MIX of the recurrence prior
+    (recurrence.CopyRows of each batch, loss_prepared_both(prep, copy=)), the weights learn what the copy term does not
+    explain, and the losses returned are the mixed ones.  A recurrence.RecurrencePrior is a fixed mix; a recurrence.CopyGate
+    with a gate_optimizer (any torch.optim over gate.parameters()) learns its gates in the same step -- their gradients stay
+    out of the model's clip norm.  A step with a prior is not in the C launch list: it pays the autograd path's host enqueue."""
     import gpu_builder
+    if prior is not None:
+        import recurrence
+        recurrence._checked(prior)
+        if gate_optimizer is not None and not isinstance(prior, recurrence.CopyGate):
+            raise ValueError('learn_observed: gate_optimizer needs prior= to be a recurrence.CopyGate')
+        if getattr(self, 'gemm_mode', None) == 'bf16s' or K.current_mode() == 'bf16s':
+            raise ValueError('learn_observed: prior= has no bf16-storage writer: use another GEMM mode')
+    elif gate_optimizer is not None:
+        raise ValueError('learn_observed: gate_optimizer without prior=')
     store = M._observed_store(obs)
     idx = M._observed_positions(store, idx)
     batch_size, steps = int(batch_size), int(steps)
@@ -111,7 +125,16 @@ def _learn_observed(self, obs, idx, optimizer, steps=1, batch_size=1024, grad_no
                 if prep.g.S == 0:
                     raise ValueError('learn_observed: no position of the batch has a history (the first timestamp of a '
                                      'stream): nothing to encode')
-                losses.append(_train_step(self, optimizer, lambda: self.loss_prepared_both(prep), grad_norm))
+                if prior is None:
+                    losses.append(_train_step(self, optimizer, lambda: self.loss_prepared_both(prep), grad_norm))
+                    continue
+                if gate_optimizer is not None:
+                    gate_optimizer.zero_grad()
+                rows = recurrence.CopyRows(store, part, prior)
+                losses.append(_train_step(self, optimizer, lambda: self.loss_prepared_both(prep, copy=rows), grad_norm))
+                if gate_optimizer is not None:
+                    gate_optimizer.step()
+                    gate_optimizer.zero_grad()
     finally:
         self.train(was_training)
     return [float(x) for x in torch.stack(losses).cpu()] if losses else []
@@ -227,7 +250,7 @@ def refresh_global(stream, global_model):
 
 # ---- RENet.evaluate_online ---------------------------------------------------------------------------------------------
 def _evaluate_online(self, obs, quads, global_model, optimizer, steps=1, replay=0, global_optimizer=None, all_triplets=None,
-                     max_batch=4096, batch_size=1024, grad_norm=1.0, prior=None):
+                     max_batch=4096, batch_size=1024, grad_norm=1.0, prior=None, learn_prior=False, gate_optimizer=None):
     """The forecast / observe / LEARN loop over the labelled, time-sorted quads on the resident stream obs (ending before
     quads[0, 3]).  Per timestamp t of quads, in this order: (1) its facts are ranked with evaluate_forecast on the stream as
     it stands -- nothing of t has been seen, by the stream or by the weights; (2) they are observed (ObservedStream.observe);
@@ -240,7 +263,12 @@ def _evaluate_online(self, obs, quads, global_model, optimizer, steps=1, replay=
     for bit.  all_triplets: as there.  These are ONLINE numbers -- a protocol of their own, not comparable with the static
     single-step, stale-horizon, rollout or multi-step ones.
     prior: a recurrence.RecurrencePrior for the forecast half (evaluate_forecast's keyword); the pair tables it reads are
-    built at the first timestamp and ride through observe() by the device append.  Learning is not touched by it."""
+    built at the first timestamp and ride through observe() by the device append.  Learning is not touched by it unless
+    learn_prior=True: then prior and gate_optimizer are passed on to learn_observed -- the steps train through the mix, and a
+    recurrence.CopyGate with a gate_optimizer learns its gates along the stream (the gate that ranks timestamp t was fitted on
+    the timestamps before t: ONLINE numbers WITH A LEARNED GATE, comparable only with numbers of the same protocol)."""
+    if (learn_prior and prior is None) or (gate_optimizer is not None and not learn_prior):
+        raise ValueError('evaluate_online: learn_prior=True needs prior=, and gate_optimizer needs learn_prior=True')
     store = M._observed_store(obs)
     cur = getattr(store, 'obs', None)
     if cur is None or not hasattr(cur, 'observe'):
@@ -275,7 +303,8 @@ def _evaluate_online(self, obs, quads, global_model, optimizer, steps=1, replay=
                 ts = cur.times
                 a = int(np.searchsorted(cur.allq[:, 3], ts[max(0, len(ts) - 1 - replay)]))
                 pos = np.concatenate((np.arange(n0, len(cur)), np.arange(a, n0)))
-                entry['losses'] = _learn_observed(self, cur, pos, optimizer, steps, batch_size, grad_norm)
+                entry['losses'] = _learn_observed(self, cur, pos, optimizer, steps, batch_size, grad_norm,
+                                                  prior if learn_prior else None, gate_optimizer if learn_prior else None)
             if global_optimizer is not None:
                 entry['global_loss'] = global_model.learn_observed(cur, [int(t)], global_optimizer, grad_norm=grad_norm)
                 cur = cur.refresh_global(global_model)

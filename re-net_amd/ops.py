@@ -644,9 +644,14 @@ def dual_gru(x, xr, enc, enc_r, step_off, total_rows):
                             xr, enc_r.weight_ih_l0, enc_r.weight_hh_l0, enc_r.bias_ih_l0, enc_r.bias_hh_l0)
 
 
-def _head_forward(a, ia, hmid, c, ic, weight, bias, target, drop_p, seed, grad_scale, need_grad, row_loss=None):
+def _head_forward(a, ia, hmid, c, ic, weight, bias, target, drop_p, seed, grad_scale, need_grad, row_loss=None, copy=None):
     """One score head up to the per-row losses: [a[ia] | hmid | c[ic]] -> dropout -> Linear -> CE.
-    -> (row_loss[B], feat, logits-or-gradient buffer, bf16 / planes gradient matrix or None, operand handle of feat or None)"""
+    -> (row_loss[B], feat, logits-or-gradient buffer, bf16 / planes gradient matrix or None, operand handle of feat or None,
+    d_a or None).  copy = (a_row, q_row), fp32 device [B]: the loss goes THROUGH THE COPY MIX of the recurrence prior,
+    row_loss = -log((1 - a) softmax[gold] + a q) (K.mix_ce_planes / K.mix_ce in the CE's place: the same gradient buffers,
+    every row scaled by its s <= 1, so the f16x3 bound grad_scale stays valid) and d_a[B] = grad_scale * d row_loss / d a."""
+    if copy is not None and K.current_mode() == 'bf16s':
+        raise ValueError('the loss through the copy mix has no bf16-storage writer: use another GEMM mode with copy=')
     feat = K.concat3_fwd(a, ia, hmid, c, ic, drop_p, seed)
     if need_grad and debug_tap is None and K.use_planes(weight, weight.shape[0]):
         # PLANES path (round 6, the entity head): every operand of the head's three GEMMs is split into its bf16 terms ONCE
@@ -661,20 +666,26 @@ def _head_forward(a, ia, hmid, c, ic, weight, bias, target, drop_p, seed, grad_s
         # planes and add exactly 0)
         feat_pl1 = K.pack_planes(feat, ones_col=True)
         K.gemm_planes(K.PlanesMat(feat_pl1.p, feat_pl1.R, feat_pl1.C - 1), w_pl, tb=True, bias=bias, out=logits)
-        row_loss, dl_pl = K.softmax_ce_planes(logits, target, grad_scale, row_loss=row_loss)
-        return row_loss, feat, feat.new_empty(0), dl_pl, feat_pl1
+        d_a = None
+        if copy is None:
+            row_loss, dl_pl = K.softmax_ce_planes(logits, target, grad_scale, row_loss=row_loss)
+        else:
+            row_loss, dl_pl, d_a = K.mix_ce_planes(logits, target, copy[0], copy[1], grad_scale, row_loss=row_loss)
+        return row_loss, feat, feat.new_empty(0), dl_pl, feat_pl1, d_a
     feat_op = K.operand(feat)                                        # (bf16 mode: packed once, reused by dW)
     logits = K.gemm(feat_op, weight, tb=True, bias=bias)             # [B, C]
     if debug_tap is not None:
         debug_tap('logits', logits)
-    dl_bf16 = None
-    if need_grad and K.current_mode() == 'bf16s':
+    dl_bf16 = d_a = None
+    if copy is not None:
+        row_loss, d_a = K.mix_ce(logits, target, copy[0], copy[1], grad_scale, need_grad, row_loss=row_loss)
+    elif need_grad and K.current_mode() == 'bf16s':
         # bf16-storage mode: the gradient is written as a bf16 operand matrix, the fp32 logits are dropped
         row_loss, dl_bf16 = K.softmax_ce_bf16(logits, target, grad_scale, row_loss=row_loss)
         logits = feat.new_empty(0)
     else:
         row_loss = K.softmax_ce(logits, target, grad_scale, need_grad, row_loss=row_loss)
-    return row_loss, feat, logits, dl_bf16, (feat_op if K.is_handle(feat_op) else None)
+    return row_loss, feat, logits, dl_bf16, (feat_op if K.is_handle(feat_op) else None), d_a
 
 
 def _scale_ce_gradient(dlogits, g, grad_scale):
@@ -739,8 +750,12 @@ class HeadCEFn(Function):
 
     @staticmethod
     @_fwd_mode
-    def forward(ctx, a, ia, hmid, c, ic, weight, bias, target, plan_a, plan_c, drop_p, seed, loss_scale=1.0):
+    def forward(ctx, a, ia, hmid, c, ic, weight, bias, target, plan_a, plan_c, drop_p, seed, loss_scale=1.0, copy_a=None,
+                copy_q=None):
+        """copy_a / copy_q (both or neither; fp32 [B]): the loss through the copy mix (see _head_forward); copy_a may
+        require grad -- a learned gate -- and receives g * d_a.  Neither: today's path, launch for launch."""
         ctx.srcs = (a, c, weight, bias)
+        copy = _copy_pair(copy_a, copy_q, hmid.shape[0])
         a, hmid, weight, bias = _c(a), _c(hmid), _c(weight), _c(bias)
         c = _c(c) if c is not None else None
         b, d = hmid.shape
@@ -748,8 +763,8 @@ class HeadCEFn(Function):
         # loss_scale (2 for the merged batch of both passes: sum of two B-row means = 2 x the 2B-row mean) goes into
         # the gradient the CE kernel writes, so that the upstream scalar stays 1 and the 188 MB are not rescaled
         ctx.grad_scale = float(loss_scale) / b
-        row_loss, feat, logits, ctx.dl_bf16, feat_op = _head_forward(a, ia, hmid, c, ic, weight, bias, target, drop_p,
-                                                                     seed, ctx.grad_scale, need_grad)
+        row_loss, feat, logits, ctx.dl_bf16, feat_op, ctx.d_gate = _head_forward(
+            a, ia, hmid, c, ic, weight, bias, target, drop_p, seed, ctx.grad_scale, need_grad, copy=copy)
         ctx.meta = (d, 3 if c is not None else 2, drop_p, seed, plan_a, plan_c, a.shape,
                     c.shape if c is not None else None)
         if need_grad:
@@ -778,7 +793,20 @@ class HeadCEFn(Function):
             grad_done(ctx.srcs[3])
         da_rows, dh, dc_rows = K.concat3_bwd(dfeat, d, parts, drop_p, seed)
         d_a, d_c = _scatter_head_rows(da_rows, dc_rows, plan_a, plan_c, t_a, t_c, a_shape, c_shape)
-        return d_a, None, dh, d_c, None, d_w, d_b, None, None, None, None, None, None
+        # (the per-row d_a is not scaled in place like the big buffer: nothing of it is consumed)
+        d_gate = ctx.d_gate * g if ctx.d_gate is not None and ctx.needs_input_grad[13] else None
+        return d_a, None, dh, d_c, None, d_w, d_b, None, None, None, None, None, None, d_gate, None
+
+
+def _copy_pair(copy_a, copy_q, b):
+    if copy_a is None and copy_q is None:
+        return None
+    if copy_a is None or copy_q is None:
+        raise ValueError('the copy mix takes both a_row and q_row')
+    pair = tuple(t.detach().contiguous() for t in (copy_a, copy_q))
+    if any(t.dtype != torch.float32 or t.numel() != b for t in pair):
+        raise ValueError('a_row and q_row must be float32 with one entry per row of the head')
+    return pair
 
 
 _loss_weights = {}
@@ -807,10 +835,12 @@ class DualHeadCEFn(Function):
     @staticmethod
     @_fwd_mode
     def forward(ctx, a, ia, h1, c, ic, w1, b1, target1, h2, w2, b2, target2, plan_a, plan_c, drop_p, seed1, seed2,
-                loss_scale=1.0, rel_weight=0.1, row_tap=None):
+                loss_scale=1.0, rel_weight=0.1, row_tap=None, copy_a=None, copy_q=None):
         """row_tap: a list that receives (row losses [2b]: entity head rows then relation head rows, s1, s2) -- the weights
-        with which the returned scalar sums them (RENet.forward's fused directions split the merged loss by direction)."""
+        with which the returned scalar sums them (RENet.forward's fused directions split the merged loss by direction).
+        copy_a / copy_q: as for HeadCEFn, for the ENTITY head only; the relation head is the plain CE."""
         ctx.srcs = (a, c, w1, b1, w2, b2)
+        copy = _copy_pair(copy_a, copy_q, h1.shape[0])
         a, h1, h2, c, w1, b1, w2, b2 = (_c(t) for t in (a, h1, h2, c, w1, b1, w2, b2))
         b, d = h1.shape
         need_grad = any(ctx.needs_input_grad)
@@ -821,11 +851,11 @@ class DualHeadCEFn(Function):
         sd = _Side(h1.device)
         if debug_tap is None:
             with sd():
-                _, feat2, lg2, dl2, fop2 = head2()
-        _, feat1, lg1, dl1, fop1 = _head_forward(a, ia, h1, c, ic, w1, b1, target1, drop_p, seed1, s1, need_grad,
-                                                 row_loss=rl[:b])
+                _, feat2, lg2, dl2, fop2, _ = head2()
+        _, feat1, lg1, dl1, fop1, ctx.d_gate = _head_forward(a, ia, h1, c, ic, w1, b1, target1, drop_p, seed1, s1, need_grad,
+                                                             row_loss=rl[:b], copy=copy)
         if debug_tap is not None:                            # test hook: the entity head reports first
-            _, feat2, lg2, dl2, fop2 = head2()
+            _, feat2, lg2, dl2, fop2, _ = head2()
         sd.join()
         ctx.meta = (d, drop_p, seed1, seed2, plan_a, plan_c, a.shape, c.shape)
         ctx.grad_scales = (s1, s2)
@@ -867,7 +897,8 @@ class DualHeadCEFn(Function):
             grad_done(ctx.srcs[5])
         da1.add_(da2)                                        # same rows ent[s] in both heads: one scatter-add
         d_a, d_c = _scatter_head_rows(da1, dc1, plan_a, plan_c, t_a, t_c, a_shape, c_shape)
-        return (d_a, None, dh1, d_c, None, d_w1, d_b1, None, dh2, d_w2, d_b2, None) + (None,) * 8
+        d_gate = ctx.d_gate * g if ctx.d_gate is not None and ctx.needs_input_grad[20] else None
+        return (d_a, None, dh1, d_c, None, d_w1, d_b1, None, dh2, d_w2, d_b2, None) + (None,) * 8 + (d_gate, None)
 
 
 class SegmentPoolFn(Function):

@@ -16,13 +16,27 @@ query gets a stale prior, nothing at or after as_of is read.  alpha = 0 is log_s
 unmixed ones except where the subtraction of the row's logsumexp rounds two logits together.
 
 The statistic is read from the resident PAIR TABLES (gpu_builder.ObservedStore.pair_tables; host statement
-preprocess.PairIndex), built on first use and carried through ObservedStream.observe() by renet_pair_append.  Not covered:
-rollout (generated facts in a prior are a protocol question of their own), the joint event paths, a relation-free term,
-fitting alpha."""
+preprocess.PairIndex), built on first use and carried through ObservedStream.observe() by renet_pair_append.
+
+TRAINING through the mix.  A CopyGate is the learned form of the prior: one gate per (side, relation), a = sigmoid(logit),
+accepted wherever `prior=` is (one renet_recurrence_mix_rows_gated launch in the scalar entry's place).  For a row with gold
+column g, p = softmax(logits), q = w[g] / W and m = (1 - a) p_g + a q, the loss L = -log m has
+    dL/dlogits[c] = s (p_c - [c == g]),  s = (1 - a) p_g / m in [0, 1],      dL/da = (p_g - q) / m
+-- the CE gradient times one scalar per row, and of the prior only the gold column's mass: CopyRows gathers (a, q, W) of a
+merged training batch with two renet_recurrence_gold_rows launches, RENet.loss_prepared_both(prep, copy=) and
+RENet.learn_observed(..., prior=, gate_optimizer=) train the model (and the gate) through the mix, fit_gate fits the gate
+alone.  A step with copy= is not in the C launch list (csrc/step.cpp): it pays the autograd path's host enqueue.  Numbers
+with a LEARNED gate are a protocol of their own: comparable only with numbers of the same protocol and the same fitting data.
+
+Not covered: rollout (generated facts in a prior are a protocol question of their own), the joint event paths, a
+relation-free term, a learned half-life, bf16-storage mode, data-parallel gate gradients."""
+import math
+
 import numpy as np
 import torch
 
 import filter_index as FI
+import graph as G
 import renet_hip as K
 
 SETTINGS = ('raw', 'filtered', 'time_filtered')
@@ -46,6 +60,122 @@ class RecurrencePrior(object):
 
     def __repr__(self):
         return 'RecurrencePrior(alpha=%g, half_life=%r)' % (self.alpha, self.half_life)
+
+
+class _GateRowsFn(torch.autograd.Function):
+    """out[i] = table[index[i]] for the flat gate table [T]; backward: the rows' gradients summed per gate by the project's
+    segmented add over a plan sorted by (side, relation) -- a fixed order, no floating-point atomics, the same bits from run
+    to run (index_add_ gives neither)."""
+
+    @staticmethod
+    def forward(ctx, table, index, plan):
+        ctx.plan, ctx.size = plan, table.numel()
+        return table[index]
+
+    @staticmethod
+    def backward(ctx, g):
+        src = torch.zeros(g.numel(), 4, device=g.device, dtype=torch.float32)      # (the segmented add takes float4 rows)
+        src[:, 0] = g
+        dst = torch.zeros(ctx.size, 4, device=g.device, dtype=torch.float32)
+        K.segment_add(src, ctx.plan, dst)
+        return dst[:, 0].contiguous(), None, None
+
+
+class _PermuteFn(torch.autograd.Function):
+    """out = x[perm] for a PERMUTATION perm; backward scatters without accumulation: one writer per element."""
+
+    @staticmethod
+    def forward(ctx, x, perm):
+        ctx.perm = perm
+        return x[perm]
+
+    @staticmethod
+    def backward(ctx, g):
+        out = torch.empty_like(g)
+        out[ctx.perm] = g
+        return out, None
+
+
+A_MAX = 1.0 - 2.0 ** -24                  # the largest fp32 below 1: a gate never reaches 1, whatever its logit
+
+
+class CopyGate(torch.nn.Module):
+    """The LEARNED recurrence prior: one gate per side and relation, a = sigmoid(logit).  logit: fp32 [2, num_rels] (row 0 the
+    'ob' side -- objects of (s, r, ?) --, row 1 the 'sub' side), or [2, 1] with per_relation=False; initialised to
+    logit(alpha).  half_life as RecurrencePrior's, fixed.  Accepted wherever `prior=` takes a RecurrencePrior; trained by
+    RENet.learn_observed(prior=gate, gate_optimizer=) and fit_gate.  state_dict() holds `logit`."""
+
+    def __init__(self, num_rels, alpha=0.3, half_life=None, per_relation=True):
+        super(CopyGate, self).__init__()
+        alpha = float(alpha)
+        if not 0.0 < alpha < 1.0:
+            raise ValueError('alpha must lie in (0, 1): it initialises logit = log(alpha / (1 - alpha))')
+        if half_life is not None and not float(half_life) > 0.0:
+            raise ValueError('half_life must be positive (None: frequency only)')
+        self.num_rels, self.per_relation = int(num_rels), bool(per_relation)
+        if self.num_rels < 1:
+            raise ValueError('num_rels must be positive')
+        self.half_life = None if half_life is None else float(half_life)
+        self.inv_half_life = 0.0 if half_life is None else float(np.float32(1.0 / float(half_life)))
+        width = self.num_rels if self.per_relation else 1
+        self.logit = torch.nn.Parameter(torch.full((2, width), math.log(alpha / (1.0 - alpha)), dtype=torch.float32))
+        self._checked_version = None
+
+    def __repr__(self):
+        return 'CopyGate(num_rels=%d, half_life=%r, per_relation=%r)' % (self.num_rels, self.half_life, self.per_relation)
+
+    def table(self):
+        """The gates [2, width] = sigmoid(logit), kept below 1."""
+        return torch.sigmoid(self.logit).clamp(max=A_MAX)
+
+    def check(self):
+        """Refuses a gate table that is not inside [0, 1) (a NaN logit) -- one small read-back per change of the parameter,
+        so that the gated mix kernel, which cannot check device memory, is never launched on one."""
+        key = (self.logit._version, self.logit.data_ptr())
+        if self._checked_version != key:
+            tab = self.table().detach()
+            if not bool(((tab >= 0) & (tab < 1)).all()):
+                raise ValueError('CopyGate: a gate outside [0, 1) (non-finite logit?)')
+            self._checked_version = key
+        return self
+
+    def index(self, side, rel):
+        """The flat index into table() of the rows of `side` with relations rel (host array or device tensor)."""
+        if side not in SIDES:
+            raise ValueError("side must be 'ob' or 'sub'")
+        width = self.logit.shape[1]
+        if isinstance(rel, torch.Tensor):
+            r = rel.long()
+            if self.per_relation and r.numel() and (int(r.min()) < 0 or int(r.max()) >= self.num_rels):
+                raise ValueError('relation outside [0, num_rels)')
+            return (r if self.per_relation else torch.zeros_like(r)) + SIDES[side] * width
+        r = np.asarray(rel, dtype=np.int64).reshape(-1)
+        if self.per_relation and len(r) and (r.min() < 0 or r.max() >= self.num_rels):
+            raise ValueError('relation outside [0, num_rels)')
+        return (r if self.per_relation else np.zeros_like(r)) + SIDES[side] * width
+
+    def rows_at(self, index):
+        """The gates at the flat table indices `index` (host int array), a device tensor with autograd: its gradient reaches
+        `logit` through a deterministic segmented add."""
+        dev = self.logit.device
+        index = np.ascontiguousarray(index, dtype=np.int64)
+        flat = self.table().reshape(-1)
+        idx_dev = torch.from_numpy(index).to(dev)
+        if not (torch.is_grad_enabled() and self.logit.requires_grad) or len(index) == 0:
+            return flat.detach()[idx_dev]
+        hp, plan = G.SegPlan.host(index), G.SegPlan()
+        plan.order, plan.seg_ptr, plan.target = (G.h2d(np.ascontiguousarray(a, dtype=np.int32), dev)
+                                                 for a in (hp.order, hp.seg_ptr, hp.target))
+        plan.num_segments = hp.num_segments
+        return _GateRowsFn.apply(flat, idx_dev, plan)
+
+    def rows(self, side, rel):
+        """The per-row gate of the rows of `side` ('ob' / 'sub') with relations rel, a device tensor with autograd."""
+        if isinstance(rel, torch.Tensor):
+            if not (torch.is_grad_enabled() and self.logit.requires_grad):
+                return self.table().detach().reshape(-1)[self.index(side, rel)]
+            rel = rel.cpu().numpy()
+        return self.rows_at(self.index(side, rel))
 
 
 class QueryRows(object):
@@ -74,15 +204,114 @@ class QueryRows(object):
         role = SIDES[name]
         d = int(self.rel.numel()) if d is None else d
         t = self.base.t
+        if isinstance(prior, CopyGate):                                 # one gate per row: the gated entry
+            width = prior.logit.shape[1]
+            with torch.no_grad():
+                tab = prior.check().table().reshape(-1)
+                rel = self.rel[c:d].long()
+                if width > 1:
+                    rel = rel.clamp(0, width - 1)        # (a relation the gate does not know reads a neighbour's gate, never memory)
+                else:
+                    rel = torch.zeros_like(rel)
+                a_row = tab[rel + role * width].contiguous()
+            return K.recurrence_mix_rows_gated(self.ent[role][c:d], self.rel[c:d], self.t[c:d], self.as_of[c:d],
+                                               self.tables[role], t['ent_ptr%d' % role], t['snap_ptr%d' % role],
+                                               self.base.num_ent, logits, a_row, prior.inv_half_life,
+                                               num_cols=self.base.num_ent, want_stats=want_stats, check=False)
         return K.recurrence_mix_rows(self.ent[role][c:d], self.rel[c:d], self.t[c:d], self.as_of[c:d], self.tables[role],
                                      t['ent_ptr%d' % role], t['snap_ptr%d' % role], self.base.num_ent, logits, prior.alpha,
                                      prior.inv_half_life, num_cols=self.base.num_ent, want_stats=want_stats)
 
 
 def _checked(prior):
-    if not isinstance(prior, RecurrencePrior):
-        raise ValueError('prior must be a recurrence.RecurrencePrior')
+    if not isinstance(prior, (RecurrencePrior, CopyGate)):
+        raise ValueError('prior must be a recurrence.RecurrencePrior or a recurrence.CopyGate')
     return prior
+
+
+class CopyRows(object):
+    """(a_row, q_row, W) of ONE merged training batch, for RENet.loss_prepared_both(prep, copy=): the positions idx of the
+    resident store `store` (a gpu_builder.ObservedStore; as_of = t: no fact of the query's own timestamp is read) under
+    `prior` (RecurrencePrior: a = alpha; CopyGate: a = its gate of (side, relation), with autograd).  Two
+    renet_recurrence_gold_rows launches, one per role -- sequence i < n of the merged batch is position i's 'ob' direction
+    (given s, gold o), sequence n + i its 'sub' direction (given o, gold s) --, a zeroed where the prior abstains (W = 0), and
+    in batch() one gather through the builder's perm (sorted position -> sequence) into the batch's row order."""
+
+    def __init__(self, store, idx, prior):
+        _checked(prior)
+        idx = np.asarray(idx, dtype=np.int64).reshape(-1)
+        rows = QueryRows(store, idx)
+        base, n = rows.base, len(idx)
+        q, w = [], []
+        for role in (0, 1):
+            qq, ww = K.recurrence_gold_rows(rows.ent[role], rows.rel, rows.t, rows.as_of, rows.ent[1 - role], rows.tables[role],
+                                            base.t['ent_ptr%d' % role], base.t['snap_ptr%d' % role], base.num_ent, base.num_ent,
+                                            prior.inv_half_life)
+            q.append(qq)
+            w.append(ww)
+        self.n = n
+        self.q_seq, self.W_seq = torch.cat(q), torch.cat(w)
+        if isinstance(prior, CopyGate):
+            rel = store.quads[idx, 1]
+            a = prior.check().rows_at(np.concatenate((prior.index('ob', rel), prior.index('sub', rel))))
+        else:
+            a = torch.full((2 * n,), prior.alpha, device=self.q_seq.device, dtype=torch.float32)
+        self.a_seq = torch.where(self.W_seq > 0, a, torch.zeros_like(a))
+
+    def batch(self, prep):
+        """-> (a_row, q_row, W) in the row order of the PreparedBatch prep built from the same positions."""
+        if prep.b != 2 * self.n:
+            raise ValueError('CopyRows: the batch does not hold the two directions of these positions')
+        perm = prep.g._v['perm'][:prep.b].long()
+        a = _PermuteFn.apply(self.a_seq, perm) if self.a_seq.requires_grad else self.a_seq[perm]
+        return a, self.q_seq[perm], self.W_seq[perm]
+
+
+def fit_gate(model, obs, idx, gate, optimizer, steps=1, max_batch=4096):
+    """"Fitting alpha" with the model FROZEN: `steps` optimizer steps of the CopyGate `gate` on the stream positions idx of
+    the resident stream obs.  Per step and per batch of max_batch positions the scores are computed under no_grad as
+    RENet.observed_scores computes them (eval mode), renet_mix_ce takes them with dlogits = NULL -- only d_a flows --, and the
+    gate's gradient of the MEAN mixed loss over all rows of both directions is accumulated before ONE optimizer.step().
+    optimizer: any torch.optim over gate.parameters().  -> the mean mixed loss per step (Python floats, before that step's
+    update).  The model's parameters and mode are left as found."""
+    import model as M
+    if not isinstance(gate, CopyGate):
+        raise ValueError('fit_gate fits a recurrence.CopyGate')
+    store = M._observed_store(obs)
+    idx = M._observed_positions(store, idx)
+    max_batch = max(1, int(max_batch))
+    n = len(idx)
+    dev = gate.logit.device
+    was_training = model.training
+    model.eval()
+    out = []
+    try:
+        for _ in range(int(steps)):
+            optimizer.zero_grad()
+            total = torch.zeros((), device=dev)
+            for c in range(0, n, max_batch):
+                part = idx[c:c + max_batch]
+                sub_pred, ob_pred = model.observed_scores(obs, part)
+                rows = CopyRows(store, part, gate)
+                m = len(part)
+                for k, (pred, gold) in enumerate(((ob_pred, rows_gold(store, part, 'ob')), (sub_pred, rows_gold(store, part, 'sub')))):
+                    a = rows.a_seq[k * m:(k + 1) * m]
+                    row_loss, d_a = K.mix_ce(pred, gold, a.detach().contiguous(), rows.q_seq[k * m:(k + 1) * m].contiguous(),
+                                             1.0 / (2 * n), False)
+                    a.backward(d_a, retain_graph=True)
+                    total = total + row_loss.sum() / (2 * n)
+            optimizer.step()
+            out.append(total)
+    finally:
+        model.train(was_training)
+    return [float(x) for x in torch.stack(out).cpu()] if out else []
+
+
+def rows_gold(store, idx, name):
+    """The gold column (int32 device [n]) of side `name` of the stream positions idx: the object for 'ob', the subject for
+    'sub'."""
+    pos = torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int64)).to(store.device)
+    return store.t['q_o' if name == 'ob' else 'q_s'][pos].contiguous()
 
 
 def _query_store(obs, queries, as_of):

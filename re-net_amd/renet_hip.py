@@ -181,6 +181,13 @@ _SIGNATURES = {
                           + [c_void_p] * 4 + [c_int] + [c_void_p] * 4),
     'renet_recurrence_mix_rows': (c_int, [c_void_p] * 4 + [c_int] + [c_void_p] * 3 + [c_int, c_void_p, c_void_p, c_int, c_int,
                                           c_void_p, c_int, c_int, c_float, c_float] + [c_void_p] * 4),
+    'renet_recurrence_mix_rows_gated': (c_int, [c_void_p] * 4 + [c_int] + [c_void_p] * 3 + [c_int, c_void_p, c_void_p, c_int,
+                                                c_int, c_void_p, c_int, c_int, c_void_p, c_float] + [c_void_p] * 4),
+    'renet_recurrence_gold_rows': (c_int, [c_void_p] * 5 + [c_int] + [c_void_p] * 3 + [c_int, c_void_p, c_void_p, c_int, c_int,
+                                           c_int, c_float] + [c_void_p] * 3),
+    'renet_mix_ce': (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_float] + [c_void_p] * 4),
+    'renet_mix_ce_planes': (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_size_t, c_int, c_int,
+                                    c_void_p, c_void_p]),
     'renet_build_full_graphs_workspace': (c_size_t, [c_void_p, c_int, c_int, c_int]),
     'renet_build_full_graphs': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t,
                                         c_void_p]),
@@ -347,7 +354,7 @@ def _timed_end(t0, name, flops=0.0, nbytes=0.0, tag=None):
 GLUE = ('softmax_ce_planes', 'gather_rows', 'segment_add', 'segment_add2', 'compose_table_items', 'rgcn_bwd_prep', 'colsum',
         'scale_by_device_scalar', 'seq_assemble_fwd', 'seq_assemble_fwd_bf16', 'softmax_ce_bf16', 'seq_assemble_bwd',
         'concat3_fwd', 'concat3_bwd', 'dropout', 'softmax_ce', 'adam_step', 'segment_pool_fwd', 'segment_pool_bwd',
-        'pack_bf16_glue', 'soft_ce_sparse')
+        'pack_bf16_glue', 'soft_ce_sparse', 'mix_ce', 'mix_ce_planes')
 _glue_saved = {}
 
 
@@ -959,6 +966,29 @@ def softmax_ce_planes(logits, target, grad_scale, row_loss=None):
     return row_loss, dl
 
 
+def _copy_rows(a_row, q_row, b, what):
+    for v, name in ((a_row, 'a_row'), (q_row, 'q_row')):
+        if not (torch.is_tensor(v) and v.is_cuda and v.dtype == torch.float32 and v.is_contiguous() and v.numel() == b):
+            raise RenetHipError('%s: %s must be a contiguous float32 device tensor with one entry per row' % (what, name))
+    return a_row.data_ptr(), q_row.data_ptr()
+
+
+def mix_ce_planes(logits, target, a_row, q_row, grad_scale, row_loss=None, want_da=True):
+    """softmax_ce_planes for the loss through the copy mix (renet_mix_ce_planes): per row the gate a_row and the prior's mass
+    on the gold column q_row (fp32 device [B]; a_row already zeroed where the prior abstains).  -> (row_loss[B] = -log((1 - a)
+    p_gold + a q), PlanesMat (softmax - onehot) * grad_scale * s, d_a[B] = grad_scale * dL/da or None)."""
+    b, c = logits.shape
+    pa, pq = _copy_rows(a_row, q_row, b, 'mix_ce_planes')
+    if row_loss is None:
+        row_loss = torch.empty(b, device=logits.device, dtype=torch.float32)
+    d_a = torch.empty(b, device=logits.device, dtype=torch.float32) if want_da else None
+    dl = planes_empty(b, c, logits.device)
+    _check(lib().renet_mix_ce_planes(logits.data_ptr(), _i32(target), pa, pq, b, c, _ld(logits), float(grad_scale),
+                                     _f32(row_loss), dl.p.data_ptr(), dl.plane, dl.p.shape[2], dl.p.shape[1], _f32(d_a),
+                                     _stream()), 'mix_ce_planes')
+    return row_loss, dl, d_a
+
+
 class F32Op(object):
     """An fp32 GEMM operand together with the bound on its largest magnitude that the f16x3 GEMM scales it by:
     `part` holds n <= 256 device floats whose maximum bounds max |t| (renet_maxabs_partials, or a known bound)."""
@@ -1480,6 +1510,19 @@ def softmax_ce(logits, target, grad_scale, want_grad, row_loss=None):
     return row_loss
 
 
+def mix_ce(logits, target, a_row, q_row, grad_scale, want_grad, row_loss=None, want_da=True):
+    """softmax_ce for the loss through the copy mix (renet_mix_ce; a_row / q_row as for mix_ce_planes): -> (row_loss[B],
+    d_a[B] or None); if want_grad, logits is OVERWRITTEN with (softmax - onehot) * grad_scale * s."""
+    b, c = logits.shape
+    pa, pq = _copy_rows(a_row, q_row, b, 'mix_ce')
+    if row_loss is None:
+        row_loss = torch.empty(b, device=logits.device, dtype=torch.float32)
+    d_a = torch.empty(b, device=logits.device, dtype=torch.float32) if want_da else None
+    _check(lib().renet_mix_ce(logits.data_ptr(), _i32(target), pa, pq, b, c, _ld(logits), float(grad_scale),
+                              _f32(row_loss), logits.data_ptr() if want_grad else None, _f32(d_a), _stream()), 'mix_ce')
+    return row_loss, d_a
+
+
 def soft_ce_sparse(logits, tgt_ptr, tgt_col, tgt_w, grad_scale, want_grad, row_loss=None):
     """renet_soft_ce_sparse on logits [B, C] (fp32, unit inner stride) with the CSR soft targets tgt_ptr [B + 1] (int32),
     tgt_col [nnz] (int32; per row distinct, ascending) and tgt_w [nnz] (fp32, >= 0; a row need not sum to 1): returns
@@ -1722,6 +1765,28 @@ def recurrence_mix_rows(ent, rel, t, as_of, tables, ent_ptr, snap_ptr, num_ent, 
     num_cols columns.  ent_ptr / snap_ptr: the role's resident history index.  0 <= alpha < 1.  A row of out is a normalised
     log-probability row: rank_rows3 and topk_rows read it as they read logits.  want_stats: -> (out, stats int32 [n, 2] =
     (distinct partners, facts counted), W fp32 [n])."""
+    return _recurrence_mix(ent, rel, t, as_of, tables, ent_ptr, snap_ptr, num_ent, logits, alpha, None, inv_half_life,
+                           num_cols, want_stats)
+
+
+def recurrence_mix_rows_gated(ent, rel, t, as_of, tables, ent_ptr, snap_ptr, num_ent, logits, alpha_row, inv_half_life=0.0,
+                              num_cols=None, want_stats=False, check=True):
+    """renet_recurrence_mix_rows_gated: recurrence_mix_rows with one gate per row, alpha_row (fp32 device [n], each in
+    [0, 1)) -- a_i = alpha_row[i] where W_i > 0, else 0.  check: read alpha_row's range back (one synchronisation) and refuse
+    a gate outside [0, 1) before the launch; a caller that built the gates from a checked table passes False."""
+    if not (torch.is_tensor(alpha_row) and alpha_row.is_cuda and alpha_row.dtype == torch.float32 and
+            alpha_row.is_contiguous() and alpha_row.numel() == ent.numel()):
+        raise RenetHipError('recurrence_mix_rows_gated: alpha_row must be a contiguous float32 device tensor, one per row')
+    if check and alpha_row.numel():
+        lo, hi = (float(v) for v in torch.aminmax(alpha_row.detach()))
+        if not (lo >= 0.0 and hi < 1.0):
+            raise RenetHipError('recurrence_mix_rows_gated: every gate must lie in [0, 1)')
+    return _recurrence_mix(ent, rel, t, as_of, tables, ent_ptr, snap_ptr, num_ent, logits, None, alpha_row.detach(),
+                           inv_half_life, num_cols, want_stats)
+
+
+def _recurrence_mix(ent, rel, t, as_of, tables, ent_ptr, snap_ptr, num_ent, logits, alpha, alpha_row, inv_half_life, num_cols,
+                    want_stats):
     n = int(ent.numel())
     if any(int(a.numel()) != n for a in (rel, t, as_of)):
         raise RenetHipError('recurrence_mix_rows: ent, rel, t and as_of must have one entry per row')
@@ -1744,14 +1809,40 @@ def recurrence_mix_rows(ent, rel, t, as_of, tables, ent_ptr, snap_ptr, num_ent, 
     stats = torch.empty(n, 2, device=dev, dtype=torch.int32) if want_stats else None
     wsum = torch.empty(n, device=dev, dtype=torch.float32) if want_stats else None
     t0 = _timed()
-    _check(lib().renet_recurrence_mix_rows(_i32(ent, 'ent'), _i32(rel, 'rel'), _i32(t, 't'), _i32(as_of, 'as_of'), n,
-                                           *[_i32(a, 'pair table') if nf else None for a in tables], nf,
-                                           _i32(ent_ptr, 'ent_ptr'), _i32(snap_ptr, 'snap_ptr'), int(snap_ptr.numel()) - 1,
-                                           int(num_ent), None if logits is None else logits.data_ptr(), ld, c, float(alpha),
-                                           float(inv_half_life), out.data_ptr(), _i32(stats), _f32(wsum), _stream()),
-           'recurrence_mix_rows')
+    front = (_i32(ent, 'ent'), _i32(rel, 'rel'), _i32(t, 't'), _i32(as_of, 'as_of'), n,
+             *[_i32(a, 'pair table') if nf else None for a in tables], nf, _i32(ent_ptr, 'ent_ptr'),
+             _i32(snap_ptr, 'snap_ptr'), int(snap_ptr.numel()) - 1, int(num_ent),
+             None if logits is None else logits.data_ptr(), ld, c)
+    back = (float(inv_half_life), out.data_ptr(), _i32(stats), _f32(wsum), _stream())
+    if alpha_row is None:
+        _check(lib().renet_recurrence_mix_rows(*front, float(alpha), *back), 'recurrence_mix_rows')
+    else:
+        _check(lib().renet_recurrence_mix_rows_gated(*front, _f32(alpha_row, 'alpha_row'), *back), 'recurrence_mix_rows_gated')
     _timed_end(t0, 'recurrence_mix_rows', nbytes=float(n * c * (4 if logits is None else 12)))
     return (out, stats, wsum) if want_stats else out
+
+
+def recurrence_gold_rows(ent, rel, t, as_of, gold, tables, ent_ptr, snap_ptr, num_ent, num_cols, inv_half_life=0.0):
+    """renet_recurrence_gold_rows, one direction: -> (q, W), fp32 device [n]: W_i the W of recurrence_mix_rows (its stats_w
+    bit for bit) and q_i = w_i[gold_i] / W_i, the prior's mass on the column gold_i (int32 device [n]); both 0 where the pair
+    has no history before as_of_i or the entity lies outside [0, num_ent), q_i = 0 where gold_i lies outside [0, num_cols)."""
+    n = int(ent.numel())
+    if any(int(a.numel()) != n for a in (rel, t, as_of, gold)):
+        raise RenetHipError('recurrence_gold_rows: ent, rel, t, as_of and gold must have one entry per row')
+    p_rel, p_other, p_t = tables
+    nf = int(p_rel.numel())
+    if p_other.numel() != nf or p_t.numel() != nf or ent_ptr.numel() != int(num_ent) + 1:
+        raise RenetHipError('recurrence_gold_rows: the pair tables do not fit num_ent / their own lengths')
+    q = torch.empty(n, device=ent.device, dtype=torch.float32)
+    w = torch.empty(n, device=ent.device, dtype=torch.float32)
+    t0 = _timed()
+    _check(lib().renet_recurrence_gold_rows(_i32(ent, 'ent'), _i32(rel, 'rel'), _i32(t, 't'), _i32(as_of, 'as_of'),
+                                            _i32(gold, 'gold'), n, *[_i32(a, 'pair table') if nf else None for a in tables],
+                                            nf, _i32(ent_ptr, 'ent_ptr'), _i32(snap_ptr, 'snap_ptr'),
+                                            int(snap_ptr.numel()) - 1, int(num_ent), int(num_cols), float(inv_half_life),
+                                            q.data_ptr(), w.data_ptr(), _stream()), 'recurrence_gold_rows')
+    _timed_end(t0, 'recurrence_gold_rows', nbytes=float(n * 28))
+    return q, w
 
 
 def joint_row_offsets(scores, num_rels, logits_r):

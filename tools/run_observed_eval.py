@@ -9,7 +9,7 @@ protocol under which RE-GCN, xERTE and TITer report the time-aware filter.  NOT 
                                       [--horizon H] [--queries FILE [--k K]] [--observe-loop]
                                       [--rollout H [--num-k K]]
                                       [--online [STEPS] [--replay N] [--online-global] [--lr LR]]
-                                      [--recurrence ALPHA [--half-life H]]
+                                      [--recurrence ALPHA [--half-life H] [--fit-gate STEPS] [--learn-copy] [--gate-lr LR]]
 
 --horizon H evaluates with STALE histories (RENet.evaluate_forecast with ObservedStream.horizon_as_of): the split's timestamps
 are cut into blocks of H, and every query forecasts from the facts before the first timestamp of its block; nothing is
@@ -44,6 +44,15 @@ after the model's own metrics it prints the model-free BASELINE alone -- how oft
 connected to each object before the query's as-of time, ranked under the same histories, filters and tie rule -- and the
 model MIXED with the prior at weight ALPHA, each labelled as such.  The baseline is a protocol-matched yardstick: report it
 with its ALPHA and half-life (in the dataset's raw timestamp units), beside model numbers of the same protocol only.
+
+--fit-gate STEPS (with --recurrence) LEARNS the weight of the prior: a recurrence.CopyGate -- one gate per side and relation,
+initialised to ALPHA -- is fitted with the model frozen (recurrence.fit_gate, STEPS Adam steps at --gate-lr) on the VALID
+split under observed histories, and the chosen split is then evaluated mixed with the learned gates.  --online --recurrence
+ALPHA mixes the prior into the forecast half of the online loop; with --learn-copy the learn steps train THROUGH the mix
+(RENet.learn_observed(prior=, gate_optimizer=)) and the gates learn along the stream.  Numbers with a LEARNED gate are a
+protocol of their own -- the gate has seen the fitting data: every line printed says so, and such numbers are comparable only
+with numbers of the same protocol and the same fitting data.  A learn step through the mix is not in the C launch list
+(csrc/step.cpp): it runs the autograd path and pays its host enqueue.
 
 --events adds the EVENT forecasts (RENet.evaluate_events_observed): MRR / Hits of the gold (relation, entity) pair among all
 pairs of the given entity, and of the gold relation given both endpoints, in the three settings; with K also the K most
@@ -168,10 +177,19 @@ def online_loop(args, model, global_model, splits, num_ent, num_rels, data_dir):
     obs.resident(model, global_model)
     opt = parallel.HipAdam(model, lr=args.lr, weight_decay=1e-5, max_norm=1.0)
     gopt = parallel.HipAdam(global_model, lr=args.lr, weight_decay=1e-5, max_norm=1.0) if args.online_global else None
+    prior, gate_opt = None, None
+    if args.recurrence is not None:
+        import recurrence
+        if args.learn_copy:
+            prior = recurrence.CopyGate(num_rels, alpha=args.recurrence, half_life=args.half_life).to(next(model.parameters()).device)
+            gate_opt = torch.optim.Adam(prior.parameters(), lr=args.gate_lr)
+        else:
+            prior = recurrence.RecurrencePrior(args.recurrence, args.half_life)
     torch.cuda.synchronize()
     t1 = time.perf_counter()
     ranks, loss, log = model.evaluate_online(obs, evaluated, global_model, opt, steps=args.online, replay=args.replay,
-                                             global_optimizer=gopt, all_triplets=known, max_batch=args.max_batch)
+                                             global_optimizer=gopt, all_triplets=known, max_batch=args.max_batch, prior=prior,
+                                             learn_prior=args.learn_copy, gate_optimizer=gate_opt)
     torch.cuda.synchronize()
     t2 = time.perf_counter()
     n_t = len(log)
@@ -181,6 +199,17 @@ def online_loop(args, model, global_model, splits, num_ent, num_rels, data_dir):
              n_t, t1 - t0, t2 - t1, 1e3 * (t2 - t1) / max(n_t, 1)))
     print('the weights that rank timestamp t have been trained on every evaluated timestamp before t: these numbers are not '
           'those of the static observed, stale-horizon, rollout or multi-step protocols')
+    if prior is not None:
+        half = 'none (frequency only)' if prior.half_life is None else '%g' % prior.half_life
+        if args.learn_copy:
+            tab = prior.table().detach().cpu().numpy()
+            print('MODEL MIXED WITH THE RECURRENCE PRIOR, LEARNED GATE (online, trained through the mix; initial alpha %g, '
+                  'half-life %s, gate lr %g): the gate that ranks timestamp t was fitted on the evaluated timestamps before t; '
+                  'gates now: ob side %.3f .. %.3f, sub side %.3f .. %.3f.  Comparable only with numbers of this protocol.'
+                  % (args.recurrence, half, args.gate_lr, tab[0].min(), tab[0].max(), tab[1].min(), tab[1].max()))
+        else:
+            print('MODEL MIXED WITH THE RECURRENCE PRIOR in the forecast half, fixed alpha %g, half-life %s; learning is not '
+                  'touched by it' % (prior.alpha, half))
     step_losses = [x for e in log for x in e['losses']]
     if step_losses:
         print('mean learn-step loss %.6f (first timestamp %.6f, last %.6f)'
@@ -192,6 +221,8 @@ def online_loop(args, model, global_model, splits, num_ent, num_rels, data_dir):
               % (name, m['mrr'], m['mr'], m['hits@1'], m['hits@3'], m['hits@10']))
     print(json.dumps({'protocol': 'observed', 'loop': 'online', 'steps': args.online, 'replay': args.replay,
                       'global_model_learns': gopt is not None, 'lr': args.lr, 'split': args.split, 'n': int(len(evaluated)),
+                      'recurrence': None if prior is None else {'alpha': args.recurrence, 'half_life': args.half_life,
+                                                                'gate_learned': bool(args.learn_copy)},
                       'metrics': {name: U.rank_metrics(ranks[name]) for name in SETTINGS}}))
 
 
@@ -227,14 +258,25 @@ def main():
                     help='also print the recurrence baseline alone and the model mixed with it at weight ALPHA in [0, 1)')
     ap.add_argument('--half-life', type=float, default=None, metavar='H',
                     help='half-life of the recurrence prior in raw timestamp units (default: frequency only)')
+    ap.add_argument('--fit-gate', type=int, default=None, metavar='STEPS',
+                    help='fit a per-relation gate on the valid split (model frozen), then evaluate mixed with it (--recurrence)')
+    ap.add_argument('--learn-copy', action='store_true',
+                    help='online steps train through the mix and the gates learn along the stream (--online --recurrence)')
+    ap.add_argument('--gate-lr', type=float, default=1e-2, help='learning rate of the gate (--fit-gate, --learn-copy)')
     args = ap.parse_args()
     if args.recurrence is not None:
         if not 0.0 <= args.recurrence < 1.0 or (args.half_life is not None and args.half_life <= 0):
             raise SystemExit('--recurrence takes ALPHA in [0, 1), --half-life a positive H')
-        if args.observe_loop or args.rollout is not None or args.online is not None or args.queries is not None:
-            raise SystemExit('--recurrence goes with the plain pass and --horizon only')
-    elif args.half_life is not None:
-        raise SystemExit('--half-life belongs to --recurrence')
+        if args.observe_loop or args.rollout is not None or args.queries is not None:
+            raise SystemExit('--recurrence goes with the plain pass, --horizon and --online only')
+        if (args.fit_gate is not None or args.learn_copy) and not args.recurrence > 0.0:
+            raise SystemExit('a learned gate starts from ALPHA in (0, 1)')
+        if args.fit_gate is not None and (args.fit_gate < 1 or args.online is not None):
+            raise SystemExit('--fit-gate takes STEPS >= 1 and goes with the plain pass and --horizon')
+        if args.learn_copy and args.online is None:
+            raise SystemExit('--learn-copy belongs to --online --recurrence')
+    elif args.half_life is not None or args.fit_gate is not None or args.learn_copy:
+        raise SystemExit('--half-life, --fit-gate and --learn-copy belong to --recurrence')
     if args.online is not None:
         if args.online < 0 or args.replay < 0:
             raise SystemExit('--online and --replay must be >= 0')
@@ -353,6 +395,36 @@ def main():
                      baseline={name: U.rank_metrics(base_ranks[name]) for name in SETTINGS},
                      mixed={name: U.rank_metrics(mix_ranks[name]) for name in SETTINGS})
         print(json.dumps(extra))
+        if args.fit_gate is not None:
+            if splits[1] is None:
+                raise SystemExit('--fit-gate fits on the valid split: %s has no valid.txt' % data_dir)
+            gate = recurrence.CopyGate(num_rels, alpha=args.recurrence, half_life=args.half_life).to(dev)
+            t6 = time.perf_counter()
+            fit = recurrence.fit_gate(model, obs, obs.positions('valid'), gate, torch.optim.Adam(gate.parameters(), lr=args.gate_lr),
+                                      steps=args.fit_gate, max_batch=args.max_batch)
+            torch.cuda.synchronize()
+            t7 = time.perf_counter()
+            gate_ranks, gate_loss = model.evaluate_forecast(obs, obs.allq[idx], as_of=as_of, max_batch=args.max_batch, prior=gate)
+            torch.cuda.synchronize()
+            t8 = time.perf_counter()
+            tab = gate.table().detach().cpu().numpy()
+            print('MODEL MIXED WITH THE RECURRENCE PRIOR, LEARNED GATE per side and relation (fitted on the valid split%s, model '
+                  'frozen, observed histories, %d Adam steps at lr %g from alpha %g, half-life %s): fit %.2f s, mean mixed loss of '
+                  'the valid split %.6f -> %.6f; gates ob side %.3f .. %.3f, sub side %.3f .. %.3f; pass %.2f s (%.0f '
+                  'quadruples/s), mean loss %.6f'
+                  % (' -- THE EVALUATED SPLIT ITSELF' if args.split == 'valid' else '', args.fit_gate, args.gate_lr, args.recurrence,
+                     'none (frequency only)' if gate.half_life is None else '%g' % gate.half_life, t7 - t6, fit[0], fit[-1],
+                     tab[0].min(), tab[0].max(), tab[1].min(), tab[1].max(), t8 - t7, len(idx) / max(t8 - t7, 1e-9),
+                     float(np.mean(gate_loss))))
+            for name in SETTINGS:
+                m = U.rank_metrics(gate_ranks[name])
+                print('%-14s MRR %.6f  MR %.3f  Hits@1 %.6f  Hits@3 %.6f  Hits@10 %.6f'
+                      % (name, m['mrr'], m['mr'], m['hits@1'], m['hits@3'], m['hits@10']))
+            print('(a LEARNED gate: the same protocol, filters and tie rule as the blocks above, but the gate has seen the valid '
+                  'split -- comparable only with numbers obtained the same way)')
+            print(json.dumps(dict(record, recurrence={'alpha': args.recurrence, 'half_life': gate.half_life, 'gate_learned': True,
+                                                      'fitted_on': 'valid', 'fit_steps': args.fit_gate, 'gate_lr': args.gate_lr},
+                                  mixed_learned_gate={name: U.rank_metrics(gate_ranks[name]) for name in SETTINGS})))
     if args.events is not None:
         t3 = time.perf_counter()
         ev = model.evaluate_events_observed(obs, idx)
