@@ -944,6 +944,38 @@ int renet_recurrence_gold_rows(const int32_t* ent, const int32_t* rel, const int
                                float inv_half_life, float* q, float* W, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * RECURRENCE PRIOR FOR EVENT FORECASTS (csrc/joint_mix.hip): the joint copy mix over (relation, entity) pairs -- "s does again
+ * what it did before, with whom it did it" mixed into the joint blocks of renet_joint_row_offsets / renet_joint_rank_rows.
+ *
+ * renet_joint_mix_rows runs AFTER renet_joint_row_offsets on the block scores [G * R, C] (row stride ld) and on off [G * R], IN
+ * PLACE.  Group g is one history: the entity ent[g], the query time t[g] and the as_of[g] <= t[g] its window was built with
+ * (device int32 [G] each); the pair tables, ent_ptr and snap_ptr are those of the role of the GIVEN entity, as for
+ * renet_recurrence_mix_rows.  With the sums over the entity's facts (e, r, c, t') with t' < as_of:
+ *     w[r, c] = sum of 2^(-(t - t') * inv_half_life)          (inv_half_life = 0: plain counts)
+ *     W       = sum over ALL counted facts of e, every relation              (entity-wide, not per relation)
+ *     a       = alpha if W > 0 else 0       (no history, or e outside [0, num_ent): the prior abstains)
+ * and J = scores[g * R + r, c] + off[g * R + r], the one fp32 addition of renet_joint_rank_rows, widened to fp64:
+ *     M = fp32(J + log1p(-a))                              for a pair without a counted fact
+ *     M = fp32(log((1 - a) * exp(J) + a * w[r, c] / W))    for a pair with counted facts
+ * For a group with a > 0 the entry writes scores[g * R + r, c] = M and off[g * R + r] = 0: scores + off in one fp32 addition is
+ * then M itself, and renet_joint_rank_rows, renet_topk_rows(_wide) + off and renet_select_events read the MIXED joint
+ * unchanged.  exp(M) sums to 1 over the R * C pairs where exp(J) does.  A group that abstains keeps its rows and its off
+ * untouched, bit for bit; alpha = 0 with W > 0 gives M == J bit for bit (and off = 0).  A fact whose partner lies outside
+ * [0, C), or whose relation lies outside [0, R), counts in W and is never addressed.
+ * mass [G] (device fp64, the caller's): W of every group, written by a first launch of one workgroup per group and read by
+ * the row launch of one workgroup per (g, r) -- W is not summed again in each of the group's R rows.  Every sum is in fp64 in
+ * an order fixed by the tables' content and the block size, each output is rounded to fp32 once: no floating-point atomics,
+ * the same bits from run to run.  The dense pass is one 16-byte read and one 16-byte write of the row (scalar head and tail:
+ * any ld, any row alignment); no workspace.
+ * 1 <= R <= 1024, C in [1, RENET_RECURRENCE_MAX_C]; alpha outside [0, 1), a negative or non-finite inv_half_life, ld < C, R or C
+ * out of range, G < 0 or a missing array: RENET_ERR_BADARG before any launch; G == 0 is a no-op.
+ * Not covered: a gate per relation (with the relation open it gives no normalised joint), training through the joint mix. */
+int renet_joint_mix_rows(const int32_t* ent, const int32_t* t, const int32_t* as_of, int G, const int32_t* p_rel,
+                         const int32_t* p_other, const int32_t* p_t, int n_facts, const int32_t* ent_ptr,
+                         const int32_t* snap_ptr, int n_snaps, int num_ent, float* scores, int ld, int R, int C, float* off,
+                         float alpha, float inv_half_life, double* mass, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * DEVICE builder for the FULL-GRAPH batches of the global model (graph.build_full_graphs; reference Aggregator.py:44-55 /
  * 87-98: dgl.batch of the whole graphs of a list of timestamps).  Resident: the per-timestamp node lists and the facts with
  * LOCAL endpoints (graph.TimeGraph.ent / ls / r / lo, concatenated in graph_dict order).  tidx_dev[G] (device int32,

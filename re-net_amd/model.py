@@ -1563,9 +1563,11 @@ class _EventChunk(object):
     group's sequence; ascending, so the lengths descend), seq [G] and, for the chunk's positions, gid [n]."""
 
 
-def _event_chunks(self, store, idx):
+def _event_chunks(self, store, idx, mix=None):
     """One _EventChunk per encoder chunk of idx (the chunks of _observed_chunks: the same batch graphs), the builder of chunk
-    k + 1 enqueued before chunk k is encoded."""
+    k + 1 enqueued before chunk k is encoded.  mix: the recurrence.EventMix of a `prior=` call (None: nothing of it is made)
+    -- every direction then carries q = (ent, t, as_of) of its groups, int32 device [G], the as_of that of the group's history
+    window: the query's own t on an ObservedStore, the as_of of the group's first query on a QueryStore."""
     import gpu_builder
     dev, H = self.ent_embeds.device, self.h_dim
     step = gpu_builder.MAX_BOTH
@@ -1596,30 +1598,43 @@ def _event_chunks(self, store, idx):
             ch.lens = (bs[:, None] > np.arange(b2)[None, :]).sum(axis=0)                    # steps of sorted position
             pos_of = np.empty(b2, dtype=np.int64)
             pos_of[perm] = np.arange(b2)
-        tr = store.quads[pos]
-        ch.dirs = {}
-        for name, col, side, given, ranked in EVENT_DIRECTIONS:
-            keys, first, inv = np.unique(tr[:, [given, 3]], axis=0, return_index=True, return_inverse=True)
-            seq = first + (n if name == 'sub' else 0)               # sequence i: direction ob of position i, n + i: sub
-            order = np.argsort(pos_of[seq], kind='stable')
-            rank = np.empty(len(order), dtype=np.int64)
-            rank[order] = np.arange(len(order))
-            d = ch.dirs[name] = _EventChunk()
-            d.ent, d.t, d.seq, d.sp, d.gid = keys[order, 0], keys[order, 1], seq[order], pos_of[seq[order]], rank[inv.reshape(-1)]
+        _event_groups(ch, store, pos, pos_of, mix)
         yield ch
 
 
-def _event_blocks(self, ch, name, q_rel, block_floats):
+def _event_groups(ch, store, pos, pos_of, mix=None):
+    """Fills ch.dirs: per direction the groups of the chunk's positions pos -- the positions that share the given entity and
+    the timestamp --, ordered by the sorted position pos_of [2 n] of the group's first sequence."""
+    n = len(pos)
+    tr = store.quads[pos]
+    ch.dirs = {}
+    for name, col, side, given, ranked in EVENT_DIRECTIONS:
+        keys, first, inv = np.unique(tr[:, [given, 3]], axis=0, return_index=True, return_inverse=True)
+        seq = first + (n if name == 'sub' else 0)                   # sequence i: direction ob of position i, n + i: sub
+        order = np.argsort(pos_of[seq], kind='stable')
+        rank = np.empty(len(order), dtype=np.int64)
+        rank[order] = np.arange(len(order))
+        d = ch.dirs[name] = _EventChunk()
+        d.ent, d.t, d.seq, d.sp, d.gid = keys[order, 0], keys[order, 1], seq[order], pos_of[seq[order]], rank[inv.reshape(-1)]
+        if mix is not None:
+            d.q = mix.groups(store, d.ent, d.t, np.asarray(pos)[first[order]])
+
+
+def _event_blocks(self, ch, name, q_rel, block_floats, mix=None):
     """The blocks of one direction of a chunk in sub-blocks of at most block_floats floats (at least one group): yields
     (g0, g1, B [(g1 - g0) * R, N_ent], off [(g1 - g0) * R]) for the groups [g0, g1), the rows group-major, then relation.  Per
     sub-block: the p_base rows of its groups' steps + the q_rel broadcast, ONE recurrence over the R-fold sequences (ordered
     by sorted position, then relation: the lengths descend, the row order of _winners_pruned), the rows [ent | h | rel_r], one
-    score GEMM, renet_joint_row_offsets."""
+    score GEMM, renet_joint_row_offsets -- and, with mix (a recurrence.EventMix), ONE renet_joint_mix_rows call behind it: B and
+    off then hold the mixed joint (off zero on the groups with history)."""
     d = ch.dirs[name]
     per = _event_groups_per_block(self, block_floats)
     for g0 in range(0, len(d.ent), per):
         g1 = min(len(d.ent), g0 + per)
-        yield (g0, g1) + _event_block(self, ch, name, q_rel, np.arange(g0, g1))
+        block, off = _event_block(self, ch, name, q_rel, np.arange(g0, g1))
+        if mix is not None:
+            mix.apply(name, block, off, d.q, g0, g1)
+        yield g0, g1, block, off
 
 
 def _event_groups_per_block(self, block_floats):
@@ -1651,6 +1666,15 @@ def _event_block(self, ch, name, q_rel, sel):
     return block, K.joint_row_offsets(block, R, logits_r)
 
 
+def _event_mix(prior):
+    """The recurrence.EventMix of the `prior=` keyword of the event family; None without a prior (nothing is imported, built
+    or launched then)."""
+    if prior is None:
+        return None
+    import recurrence
+    return recurrence.EventMix(prior)
+
+
 def _event_setup(self, obs, idx):
     store = _observed_store(obs)
     idx = _observed_positions(store, idx)
@@ -1666,13 +1690,18 @@ def _event_q_rel(self):
     return {'ob': K.gemm(self.rel_embeds[:R].contiguous(), w, tb=True), 'sub': K.gemm(self.rel_embeds[R:].contiguous(), w, tb=True)}
 
 
-def _observed_event_scores(self, obs, idx, block_floats=1 << 28):
+def _observed_event_scores(self, obs, idx, block_floats=1 << 28, prior=None):
     """The blocks of the stream positions idx under observed histories (for small n: tests, inspection): {'ob': (B [n, R,
     N_ent], off [n, R]), 'sub': (...)} as device tensors.  B[i, r] is the logits row observed_scores(obs, idx) computes for
     position i in that direction if the quadruple's relation were r (the same encoder chunks, true history and global table;
     the GRU input projection is associated differently), off[i, r] the row's offset: J = B + off[..., None] in fp32 is the
-    joint log-probability that evaluate_events_observed ranks.  ValueError if n * R * N_ent exceeds block_floats."""
+    joint log-probability that evaluate_events_observed ranks.  ValueError if n * R * N_ent exceeds block_floats.
+    prior: a recurrence.RecurrencePrior or a CopyGate(per_relation=False) -- the pair is then (M, off) AFTER
+    renet_joint_mix_rows: for a position whose given entity has history before its as_of, B holds the mixed joint M and off
+    is ZERO (M + 0 is M); a position without history keeps its (B, off) bit for bit.  J = B + off[..., None] in fp32 holds
+    either way."""
     store, idx = _event_setup(self, obs, idx)
+    mix = _event_mix(prior)
     n, R, N = len(idx), self.num_rels, self.in_dim
     if n * R * N > int(block_floats):
         raise ValueError('observed_event_scores: %d positions x %d relations x %d entities exceed block_floats = %d'
@@ -1681,10 +1710,10 @@ def _observed_event_scores(self, obs, idx, block_floats=1 << 28):
     out = {name: (torch.empty(n, R, N, device=dev), torch.empty(n, R, device=dev)) for name in ('ob', 'sub')}
     with torch.no_grad():
         q_rel = _event_q_rel(self)
-        for ch in _event_chunks(self, store, idx):
+        for ch in _event_chunks(self, store, idx, mix):
             for name in ('sub', 'ob'):
                 gid = G.h2d(ch.dirs[name].gid, dev)
-                for g0, g1, block, off in _event_blocks(self, ch, name, q_rel[name], block_floats):
+                for g0, g1, block, off in _event_blocks(self, ch, name, q_rel[name], block_floats, mix):
                     here = torch.nonzero((gid >= g0) & (gid < g1)).view(-1)
                     out[name][0][ch.c + here] = block.view(g1 - g0, R, N)[gid[here] - g0]
                     out[name][1][ch.c + here] = off.view(g1 - g0, R)[gid[here] - g0]
@@ -1696,7 +1725,7 @@ def _event_known(d, R):
     return np.stack((np.repeat(d.ent, R), np.tile(np.arange(R, dtype=np.int64), len(d.ent)), np.repeat(d.t, R)), axis=1)
 
 
-def _evaluate_events_observed(self, obs, idx, all_triplets=None, block_floats=1 << 28):
+def _evaluate_events_observed(self, obs, idx, all_triplets=None, block_floats=1 << 28, prior=None):
     """Ranks of the gold EVENT of the stream positions idx under observed histories (extension of the reference API):
     {'pair': {setting: float64 [len, 2]}, 'relation': {setting: float64 [len, 2]}, 'logp': float32 [len, 2]}, column 0 the
     direction sub (the object given: pairs (r, s)), column 1 ob (the subject given: pairs (r, o)); the settings are SETTINGS.
@@ -1709,9 +1738,24 @@ def _evaluate_events_observed(self, obs, idx, all_triplets=None, block_floats=1 
     all_triplets: the known facts (None: the stream itself).  Per encoder chunk the host filter lookups of every (group,
     relation) row are done and uploaded before its sub-blocks run (block_floats bounds a sub-block's score block); one
     renet_joint_row_offsets and one renet_joint_rank_rows launch per sub-block; the counts come back in one copy at the end.
-    Repeatable in place; the multi-step state is untouched."""
+    Repeatable in place; the multi-step state is untouched.
+    prior: a recurrence.RecurrencePrior or a CopyGate(per_relation=False) (None: today's launches and results) -- one
+    renet_joint_mix_rows call per sub-block between the offsets and the rank launch; ranks and logp are then those of the
+    MIXED joint (recurrence.py): to be reported with alpha and half_life, beside recurrence.evaluate_events' baseline."""
     store, idx = _event_setup(self, obs, idx)
-    dev, n, R = self.ent_embeds.device, len(idx), self.num_rels
+    mix = _event_mix(prior)
+    dev = self.ent_embeds.device
+    with torch.no_grad():
+        q_rel = _event_q_rel(self)
+        return _rank_events(store, idx, self.num_rels, dev, all_triplets, _event_chunks(self, store, idx, mix),
+                            lambda ch, name: _event_blocks(self, ch, name, q_rel[name], block_floats, mix))
+
+
+def _rank_events(store, idx, R, dev, all_triplets, chunks, blocks):
+    """The rank tail of evaluate_events_observed over any source of joint blocks: `chunks` yields the _EventChunks of idx (c,
+    dirs), blocks(ch, name) the sub-blocks (g0, g1, B, off) of one direction of a chunk.  recurrence.evaluate_events runs it
+    over uniform blocks: the same groups, filter lists and tie rule.  Called under no_grad."""
+    n = len(idx)
     index = FI.filter_index_for(store, all_triplets if all_triplets is not None else store.quads)
     cols = {side: (index.resident(side, dev), index.resident(side, dev, timed=True)) for side in ('s', 'o')}
     gold = torch.from_numpy(np.ascontiguousarray(store.quads[idx][:, :3].T).astype(np.int32)).to(dev)      # s, r, o
@@ -1719,42 +1763,40 @@ def _evaluate_events_observed(self, obs, idx, all_triplets=None, block_floats=1 
     rel = torch.zeros(6, n, 2, device=dev, dtype=torch.int64)
     logp = torch.empty(n, 2, device=dev)
     rels = torch.arange(R, device=dev).view(1, R)
-    with torch.no_grad():
-        q_rel = _event_q_rel(self)
-        for ch in _event_chunks(self, store, idx):
-            # every host lookup of the chunk, and its upload, before the first sub-block runs
-            ups = {}
-            for name, col, side, given, ranked in EVENT_DIRECTIONS:
-                d = ch.dirs[name]
-                by_group = np.argsort(d.gid, kind='stable')                                # the chunk's positions, group-major
-                lists = np.stack(index.ranges_both_host(side, _event_known(d, R))).astype(np.int32)
-                ups[name] = (by_group, d.gid[by_group], G.h2d(by_group, dev), G.h2d(d.gid[by_group].astype(np.int32), dev),
-                             torch.from_numpy(lists).to(dev).view(4, len(d.ent), R))
-            for name, col, side, given, ranked in EVENT_DIRECTIONS:
-                by_group, gid_h, here, gid, lists = ups[name]
-                for g0, g1, block, off in _event_blocks(self, ch, name, q_rel[name], block_floats):
-                    a, b = np.searchsorted(gid_h, (g0, g1))
-                    pos = ch.c + here[a:b]                                                  # positions of idx, group-major
-                    grp = gid[a:b] - g0
-                    gr, gc = gold[1][pos].contiguous(), gold[ranked][pos].contiguous()
-                    rows = lists[:, g0:g1][:, grp.long()].reshape(4, -1).contiguous()       # [4, Q * R]: per (query, relation)
-                    cnt, at_gold, listed, _ = K.joint_rank_rows(block, R, off, grp.contiguous(), gr, gc, cols[side][0], rows[0],
-                                                                rows[1], cols[side][1], rows[2], rows[3])
-                    pair[:, pos, col] = cnt
-                    v = at_gold.gather(1, gr.long().view(-1, 1))
-                    logp[pos, col] = v.view(-1)
-                    own = rels == gr.long().view(-1, 1)
-                    for k, keep in enumerate((None, (listed[0] == 0) | own, (listed[1] == 0) | own)):
-                        gt, eq = at_gold > v, at_gold == v
-                        rel[2 * k, pos, col] = (gt if keep is None else gt & keep).sum(dim=1)
-                        rel[2 * k + 1, pos, col] = (eq if keep is None else eq & keep).sum(dim=1)
+    for ch in chunks:
+        # every host lookup of the chunk, and its upload, before the first sub-block runs
+        ups = {}
+        for name, col, side, given, ranked in EVENT_DIRECTIONS:
+            d = ch.dirs[name]
+            by_group = np.argsort(d.gid, kind='stable')                                # the chunk's positions, group-major
+            lists = np.stack(index.ranges_both_host(side, _event_known(d, R))).astype(np.int32)
+            ups[name] = (by_group, d.gid[by_group], G.h2d(by_group, dev), G.h2d(d.gid[by_group].astype(np.int32), dev),
+                         torch.from_numpy(lists).to(dev).view(4, len(d.ent), R))
+        for name, col, side, given, ranked in EVENT_DIRECTIONS:
+            by_group, gid_h, here, gid, lists = ups[name]
+            for g0, g1, block, off in blocks(ch, name):
+                a, b = np.searchsorted(gid_h, (g0, g1))
+                pos = ch.c + here[a:b]                                                  # positions of idx, group-major
+                grp = gid[a:b] - g0
+                gr, gc = gold[1][pos].contiguous(), gold[ranked][pos].contiguous()
+                rows = lists[:, g0:g1][:, grp.long()].reshape(4, -1).contiguous()       # [4, Q * R]: per (query, relation)
+                cnt, at_gold, listed, _ = K.joint_rank_rows(block, R, off, grp.contiguous(), gr, gc, cols[side][0], rows[0],
+                                                            rows[1], cols[side][1], rows[2], rows[3])
+                pair[:, pos, col] = cnt
+                v = at_gold.gather(1, gr.long().view(-1, 1))
+                logp[pos, col] = v.view(-1)
+                own = rels == gr.long().view(-1, 1)
+                for k, keep in enumerate((None, (listed[0] == 0) | own, (listed[1] == 0) | own)):
+                    gt, eq = at_gold > v, at_gold == v
+                    rel[2 * k, pos, col] = (gt if keep is None else gt & keep).sum(dim=1)
+                    rel[2 * k + 1, pos, col] = (eq if keep is None else eq & keep).sum(dim=1)
     # ONE copy: the counts of both kinds and logp as [13, n, 2] float64 (counts and fp32 values are exact in it)
     back = torch.cat((pair.double(), rel.double(), logp.double().view(1, n, 2))).cpu().numpy()
     ranks = [{name: c[2 * k] + (c[2 * k + 1] - 1.0) / 2 + 1 for k, name in enumerate(SETTINGS)} for c in (back[0:6], back[6:12])]
     return {'pair': ranks[0], 'relation': ranks[1], 'logp': back[12].astype(np.float32)}
 
 
-def _predict_events_observed(self, obs, idx, k=10, all_triplets=None, setting='raw', sides=('sub', 'ob')):
+def _predict_events_observed(self, obs, idx, k=10, all_triplets=None, setting='raw', sides=('sub', 'ob'), prior=None):
     """The k most probable events of the stream positions idx under observed histories: {'ob': (rel int32 [n, k], ent int32
     [n, k], logp [n, k], n_valid int32 [n]), 'sub': (...)} as device tensors -- for 'ob' the pairs (r, o) of the position's
     subject, for 'sub' the pairs (r, s) of its object, by joint log-probability J descending, then relation, then entity
@@ -1765,47 +1807,58 @@ def _predict_events_observed(self, obs, idx, k=10, all_triplets=None, setting='r
     (a pair outside its own row's k best by SCORE cannot enter: exact unless two distinct scores of a row round to one J at
     that row's k-th place).  k <= 1024; N_ent <= 2^20 (renet_hip.topk_rows: beyond 32768 entities the rows are taken in
     pieces by renet_topk_rows_wide, with the same results).  sides: the directions to compute; one left out costs no
-    block and is missing from the result."""
+    block and is missing from the result.  prior: as in evaluate_events_observed -- the k best of the mixed joint, logp its
+    log-probability, bit for bit B + off of observed_event_scores(prior=)."""
     if setting not in SETTINGS:
         raise ValueError('setting must be one of %s, not %r' % (', '.join(SETTINGS), setting))
     store, idx = _event_setup(self, obs, idx)
-    dev, n, R, N, k = self.ent_embeds.device, len(idx), self.num_rels, self.in_dim, int(k)
+    mix = _event_mix(prior)
+    dev = self.ent_embeds.device
+    with torch.no_grad():
+        q_rel = _event_q_rel(self)
+        return _topk_events(store, idx, int(k), self.num_rels, self.in_dim, dev, all_triplets, setting, sides,
+                            _event_chunks(self, store, idx, mix),
+                            lambda ch, name: _event_blocks(self, ch, name, q_rel[name], 1 << 28, mix))
+
+
+def _topk_events(store, idx, k, R, N, dev, all_triplets, setting, sides, chunks, blocks):
+    """The top-k tail of predict_events_observed over any source of joint blocks (chunks / blocks as in _rank_events);
+    recurrence.topk_events runs it over uniform blocks.  Called under no_grad."""
+    n = len(idx)
     index = FI.filter_index_for(store, all_triplets if all_triplets is not None else store.quads) if setting != 'raw' else None
     out = {name: (torch.full((n, k), -1, device=dev, dtype=torch.int32), torch.full((n, k), -1, device=dev, dtype=torch.int32),
                   torch.full((n, k), -np.inf, device=dev), torch.zeros(n, device=dev, dtype=torch.int32))
            for name in ('ob', 'sub') if name in sides}
-    with torch.no_grad():
-        q_rel = _event_q_rel(self)
-        for ch in _event_chunks(self, store, idx):
-            for name, col, side, given, ranked in EVENT_DIRECTIONS:
-                if name not in sides:
-                    continue
-                d = ch.dirs[name]
-                lists = (None, None, None)
-                if index is not None:
-                    keys = _event_known(d, R)
-                    lists = index.ranges(side, keys if setting == 'time_filtered' else keys[:, :2], dev)
-                gid = G.h2d(d.gid, dev)
-                for g0, g1, block, off in _event_blocks(self, ch, name, q_rel[name], 1 << 28):
-                    m = g1 - g0
-                    row_lists = (lists[0], lists[1][g0 * R:g1 * R].contiguous(), lists[2][g0 * R:g1 * R].contiguous()) \
-                        if index is not None else lists
-                    ent, val, _, _ = K.topk_rows(block, k, *row_lists, want_logp=False)      # [m * R, k] each
-                    cand = (val + off.view(-1, 1)).view(m, R * k)                           # J, fp32; empty slots -inf
-                    ent = ent.view(m, R * k).long()
-                    code = torch.where(ent >= 0, _event_slot_rels(R, k, dev) * N + ent, R * N)      # relation-major, entity ascending
-                    by_code = torch.sort(code, dim=1, stable=True)[1]
-                    best = torch.sort(cand.gather(1, by_code), dim=1, descending=True, stable=True)[1][:, :k]
-                    take = by_code.gather(1, best)                                          # [m, min(k, R * k)]
-                    j, e = cand.gather(1, take), ent.gather(1, take)
-                    ok = e >= 0
-                    here = torch.nonzero((gid >= g0) & (gid < g1)).view(-1)
-                    grp = gid[here] - g0
-                    o_rel, o_ent, o_logp, o_n = out[name]
-                    o_rel[ch.c + here] = torch.where(ok, torch.div(take, k, rounding_mode='floor'), -1).int()[grp]
-                    o_ent[ch.c + here] = e.int()[grp]
-                    o_logp[ch.c + here] = torch.where(ok, j, -np.inf)[grp]
-                    o_n[ch.c + here] = ok.sum(dim=1).int()[grp]
+    for ch in chunks:
+        for name, col, side, given, ranked in EVENT_DIRECTIONS:
+            if name not in sides:
+                continue
+            d = ch.dirs[name]
+            lists = (None, None, None)
+            if index is not None:
+                keys = _event_known(d, R)
+                lists = index.ranges(side, keys if setting == 'time_filtered' else keys[:, :2], dev)
+            gid = G.h2d(d.gid, dev)
+            for g0, g1, block, off in blocks(ch, name):
+                m = g1 - g0
+                row_lists = (lists[0], lists[1][g0 * R:g1 * R].contiguous(), lists[2][g0 * R:g1 * R].contiguous()) \
+                    if index is not None else lists
+                ent, val, _, _ = K.topk_rows(block, k, *row_lists, want_logp=False)      # [m * R, k] each
+                cand = (val + off.view(-1, 1)).view(m, R * k)                           # J, fp32; empty slots -inf
+                ent = ent.view(m, R * k).long()
+                code = torch.where(ent >= 0, _event_slot_rels(R, k, dev) * N + ent, R * N)      # relation-major, entity ascending
+                by_code = torch.sort(code, dim=1, stable=True)[1]
+                best = torch.sort(cand.gather(1, by_code), dim=1, descending=True, stable=True)[1][:, :k]
+                take = by_code.gather(1, best)                                          # [m, min(k, R * k)]
+                j, e = cand.gather(1, take), ent.gather(1, take)
+                ok = e >= 0
+                here = torch.nonzero((gid >= g0) & (gid < g1)).view(-1)
+                grp = gid[here] - g0
+                o_rel, o_ent, o_logp, o_n = out[name]
+                o_rel[ch.c + here] = torch.where(ok, torch.div(take, k, rounding_mode='floor'), -1).int()[grp]
+                o_ent[ch.c + here] = e.int()[grp]
+                o_logp[ch.c + here] = torch.where(ok, j, -np.inf)[grp]
+                o_n[ch.c + here] = ok.sum(dim=1).int()[grp]
     return out
 
 
@@ -1908,12 +1961,13 @@ def _evaluate_forecast(self, obs, queries, as_of=None, all_triplets=None, max_ba
                               max_batch, relation, prior)
 
 
-def _forecast_events(self, obs, ents, t, k=10, direction='ob', all_triplets=None, setting='raw', as_of=None):
+def _forecast_events(self, obs, ents, t, k=10, direction='ob', all_triplets=None, setting='raw', as_of=None, prior=None):
     """The k most probable events of the entities `ents` [n] at time(s) t (a scalar or [n]; it may lie past the stream's
     end): (rel int32 [n, k], ent int32 [n, k], logp [n, k], n_valid int32 [n]) as predict_events_observed gives per
     direction -- 'ob': the pairs (r, o) of ents as subjects, 'sub': the pairs (r, s) of ents as objects.  Runs
     predict_events_observed over a QueryStore whose relation column is 0 (history, RGCN rows and encoder_r's state do not
-    depend on it) and whose other side is absent; the other direction is not computed."""
+    depend on it) and whose other side is absent; the other direction is not computed.  prior: as in
+    predict_events_observed; the as_of that cuts the histories cuts the prior -- a stale history gets a stale prior."""
     if direction not in ('ob', 'sub'):
         raise ValueError("direction must be 'ob' or 'sub'")
     if isinstance(ents, torch.Tensor) and ents.is_cuda:
@@ -1930,7 +1984,7 @@ def _forecast_events(self, obs, ents, t, k=10, direction='ob', all_triplets=None
             raise ValueError('forecast_events: entity id outside [0, num_ent)')
     qs = _query_store(obs, quads, as_of)
     return _predict_events_observed(self, qs, np.arange(qs.n_quads), k, all_triplets if all_triplets is not None else qs.facts,
-                                    setting, sides=(direction,))[direction]
+                                    setting, sides=(direction,), prior=prior)[direction]
 
 
 # =================================================================================================

@@ -302,6 +302,33 @@ class PairIndex(object):
         return (np.asarray(ptr, dtype=np.int64), np.concatenate(col) if col else np.zeros(0, dtype=np.int64),
                 np.concatenate(w) if w else np.zeros(0, dtype=np.float64))
 
+    def event_rows(self, ent, t, as_of, half_life=None, inv_half_life=None):
+        """The JOINT recurrence statistic of the histories (ent, t) [n] as of as_of (<= t), every relation at once: CSR lists
+        (ptr int64 [n + 1], rel int64, col int64, w float64), row i holding, in ascending (relation, partner) order, every
+        pair (r, o) of a fact (ent_i, r, o, t') with t' < as_of_i and w[r, o] = sum over those facts of 2^(-(t_i - t') *
+        inv_half_life).  The row's sum of w is the entity-wide W of renet_joint_mix_rows; restricted to one relation r the
+        row is prior_rows(ent, r, ...)'s, list for list.  half_life / inv_half_life and every other convention as in
+        prior_rows; an entity outside [0, num_ent) has an empty row.  The host statement, with
+        tests/event_prior_statement.py, of renet_joint_mix_rows."""
+        ent, t = (np.asarray(x, dtype=np.int64).reshape(-1) for x in (ent, t))
+        as_of = np.broadcast_to(np.asarray(as_of, dtype=np.int64).reshape(-1), ent.shape)
+        ihl = float(inv_half_life) if inv_half_life is not None else (0.0 if half_life is None else 1.0 / float(half_life))
+        ptr, rel, col, w = [0], [], [], []
+        for i in range(len(ent)):
+            a, b = (int(self.run_ptr[ent[i]]), int(self.run_ptr[ent[i] + 1])) if 0 <= ent[i] < self.num_ent else (0, 0)
+            seen = self.p_t[a:b] < as_of[i]
+            r, o, tp = self.p_rel[a:b][seen], self.p_other[a:b][seen], self.p_t[a:b][seen]
+            n = 0
+            if len(o):
+                pairs, inv = np.unique(np.stack((r, o), axis=1), axis=0, return_inverse=True)      # ascending (relation, partner)
+                n = len(pairs)
+                rel.append(pairs[:, 0])
+                col.append(pairs[:, 1])
+                w.append(np.bincount(inv.reshape(-1), weights=np.exp2(-(t[i] - tp).astype(np.float64) * ihl), minlength=n))
+            ptr.append(ptr[-1] + n)
+        cat = lambda parts, dtype: np.concatenate(parts) if parts else np.zeros(0, dtype=dtype)
+        return np.asarray(ptr, dtype=np.int64), cat(rel, np.int64), cat(col, np.int64), cat(w, np.float64)
+
     def prior_stats(self, ent, rel, t, as_of):
         """int64 [n, 2] = (distinct partners seen before as_of, facts counted) of every query: the integers
         renet_recurrence_mix_rows reports."""

@@ -28,7 +28,25 @@ RENet.learn_observed(..., prior=, gate_optimizer=) train the model (and the gate
 alone.  A step with copy= is not in the C launch list (csrc/step.cpp): it pays the autograd path's host enqueue.  Numbers
 with a LEARNED gate are a protocol of their own: comparable only with numbers of the same protocol and the same fitting data.
 
-Not covered: rollout (generated facts in a prior are a protocol question of their own), the joint event paths, a
+EVENTS.  The event entries (RENet.evaluate_events_observed, predict_events_observed, observed_event_scores, forecast_events)
+rank a (relation, entity) PAIR among R * N_ent candidates; their `prior=` keyword mixes the JOINT statistic into the joint
+log-probabilities J of a history (a "group": the given entity e, t, as_of) with one renet_joint_mix_rows call per sub-block,
+between renet_joint_row_offsets and the rank / top-k launches:
+
+    M[r, c] = log((1 - a) exp(J[r, c]) + a w[r, c] / W),   w[r, c] = sum over the facts (e, r, c, t' < as_of) of
+                                                                      2^(-(t - t') / half_life),   W = sum of ALL w of e
+
+W is entity-wide -- "s does again what it did before, with whom it did it", whatever the relation -- so exp(M) is a
+distribution over the pairs as exp(J) is, and a = alpha where e has any history before as_of, else 0.  A RecurrencePrior is
+taken as it is; a CopyGate(per_relation=False) as its side's single gate, read to the host once per call; a per-relation
+CopyGate is refused: with the relation open, a gate per relation does not give a normalised joint.  `evaluate_events` is the
+MODEL-FREE baseline in evaluate_events_observed's layout (the uniform joint through the same mix entry, groups, filter lists
+and tie rule).  The baseline's and the mixed event numbers go beside event numbers of the SAME protocol only, and with their
+alpha and half_life.  `topk_events` is the baseline's top-k in predict_events_observed's layout, through that entry's own tail.
+
+Not covered: rollout (generated facts in a prior are a protocol question of their own; generate_events_observed and
+evaluate_rollout take no prior: generation stays the model's own), training through the joint mix, a learned per-relation
+gate for events, fusing the mix into renet_joint_row_offsets or the rank kernel (measured first: profiles/event_prior.md), a
 relation-free term, a learned half-life, bf16-storage mode, data-parallel gate gradients."""
 import math
 
@@ -229,6 +247,59 @@ def _checked(prior):
     return prior
 
 
+def event_alphas(prior):
+    """{'ob': a, 'sub': a}: the scalar weight of the JOINT mix per direction.  A RecurrencePrior gives its alpha for both; a
+    CopyGate(per_relation=False) its side's single gate (checked, then read to the host: one small copy per call).  A
+    per-relation CopyGate is refused: the joint mix takes ONE gate per history."""
+    _checked(prior)
+    if not isinstance(prior, CopyGate):
+        return {name: prior.alpha for name in SIDES}
+    if prior.per_relation:
+        raise ValueError('the event entries take a RecurrencePrior or a CopyGate(per_relation=False), not a per-relation gate: '
+                         'with the relation open, a gate per relation does not give a normalised joint')
+    tab = prior.check().table().detach().reshape(-1).cpu().numpy()                  # [2]: the 'ob' gate, the 'sub' gate
+    return {name: float(np.float32(tab[row])) for name, row in SIDES.items()}
+
+
+def event_alpha(prior, name):
+    """event_alphas(prior)[name] for the direction name ('ob': pairs (r, o) of a subject, 'sub': pairs (r, s) of an object)."""
+    if name not in SIDES:
+        raise ValueError("direction must be 'ob' or 'sub'")
+    return event_alphas(prior)[name]
+
+
+class EventMix(object):
+    """What the `prior=` keyword of the event entries carries through one call: the two directions' alpha (event_alphas, read
+    once), inv_half_life, and -- from the first groups() on -- the base store whose pair tables are read."""
+
+    def __init__(self, prior):
+        self.alpha = event_alphas(prior)
+        self.inv_half_life = prior.inv_half_life
+        self.base = None
+
+    def groups(self, store, ent, t, first):
+        """(ent, t, as_of) of the groups of one direction of a chunk, int32 device [G]: ent, t host arrays; first [G] the store
+        position whose history window is the group's -- its as_of on a QueryStore, the group's own t on an ObservedStore."""
+        dev = store.device
+        if self.base is None:
+            self.base, self.tables = getattr(store, 'base', store), store.pair_tables()
+        et = torch.from_numpy(np.ascontiguousarray(np.stack((ent, t)), dtype=np.int32)).to(dev)
+        if 'as_of' in store.t:
+            as_of = store.t['as_of'][torch.from_numpy(np.ascontiguousarray(first, dtype=np.int64)).to(dev)].contiguous()
+        else:
+            as_of = et[1]
+        return et[0], et[1], as_of
+
+    def apply(self, name, block, off, q, g0=0, g1=None, mass=None):
+        """ONE renet_joint_mix_rows call on the sub-block (block [(g1 - g0) * R, C], off) of the groups [g0, g1) of direction
+        `name`, in place; q: groups()' triple of the whole direction.  -> mass."""
+        g1 = int(q[0].numel()) if g1 is None else g1
+        role, t = SIDES[name], self.base.t
+        return K.joint_mix_rows(block, block.shape[0] // max(g1 - g0, 1), off, q[0][g0:g1], q[1][g0:g1], q[2][g0:g1],
+                                self.tables[role], t['ent_ptr%d' % role], t['snap_ptr%d' % role], self.base.num_ent,
+                                self.alpha[name], self.inv_half_life, mass=mass)
+
+
 class CopyRows(object):
     """(a_row, q_row, W) of ONE merged training batch, for RENet.loss_prepared_both(prep, copy=): the positions idx of the
     resident store `store` (a gpu_builder.ObservedStore; as_of = t: no fact of the query's own timestamp is read) under
@@ -378,3 +449,69 @@ def topk(obs, queries, prior, k=10, all_triplets=None, setting='raw', as_of=None
             lists = index.ranges(side, np.stack((key, r, t) if setting == 'time_filtered' else (key, r), axis=1), qs.device)
         out[name] = K.topk_rows(rows.mix(prior, name, None), k, *lists, keep=None)
     return out
+
+
+def _uniform_events(obs, idx, prior, block_floats):
+    """(store, idx, R, N, dev, chunks, blocks) of the model-free event passes: the groups of RENet's event entries (positions
+    that share the given entity and the timestamp inside a chunk of gpu_builder.MAX_BOTH positions) and, per sub-block of at
+    most block_floats floats, a ZERO block with the offset -log(R * N_ent) through renet_joint_mix_rows."""
+    import gpu_builder
+    import model as M
+    store = M._observed_store(obs)
+    idx = M._observed_positions(store, idx)
+    R, N, dev = store.num_rels, store.num_ent, store.device
+    if R > 1024:
+        raise ValueError('event forecasts take at most 1024 relations (renet_joint_row_offsets)')
+    mix = EventMix(prior)
+    per = max(1, int(block_floats) // max(R * N, 1))
+    flat = float(-np.log(float(R) * float(N)))
+
+    def chunks():
+        step = gpu_builder.MAX_BOTH
+        for c in range(0, len(idx), step):
+            ch = M._EventChunk()
+            pos = idx[c:c + step]
+            ch.c, ch.n = c, len(pos)
+            M._event_groups(ch, store, pos, np.arange(2 * len(pos)), mix)
+            yield ch
+
+    def blocks(ch, name):
+        d = ch.dirs[name]
+        for g0 in range(0, len(d.ent), per):
+            g1 = min(len(d.ent), g0 + per)
+            block = torch.zeros((g1 - g0) * R, N, device=dev)
+            off = torch.full(((g1 - g0) * R,), flat, device=dev)
+            mix.apply(name, block, off, d.q, g0, g1)
+            yield g0, g1, block, off
+    return store, idx, R, N, dev, chunks(), blocks
+
+
+def evaluate_events(obs, idx, prior, all_triplets=None, block_floats=1 << 28):
+    """The model-free EVENT baseline under the observed protocol, in RENet.evaluate_events_observed's layout: {'pair':
+    {setting: float64 [len, 2]}, 'relation': {setting: float64 [len, 2]}, 'logp': float32 [len, 2]}, column 0 the direction
+    sub, column 1 ob.  obs / idx as there (a resident stream or store and its positions; a gpu_builder.QueryStore of labelled
+    queries with arange(n) gives stale-history numbers, its as_of cutting the prior).  The same groups, filter lists and tie
+    rule; the joint is UNIFORM, J = -log(R * N_ent): zero blocks with that offset go through renet_joint_mix_rows and
+    renet_joint_rank_rows.  No encoder, GRU or GEMM launch is made.  A group without history is one R * N_ent-way tie.  To
+    be reported with alpha and half_life, beside event numbers of the same protocol only."""
+    import model as M
+    store, idx, R, N, dev, chunks, blocks = _uniform_events(obs, idx, prior, block_floats)
+    with torch.no_grad():
+        return M._rank_events(store, idx, R, dev, all_triplets, chunks, blocks)
+
+
+def topk_events(obs, idx, prior, k=10, all_triplets=None, setting='raw', sides=('sub', 'ob'), block_floats=1 << 28):
+    """The k most probable events under the recurrence prior alone, in RENet.predict_events_observed's layout: {'ob': (rel
+    int32 [n, k], ent int32 [n, k], logp [n, k], n_valid int32 [n]), 'sub': (...)} as device tensors -- the given entity's
+    most frequent (and, with a half-life, most recent) (relation, partner) pairs before as_of, then the unseen pairs, which
+    all tie, by relation and entity ascending.  setting / all_triplets / sides as there; it runs predict_events_observed's own
+    tail on the mixed uniform blocks of evaluate_events."""
+    import model as M
+    if setting not in SETTINGS:
+        raise ValueError('setting must be one of %s, not %r' % (', '.join(SETTINGS), setting))
+    sides = tuple(sides)
+    if not sides or any(name not in SIDES for name in sides):
+        raise ValueError("sides must name 'sub', 'ob' or both")
+    store, idx, R, N, dev, chunks, blocks = _uniform_events(obs, idx, prior, block_floats)
+    with torch.no_grad():
+        return M._topk_events(store, idx, int(k), R, N, dev, all_triplets, setting, sides, chunks, blocks)

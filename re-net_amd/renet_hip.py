@@ -185,6 +185,8 @@ _SIGNATURES = {
                                                 c_int, c_void_p, c_int, c_int, c_void_p, c_float] + [c_void_p] * 4),
     'renet_recurrence_gold_rows': (c_int, [c_void_p] * 5 + [c_int] + [c_void_p] * 3 + [c_int, c_void_p, c_void_p, c_int, c_int,
                                            c_int, c_float] + [c_void_p] * 3),
+    'renet_joint_mix_rows': (c_int, [c_void_p] * 3 + [c_int] + [c_void_p] * 3 + [c_int, c_void_p, c_void_p, c_int, c_int,
+                                     c_void_p, c_int, c_int, c_int, c_void_p, c_float, c_float, c_void_p, c_void_p]),
     'renet_mix_ce': (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_float] + [c_void_p] * 4),
     'renet_mix_ce_planes': (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_size_t, c_int, c_int,
                                     c_void_p, c_void_p]),
@@ -1864,6 +1866,42 @@ def joint_row_offsets(scores, num_rels, logits_r):
                                          _block_ld(logits_r), off.data_ptr(), _stream()), 'joint_row_offsets')
     _timed_end(t0, 'joint_row_offsets', nbytes=float(rows * c * 4))
     return off
+
+
+def joint_mix_rows(scores, num_rels, off, ent, t, as_of, tables, ent_ptr, snap_ptr, num_ent, alpha, inv_half_life=0.0,
+                   mass=None):
+    """renet_joint_mix_rows: the recurrence prior mixed into the joint block scores [G * R, C] (fp32, unit inner stride) and its
+    offsets off [G * R] (joint_row_offsets) IN PLACE -> mass (fp64 device [G]; the tensor given, or a fresh one).  Group g is the
+    history of the entity ent[g] at t[g] as of as_of[g] (int32 device [G]); tables = (p_rel, p_other, p_t), ent_ptr and snap_ptr
+    those of the GIVEN entity's role.  With w[r, c] the 2^(-(t - t') inv_half_life)-weighted count of the facts (ent, r, c, t' <
+    as_of), W (= mass[g]) their sum over every relation and a = alpha where W > 0, else 0, and J = scores + off[row] in fp32:
+        M = J + log1p(-a) for a pair without a counted fact,  M = log((1 - a) exp(J) + a w[r, c] / W) for one with,
+    in fp64, rounded once.  Where a > 0 (and for alpha = 0 where W > 0) scores holds M and off is 0 afterwards, so that
+    joint_rank_rows / topk_rows + off read the mixed joint unchanged; a group without history keeps rows and off bit for bit.
+    0 <= alpha < 1; R <= 1024."""
+    if not (scores.is_cuda and scores.dtype == torch.float32 and scores.dim() == 2 and scores.stride(1) == 1):
+        raise RenetHipError('joint_mix_rows needs a 2-D float32 device tensor with unit inner stride')
+    rows, c = scores.shape
+    r = int(num_rels)
+    g = int(ent.numel())
+    if r < 1 or rows != g * r or off.numel() != rows or t.numel() != g or as_of.numel() != g:
+        raise RenetHipError('joint_mix_rows: shape mismatch')
+    p_rel, p_other, p_t = tables
+    nf = int(p_rel.numel())
+    if p_other.numel() != nf or p_t.numel() != nf or ent_ptr.numel() != int(num_ent) + 1:
+        raise RenetHipError('joint_mix_rows: the pair tables do not fit num_ent / their own lengths')
+    if mass is None:
+        mass = torch.empty(g, device=scores.device, dtype=torch.float64)
+    elif not (mass.is_cuda and mass.dtype == torch.float64 and mass.is_contiguous() and mass.numel() == g):
+        raise RenetHipError('joint_mix_rows: mass must be a contiguous float64 device tensor, one per group')
+    t0 = _timed()
+    _check(lib().renet_joint_mix_rows(_i32(ent, 'ent'), _i32(t, 't'), _i32(as_of, 'as_of'), g,
+                                      *[_i32(a, 'pair table') if nf else None for a in tables], nf, _i32(ent_ptr, 'ent_ptr'),
+                                      _i32(snap_ptr, 'snap_ptr'), int(snap_ptr.numel()) - 1, int(num_ent), scores.data_ptr(),
+                                      _block_ld(scores), r, int(c), _f32(off, 'off'), float(alpha), float(inv_half_life),
+                                      mass.data_ptr(), _stream()), 'joint_mix_rows')
+    _timed_end(t0, 'joint_mix_rows', nbytes=float(rows * c * 8))
+    return mass
 
 
 SELECT_EVENTS_MAX = 1024               # renet_select_events: R, k and num_k at most this

@@ -57,6 +57,10 @@ with numbers of the same protocol and the same fitting data.  A learn step throu
 --events adds the EVENT forecasts (RENet.evaluate_events_observed): MRR / Hits of the gold (relation, entity) pair among all
 pairs of the given entity, and of the gold relation given both endpoints, in the three settings; with K also the K most
 probable (relation, object) pairs of the first few queries (RENet.predict_events_observed, time-aware filtered).
+--events with --recurrence ALPHA [--half-life H] prints three event blocks of one protocol, each labelled with ALPHA and the
+half-life: the model-free recurrence baseline (recurrence.evaluate_events), the model mixed with the JOINT prior
+(evaluate_events_observed(prior=)) and the model alone; the JSON record gains `recurrence`, `baseline` and `mixed`.  The
+histories (and the prior) are as of each query's own timestamp, as for --events alone.
 
 DATA_DIR holds stat.txt, train.txt, valid.txt (optional) and test.txt.  From the model directory (default: models/<name of
 DATA_DIR>, where the reference's drivers write) only the weights are read: `rgcn.pth` (train.py:189) and the global model's
@@ -426,20 +430,37 @@ def main():
                                                       'fitted_on': 'valid', 'fit_steps': args.fit_gate, 'gate_lr': args.gate_lr},
                                   mixed_learned_gate={name: U.rank_metrics(gate_ranks[name]) for name in SETTINGS})))
     if args.events is not None:
-        t3 = time.perf_counter()
-        ev = model.evaluate_events_observed(obs, idx)
-        torch.cuda.synchronize()
-        dt = time.perf_counter() - t3
-        print('event forecasts, columns (given o: pairs (r, s) | given s: pairs (r, o)): pass %.2f s (%.0f quadruples/s), '
-              'mean log p of the gold event %.4f | %.4f' % ((dt, len(idx) / max(dt, 1e-9)) + tuple(ev['logp'].mean(axis=0))))
-        for kind, what in (('pair', 'pair (r, entity) among R x N_ent'), ('relation', 'relation given both endpoints')):
-            for name in SETTINGS:
-                m = U.rank_metrics(ev[kind][name])
-                print('%-30s %-14s MRR %.6f  MR %.3f  Hits@1 %.6f  Hits@3 %.6f  Hits@10 %.6f'
-                      % (what, name, m['mrr'], m['mr'], m['hits@1'], m['hits@3'], m['hits@10']))
-        print(json.dumps({'protocol': 'observed', 'task': 'events', 'split': args.split, 'n': int(len(idx)),
-                          'metrics': {kind: {name: U.rank_metrics(ev[kind][name]) for name in SETTINGS}
-                                      for kind in ('pair', 'relation')}}))
+        def event_pass(label, run):
+            t3 = time.perf_counter()
+            ev = run()
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t3
+            print('%s, columns (given o: pairs (r, s) | given s: pairs (r, o)): pass %.2f s (%.0f quadruples/s), '
+                  'mean log p of the gold event %.4f | %.4f' % ((label, dt, len(idx) / max(dt, 1e-9)) + tuple(ev['logp'].mean(axis=0))))
+            for kind, what in (('pair', 'pair (r, entity) among R x N_ent'), ('relation', 'relation given both endpoints')):
+                for name in SETTINGS:
+                    m = U.rank_metrics(ev[kind][name])
+                    print('%-30s %-14s MRR %.6f  MR %.3f  Hits@1 %.6f  Hits@3 %.6f  Hits@10 %.6f'
+                          % (what, name, m['mrr'], m['mr'], m['hits@1'], m['hits@3'], m['hits@10']))
+            return {kind: {name: U.rank_metrics(ev[kind][name]) for name in SETTINGS} for kind in ('pair', 'relation')}
+
+        event_record = {'protocol': 'observed', 'task': 'events', 'split': args.split, 'n': int(len(idx))}
+        if args.recurrence is None:
+            event_record['metrics'] = event_pass('event forecasts', lambda: model.evaluate_events_observed(obs, idx))
+        else:
+            # three blocks of ONE protocol (histories as of each query's own t, the same groups, filter lists and tie rule),
+            # each labelled with the prior's alpha and half-life: they go beside each other and beside nothing else
+            import recurrence
+            prior = recurrence.RecurrencePrior(args.recurrence, args.half_life)
+            tag = 'alpha %g, half-life %s' % (prior.alpha, 'none (frequency only)' if prior.half_life is None else '%g' % prior.half_life)
+            event_record['recurrence'] = {'alpha': prior.alpha, 'half_life': prior.half_life}
+            event_record['baseline'] = event_pass('event forecasts, RECURRENCE BASELINE ALONE (no model), %s' % tag,
+                                                  lambda: recurrence.evaluate_events(obs, idx, prior))
+            event_record['mixed'] = event_pass('event forecasts, MODEL MIXED WITH THE RECURRENCE PRIOR, %s' % tag,
+                                               lambda: model.evaluate_events_observed(obs, idx, prior=prior))
+            event_record['metrics'] = event_pass('event forecasts, THE MODEL ALONE (beside the blocks at %s)' % tag,
+                                                 lambda: model.evaluate_events_observed(obs, idx))
+        print(json.dumps(event_record))
         if args.events > 0:
             few = idx[:5]
             rel, ent, logp, n_valid = (x.cpu().numpy() for x in
