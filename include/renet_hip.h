@@ -922,7 +922,23 @@ int renet_append_i32(const int32_t* old, int n_old, const int32_t* add, int n_ad
  *            facts are those with t' < as_of
  * q = 0 and W = 0 where the pair has no history before as_of or the entity lies outside [0, num_ent); q = 0 where gold lies
  * outside [0, C) or has no counted fact.  One workgroup per row, two floats out, no atomics, no workspace; refusals as for
- * renet_recurrence_mix_rows. */
+ * renet_recurrence_mix_rows.
+ *
+ * renet_recurrence_mix_rows_decay: renet_recurrence_mix_rows_gated with ONE DECAY PER ROW as well, ihl_row[i] (device fp32 [n],
+ * each finite and >= 0: the caller's to keep, as alpha_row's range is) in the place of inv_half_life -- what a learned
+ * per-relation half-life is evaluated with.  Every weight of row i is 2^(-(t - t') * ihl_row[i]): the strided pass, the
+ * per-head sums and the whole-wave sums of long groups read the row's own value.  A constant ihl_row gives the bits of
+ * renet_recurrence_mix_rows_gated; rows of one launch do not depend on each other.  A bad decay gives a non-finite row, never
+ * an address: it only feeds exp2.  Refusals as there, and a missing ihl_row.
+ *
+ * renet_recurrence_gold_rows_decay: renet_recurrence_gold_rows with the per-row decay ihl_row[i], and the derivative of q by
+ * it.  With the lag D = t - t' of a counted fact and its weight w = 2^(-D * ihl_row[i]),
+ *     G = sum over gold's facts of w,  W = sum over all of w,  GD = sum over gold's of D w,  WD = sum over all of D w
+ *     q[i]  = fp32(G / W),  W[i] = fp32(W)               (a constant ihl_row: the bits of renet_recurrence_gold_rows)
+ *     dq[i] = fp32(-ln2 * (GD * W - G * WD) / (W * W))    = d q / d ihl_row[i];  exactly 0 where W = 0 or G = 0
+ * all four sums in fp64 through the same strided shares, shuffle tree and per-wave fold; no atomics: the same bits from run to
+ * run.  With L = -log((1 - a) p_g + a q) of renet_mix_ce, dL/dq = -a * exp(L): the loss's gradient reaches the decay as
+ * dL/dq * dq.  Three floats out per row; refusals as for renet_recurrence_gold_rows, and a missing ihl_row or dq. */
 #define RENET_RECURRENCE_MAX_C (1 << 20)
 int renet_pair_append(const int32_t* p_rel, const int32_t* p_other, const int32_t* p_t, int n, const int32_t* ent_ptr,
                       const int32_t* snap_ptr, int n_snaps, const int32_t* ent_ptr_new, const int32_t* snap_ptr_new,
@@ -942,6 +958,16 @@ int renet_recurrence_gold_rows(const int32_t* ent, const int32_t* rel, const int
                                const int32_t* gold, int n, const int32_t* p_rel, const int32_t* p_other, const int32_t* p_t,
                                int n_facts, const int32_t* ent_ptr, const int32_t* snap_ptr, int n_snaps, int num_ent, int C,
                                float inv_half_life, float* q, float* W, void* stream);
+int renet_recurrence_mix_rows_decay(const int32_t* ent, const int32_t* rel, const int32_t* t, const int32_t* as_of, int n,
+                                    const int32_t* p_rel, const int32_t* p_other, const int32_t* p_t, int n_facts,
+                                    const int32_t* ent_ptr, const int32_t* snap_ptr, int n_snaps, int num_ent,
+                                    const float* logits, int ld, int C, const float* alpha_row, const float* ihl_row,
+                                    float* out, int32_t* stats, float* stats_w, void* stream);
+int renet_recurrence_gold_rows_decay(const int32_t* ent, const int32_t* rel, const int32_t* t, const int32_t* as_of,
+                                     const int32_t* gold, int n, const int32_t* p_rel, const int32_t* p_other,
+                                     const int32_t* p_t, int n_facts, const int32_t* ent_ptr, const int32_t* snap_ptr,
+                                     int n_snaps, int num_ent, int C, const float* ihl_row, float* q, float* W, float* dq,
+                                     void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * RECURRENCE PRIOR FOR EVENT FORECASTS (csrc/joint_mix.hip): the joint copy mix over (relation, entity) pairs -- "s does again

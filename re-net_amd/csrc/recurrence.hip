@@ -6,6 +6,9 @@
 //                             renet_recurrence_mix_rows_gated is the same kernel body with one gate per row
 //   renet_recurrence_gold_rows the prior mass of ONE column per row, q = w[gold] / W, and W: what the loss through the mix
 //                             needs of the prior (host statement: tests/copy_gate_statement.py gold_rows)
+//   renet_recurrence_mix_rows_decay / renet_recurrence_gold_rows_decay are the same two kernel bodies with ONE DECAY PER ROW,
+//                             ihl_row[i] in the launch scalar's place -- a learned per-relation half-life -- and, for the gold
+//                             entry, dq / d(decay) beside q (host statement: tests/half_life_statement.py)
 //
 // PAIR TABLES.  Per role the facts of entity e are the index range run(e) = [snap_ptr[ent_ptr[e]], snap_ptr[ent_ptr[e + 1]])
 // of the resident history index (renet_store_append keeps it contiguous).  The pair tables p_rel / p_other / p_t hold the
@@ -135,15 +138,17 @@ __device__ __forceinline__ void rc_lse4(const float4 v, float& m, double& s) {
 
 __device__ __forceinline__ float rc_dense(float l, double shift) { return (float)((double)l - shift); }
 
-// GATED: the gate of row i is alpha_row[i] instead of the launch's scalar; everything else is one body
-template <bool GATED>
+// GATED: the gate of row i is alpha_row[i] instead of the launch's scalar; DECAY: its decay is ihl_row[i] instead of the
+// launch's inv_half_life (steps 2 and 5 read it: the strided pass, the per-head sums, the whole-wave sums); everything else
+// is one body
+template <bool GATED, bool DECAY>
 __global__ __launch_bounds__(RC_THREADS) void recurrence_mix_rows_kernel(
     const int32_t* __restrict__ q_ent, const int32_t* __restrict__ q_rel, const int32_t* __restrict__ q_t,
     const int32_t* __restrict__ q_as_of, const int32_t* __restrict__ p_rel, const int32_t* __restrict__ p_other,
     const int32_t* __restrict__ p_t, int n_facts, const int32_t* __restrict__ ent_ptr, const int32_t* __restrict__ snap_ptr,
     int n_snaps, int num_ent, const float* __restrict__ logits, int ld, int C, float alpha,
-    const float* __restrict__ alpha_row, float inv_half_life, float* __restrict__ out, int32_t* __restrict__ stats,
-    float* __restrict__ stats_w) {
+    const float* __restrict__ alpha_row, float inv_half_life, const float* __restrict__ ihl_row, float* __restrict__ out,
+    int32_t* __restrict__ stats, float* __restrict__ stats_w) {
     __shared__ float s_m[RC_WAVES];
     __shared__ double s_s[RC_WAVES], s_w[RC_WAVES];
     __shared__ int s_np[RC_WAVES], s_nf[RC_WAVES];
@@ -151,7 +156,7 @@ __global__ __launch_bounds__(RC_THREADS) void recurrence_mix_rows_kernel(
     const int row = blockIdx.x, tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
     const int e = q_ent[row], r = q_rel[row], t = q_t[row], as_of = q_as_of[row];
-    const double ihl = (double)inv_half_life;
+    const double ihl = DECAY ? (double)ihl_row[row] : (double)inv_half_life;
 
     // 1. the (e, r) sub-run [a, b)
     int a, b;
@@ -296,53 +301,86 @@ __global__ __launch_bounds__(RC_THREADS) void recurrence_mix_rows_kernel(
 }
 
 // ---- the gold column's prior mass ---------------------------------------------------------------------------------------
+// a b - c d with BOTH products rounded (no fused multiply-add): equal products cancel to exactly 0, so a pair whose only
+// counted partner is the gold one (q = 1 whatever the decay) has dq = 0, not the rounding residue of one product
+__device__ __forceinline__ double rc_cross(double a, double b, double c, double d) {
+#pragma clang fp contract(off)
+    const double ab = a * b, cd = c * d;
+    return ab - cd;
+}
+
 // One workgroup per row, the mix kernel's steps 1 and 2 and its reduction tree for W (the same operations in the same order:
 // W here is stats_w there, bit for bit), and beside them the gold partner's group [k, cut) -- contiguous, ascending in time,
 // three binary searches -- summed in the same strided shares through the same tree.  Two floats out per row, nothing else.
+// DECAY: the row's decay is ihl_row[row], and two more sums ride the same shares and the same tree, WD = sum of D w over the
+// sub-run and GD over the gold group (D = t - t' the lag): q = G / W has dq / d(decay) = -ln2 (GD W - G WD) / W^2, a third
+// float per row.  The DECAY = false instance holds none of it: the arithmetic it had.
+template <bool DECAY>
 __global__ __launch_bounds__(RC_THREADS) void recurrence_gold_rows_kernel(
     const int32_t* __restrict__ q_ent, const int32_t* __restrict__ q_rel, const int32_t* __restrict__ q_t,
     const int32_t* __restrict__ q_as_of, const int32_t* __restrict__ q_gold, const int32_t* __restrict__ p_rel,
     const int32_t* __restrict__ p_other, const int32_t* __restrict__ p_t, int n_facts, const int32_t* __restrict__ ent_ptr,
-    const int32_t* __restrict__ snap_ptr, int n_snaps, int num_ent, int C, float inv_half_life, float* __restrict__ q_out,
-    float* __restrict__ w_out) {
+    const int32_t* __restrict__ snap_ptr, int n_snaps, int num_ent, int C, float inv_half_life,
+    const float* __restrict__ ihl_row, float* __restrict__ q_out, float* __restrict__ w_out, float* __restrict__ dq_out) {
     __shared__ double s_w[RC_WAVES], s_g[RC_WAVES];
+    __shared__ double s_wd[DECAY ? RC_WAVES : 1], s_gd[DECAY ? RC_WAVES : 1];
     const int row = blockIdx.x, tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
     const int e = q_ent[row], r = q_rel[row], t = q_t[row], as_of = q_as_of[row], g = q_gold[row];
-    const double ihl = (double)inv_half_life;
+    const double ihl = DECAY ? (double)ihl_row[row] : (double)inv_half_life;
     int a, b;
     rc_pair_run(p_rel, n_facts, ent_ptr, snap_ptr, n_snaps, num_ent, e, r, a, b);
-    double w_sum = 0.0;
+    double w_sum = 0.0, wd_sum = 0.0;
     for (int k = a + tid; k < b; k += RC_THREADS) {
         const int tp = p_t[k];
         if (tp >= as_of) continue;
-        w_sum += rc_weight(t, tp, ihl);
+        const double w = rc_weight(t, tp, ihl);
+        w_sum += w;
+        if (DECAY) wd_sum += ((double)t - (double)tp) * w;
     }
-    double g_sum = 0.0;
+    double g_sum = 0.0, gd_sum = 0.0;
     if (g >= 0 && g < C && a < b) {                                       // (uniform over the workgroup)
         const int k0 = rc_lower(p_other, a, b, g);
         const int cut = rc_lower(p_t, k0, rc_lower(p_other, k0, b, g + 1), as_of);
-        for (int j = k0 + tid; j < cut; j += RC_THREADS) g_sum += rc_weight(t, p_t[j], ihl);
+        for (int j = k0 + tid; j < cut; j += RC_THREADS) {
+            const int tp = p_t[j];
+            const double w = rc_weight(t, tp, ihl);
+            g_sum += w;
+            if (DECAY) gd_sum += ((double)t - (double)tp) * w;
+        }
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         w_sum += __shfl_xor(w_sum, o);
         g_sum += __shfl_xor(g_sum, o);
+        if (DECAY) {
+            wd_sum += __shfl_xor(wd_sum, o);
+            gd_sum += __shfl_xor(gd_sum, o);
+        }
     }
     if (lane == 0) {
         s_w[wave] = w_sum;
         s_g[wave] = g_sum;
+        if (DECAY) {
+            s_wd[wave] = wd_sum;
+            s_gd[wave] = gd_sum;
+        }
     }
     __syncthreads();
     if (tid != 0) return;
-    double W = 0.0, G = 0.0;
+    double W = 0.0, G = 0.0, WD = 0.0, GD = 0.0;
 #pragma unroll
     for (int w = 0; w < RC_WAVES; ++w) {
         W += s_w[w];
         G += s_g[w];
+        if (DECAY) {
+            WD += s_wd[w];
+            GD += s_gd[w];
+        }
     }
     w_out[row] = (float)W;
     q_out[row] = W > 0.0 ? (float)(G / W) : 0.f;
+    if (DECAY) dq_out[row] = (W > 0.0 && G > 0.0) ? (float)(-M_LN2 * rc_cross(GD, W, G, WD) / (W * W)) : 0.f;
 }
 
 inline int rc_blocks(long long n) { return (int)((n + RC_THREADS - 1) / RC_THREADS); }
@@ -380,23 +418,28 @@ extern "C" int renet_pair_append(const int32_t* p_rel, const int32_t* p_other, c
 static int recurrence_mix_front(const int32_t* ent, const int32_t* rel, const int32_t* t, const int32_t* as_of, int n,
                                 const int32_t* p_rel, const int32_t* p_other, const int32_t* p_t, int n_facts,
                                 const int32_t* ent_ptr, const int32_t* snap_ptr, int n_snaps, int num_ent, const float* logits,
-                                int ld, int C, float alpha, const float* alpha_row, bool gated, float inv_half_life, float* out,
-                                int32_t* stats, float* stats_w, void* stream) {
+                                int ld, int C, float alpha, const float* alpha_row, bool gated, float inv_half_life,
+                                const float* ihl_row, bool decay, float* out, int32_t* stats, float* stats_w, void* stream) {
     if (n < 0 || C < 1 || C > RENET_RECURRENCE_MAX_C || n_facts < 0 || n_snaps < 0 || num_ent < 0) return RENET_ERR_BADARG;
     if (!(alpha >= 0.f && alpha < 1.f) || !(inv_half_life >= 0.f) || !(inv_half_life <= FLT_MAX)) return RENET_ERR_BADARG;
     if (logits && ld < C) return RENET_ERR_BADARG;
     if ((stats == nullptr) != (stats_w == nullptr)) return RENET_ERR_BADARG;
     if (n == 0) return RENET_OK;
-    if (!ent || !rel || !t || !as_of || !out || !ent_ptr || !snap_ptr || (gated && !alpha_row)) return RENET_ERR_BADARG;
+    if (!ent || !rel || !t || !as_of || !out || !ent_ptr || !snap_ptr || (gated && !alpha_row) || (decay && !ihl_row))
+        return RENET_ERR_BADARG;
     if (n_facts > 0 && (!p_rel || !p_other || !p_t)) return RENET_ERR_BADARG;
-    if (gated)
-        RENET_LAUNCH(recurrence_mix_rows_kernel<true>, dim3(n), dim3(RC_THREADS), 0, (hipStream_t)stream, ent, rel, t, as_of,
+    if (decay)                                                            // (one gate per row as well: the learned prior's entry)
+        RENET_LAUNCH((recurrence_mix_rows_kernel<true, true>), dim3(n), dim3(RC_THREADS), 0, (hipStream_t)stream, ent, rel, t,
+                     as_of, p_rel, p_other, p_t, n_facts, ent_ptr, snap_ptr, n_snaps, num_ent, logits, ld, C, alpha, alpha_row,
+                     inv_half_life, ihl_row, out, stats, stats_w);
+    else if (gated)
+        RENET_LAUNCH((recurrence_mix_rows_kernel<true, false>), dim3(n), dim3(RC_THREADS), 0, (hipStream_t)stream, ent, rel, t, as_of,
                      p_rel, p_other, p_t, n_facts, ent_ptr, snap_ptr, n_snaps, num_ent, logits, ld, C, alpha, alpha_row,
-                     inv_half_life, out, stats, stats_w);
+                     inv_half_life, ihl_row, out, stats, stats_w);
     else
-        RENET_LAUNCH(recurrence_mix_rows_kernel<false>, dim3(n), dim3(RC_THREADS), 0, (hipStream_t)stream, ent, rel, t, as_of,
+        RENET_LAUNCH((recurrence_mix_rows_kernel<false, false>), dim3(n), dim3(RC_THREADS), 0, (hipStream_t)stream, ent, rel, t, as_of,
                      p_rel, p_other, p_t, n_facts, ent_ptr, snap_ptr, n_snaps, num_ent, logits, ld, C, alpha, alpha_row,
-                     inv_half_life, out, stats, stats_w);
+                     inv_half_life, ihl_row, out, stats, stats_w);
     RENET_LAUNCH_CHECK();
     return RENET_OK;
 }
@@ -407,7 +450,7 @@ extern "C" int renet_recurrence_mix_rows(const int32_t* ent, const int32_t* rel,
                                          const float* logits, int ld, int C, float alpha, float inv_half_life, float* out,
                                          int32_t* stats, float* stats_w, void* stream) {
     return recurrence_mix_front(ent, rel, t, as_of, n, p_rel, p_other, p_t, n_facts, ent_ptr, snap_ptr, n_snaps, num_ent, logits,
-                                ld, C, alpha, nullptr, false, inv_half_life, out, stats, stats_w, stream);
+                                ld, C, alpha, nullptr, false, inv_half_life, nullptr, false, out, stats, stats_w, stream);
 }
 
 // alpha_row is DEVICE memory: its range [0, 1) is the caller's to keep (renet_hip.recurrence_mix_rows_gated checks it where
@@ -418,7 +461,19 @@ extern "C" int renet_recurrence_mix_rows_gated(const int32_t* ent, const int32_t
                                                int num_ent, const float* logits, int ld, int C, const float* alpha_row,
                                                float inv_half_life, float* out, int32_t* stats, float* stats_w, void* stream) {
     return recurrence_mix_front(ent, rel, t, as_of, n, p_rel, p_other, p_t, n_facts, ent_ptr, snap_ptr, n_snaps, num_ent, logits,
-                                ld, C, 0.f, alpha_row, true, inv_half_life, out, stats, stats_w, stream);
+                                ld, C, 0.f, alpha_row, true, inv_half_life, nullptr, false, out, stats, stats_w, stream);
+}
+
+// alpha_row and ihl_row are DEVICE memory: the gate's range [0, 1) and the decay's (finite, >= 0) are the caller's to keep
+// (recurrence.CopyGate.check reads both tables back where they change); a bad decay gives a non-finite row, never an address:
+// it only feeds exp2
+extern "C" int renet_recurrence_mix_rows_decay(const int32_t* ent, const int32_t* rel, const int32_t* t, const int32_t* as_of,
+                                               int n, const int32_t* p_rel, const int32_t* p_other, const int32_t* p_t,
+                                               int n_facts, const int32_t* ent_ptr, const int32_t* snap_ptr, int n_snaps,
+                                               int num_ent, const float* logits, int ld, int C, const float* alpha_row,
+                                               const float* ihl_row, float* out, int32_t* stats, float* stats_w, void* stream) {
+    return recurrence_mix_front(ent, rel, t, as_of, n, p_rel, p_other, p_t, n_facts, ent_ptr, snap_ptr, n_snaps, num_ent, logits,
+                                ld, C, 0.f, alpha_row, true, 0.f, ihl_row, true, out, stats, stats_w, stream);
 }
 
 extern "C" int renet_recurrence_gold_rows(const int32_t* ent, const int32_t* rel, const int32_t* t, const int32_t* as_of,
@@ -431,8 +486,23 @@ extern "C" int renet_recurrence_gold_rows(const int32_t* ent, const int32_t* rel
     if (n == 0) return RENET_OK;
     if (!ent || !rel || !t || !as_of || !gold || !q || !W || !ent_ptr || !snap_ptr) return RENET_ERR_BADARG;
     if (n_facts > 0 && (!p_rel || !p_other || !p_t)) return RENET_ERR_BADARG;
-    RENET_LAUNCH(recurrence_gold_rows_kernel, dim3(n), dim3(RC_THREADS), 0, (hipStream_t)stream, ent, rel, t, as_of, gold, p_rel,
-                 p_other, p_t, n_facts, ent_ptr, snap_ptr, n_snaps, num_ent, C, inv_half_life, q, W);
+    RENET_LAUNCH(recurrence_gold_rows_kernel<false>, dim3(n), dim3(RC_THREADS), 0, (hipStream_t)stream, ent, rel, t, as_of, gold,
+                 p_rel, p_other, p_t, n_facts, ent_ptr, snap_ptr, n_snaps, num_ent, C, inv_half_life, nullptr, q, W, nullptr);
+    RENET_LAUNCH_CHECK();
+    return RENET_OK;
+}
+
+extern "C" int renet_recurrence_gold_rows_decay(const int32_t* ent, const int32_t* rel, const int32_t* t, const int32_t* as_of,
+                                                const int32_t* gold, int n, const int32_t* p_rel, const int32_t* p_other,
+                                                const int32_t* p_t, int n_facts, const int32_t* ent_ptr, const int32_t* snap_ptr,
+                                                int n_snaps, int num_ent, int C, const float* ihl_row, float* q, float* W,
+                                                float* dq, void* stream) {
+    if (n < 0 || C < 1 || C > RENET_RECURRENCE_MAX_C || n_facts < 0 || n_snaps < 0 || num_ent < 0) return RENET_ERR_BADARG;
+    if (n == 0) return RENET_OK;
+    if (!ent || !rel || !t || !as_of || !gold || !ihl_row || !q || !W || !dq || !ent_ptr || !snap_ptr) return RENET_ERR_BADARG;
+    if (n_facts > 0 && (!p_rel || !p_other || !p_t)) return RENET_ERR_BADARG;
+    RENET_LAUNCH(recurrence_gold_rows_kernel<true>, dim3(n), dim3(RC_THREADS), 0, (hipStream_t)stream, ent, rel, t, as_of, gold,
+                 p_rel, p_other, p_t, n_facts, ent_ptr, snap_ptr, n_snaps, num_ent, C, 0.f, ihl_row, q, W, dq);
     RENET_LAUNCH_CHECK();
     return RENET_OK;
 }

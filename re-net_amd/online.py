@@ -105,6 +105,8 @@ def _learn_observed(self, obs, idx, optimizer, steps=1, batch_size=1024, grad_no
             raise ValueError('learn_observed: gate_optimizer needs prior= to be a recurrence.CopyGate')
         if getattr(self, 'gemm_mode', None) == 'bf16s' or K.current_mode() == 'bf16s':
             raise ValueError('learn_observed: prior= has no bf16-storage writer: use another GEMM mode')
+        if isinstance(prior, recurrence.CopyGate):
+            prior.check()                                               # (a non-finite parameter is refused before any launch)
     elif gate_optimizer is not None:
         raise ValueError('learn_observed: gate_optimizer without prior=')
     store = M._observed_store(obs)

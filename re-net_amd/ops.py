@@ -753,7 +753,8 @@ class HeadCEFn(Function):
     def forward(ctx, a, ia, hmid, c, ic, weight, bias, target, plan_a, plan_c, drop_p, seed, loss_scale=1.0, copy_a=None,
                 copy_q=None):
         """copy_a / copy_q (both or neither; fp32 [B]): the loss through the copy mix (see _head_forward); copy_a may
-        require grad -- a learned gate -- and receives g * d_a.  Neither: today's path, launch for launch."""
+        require grad -- a learned gate -- and receives g * d_a; copy_q may require grad -- a learned decay -- and receives
+        g * d_q (copy_q_grad), else None.  Neither: today's path, launch for launch."""
         ctx.srcs = (a, c, weight, bias)
         copy = _copy_pair(copy_a, copy_q, hmid.shape[0])
         a, hmid, weight, bias = _c(a), _c(hmid), _c(weight), _c(bias)
@@ -765,6 +766,7 @@ class HeadCEFn(Function):
         ctx.grad_scale = float(loss_scale) / b
         row_loss, feat, logits, ctx.dl_bf16, feat_op, ctx.d_gate = _head_forward(
             a, ia, hmid, c, ic, weight, bias, target, drop_p, seed, ctx.grad_scale, need_grad, copy=copy)
+        ctx.d_q = copy_q_grad(copy[0], row_loss, ctx.grad_scale) if copy is not None and ctx.needs_input_grad[14] else None
         ctx.meta = (d, 3 if c is not None else 2, drop_p, seed, plan_a, plan_c, a.shape,
                     c.shape if c is not None else None)
         if need_grad:
@@ -795,7 +797,17 @@ class HeadCEFn(Function):
         d_a, d_c = _scatter_head_rows(da_rows, dc_rows, plan_a, plan_c, t_a, t_c, a_shape, c_shape)
         # (the per-row d_a is not scaled in place like the big buffer: nothing of it is consumed)
         d_gate = ctx.d_gate * g if ctx.d_gate is not None and ctx.needs_input_grad[13] else None
-        return d_a, None, dh, d_c, None, d_w, d_b, None, None, None, None, None, None, d_gate, None
+        d_q = ctx.d_q * g if ctx.d_q is not None else None
+        return d_a, None, dh, d_c, None, d_w, d_b, None, None, None, None, None, None, d_gate, d_q
+
+
+def copy_q_grad(a, row_loss, grad_scale):
+    """grad_scale * d row_loss / d q of the loss through the copy mix, per row: with m = (1 - a) p_g + a q and row_loss =
+    -log m, dL/dq = -a / m = -a exp(row_loss) -- from the row losses the CE writers already return, on [B] tensors.  A row
+    whose gate is 0 (the prior abstains) gets exactly 0, whatever its loss, and so does a row whose m is below fp32's range
+    (1 / m = exp(row_loss) overflows: p_g = 0 in fp32 and q = 0) -- it is not divided by, as d_a is not."""
+    inv_m = torch.exp(row_loss)
+    return torch.where((a > 0) & torch.isfinite(inv_m), a * inv_m, torch.zeros_like(a)) * (-float(grad_scale))
 
 
 def _copy_pair(copy_a, copy_q, b):
@@ -838,7 +850,8 @@ class DualHeadCEFn(Function):
                 loss_scale=1.0, rel_weight=0.1, row_tap=None, copy_a=None, copy_q=None):
         """row_tap: a list that receives (row losses [2b]: entity head rows then relation head rows, s1, s2) -- the weights
         with which the returned scalar sums them (RENet.forward's fused directions split the merged loss by direction).
-        copy_a / copy_q: as for HeadCEFn, for the ENTITY head only; the relation head is the plain CE."""
+        copy_a / copy_q: as for HeadCEFn (d_a and d_q included), for the ENTITY head only; the relation head is the plain
+        CE."""
         ctx.srcs = (a, c, w1, b1, w2, b2)
         copy = _copy_pair(copy_a, copy_q, h1.shape[0])
         a, h1, h2, c, w1, b1, w2, b2 = (_c(t) for t in (a, h1, h2, c, w1, b1, w2, b2))
@@ -854,6 +867,7 @@ class DualHeadCEFn(Function):
                 _, feat2, lg2, dl2, fop2, _ = head2()
         _, feat1, lg1, dl1, fop1, ctx.d_gate = _head_forward(a, ia, h1, c, ic, w1, b1, target1, drop_p, seed1, s1, need_grad,
                                                              row_loss=rl[:b], copy=copy)
+        ctx.d_q = copy_q_grad(copy[0], rl[:b], s1) if copy is not None and ctx.needs_input_grad[21] else None
         if debug_tap is not None:                            # test hook: the entity head reports first
             _, feat2, lg2, dl2, fop2, _ = head2()
         sd.join()
@@ -898,7 +912,8 @@ class DualHeadCEFn(Function):
         da1.add_(da2)                                        # same rows ent[s] in both heads: one scatter-add
         d_a, d_c = _scatter_head_rows(da1, dc1, plan_a, plan_c, t_a, t_c, a_shape, c_shape)
         d_gate = ctx.d_gate * g if ctx.d_gate is not None and ctx.needs_input_grad[20] else None
-        return (d_a, None, dh1, d_c, None, d_w1, d_b1, None, dh2, d_w2, d_b2, None) + (None,) * 8 + (d_gate, None)
+        d_q = ctx.d_q * g if ctx.d_q is not None else None
+        return (d_a, None, dh1, d_c, None, d_w1, d_b1, None, dh2, d_w2, d_b2, None) + (None,) * 8 + (d_gate, d_q)
 
 
 class SegmentPoolFn(Function):

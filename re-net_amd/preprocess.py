@@ -285,15 +285,25 @@ class PairIndex(object):
         [n + 1], col int64, w float64), row i holding, in ascending partner order, every partner o of a fact (ent_i, rel_i,
         o, t') with t' < as_of_i and w[o] = sum over those facts of 2^(-(t_i - t') * inv_half_life).  half_life None (or
         inv_half_life 0): plain counts.  inv_half_life, when given, is used as it stands (the device takes it as fp32:
-        recurrence.RecurrencePrior.inv_half_life); else it is 1 / half_life."""
+        recurrence.RecurrencePrior.inv_half_life); else it is 1 / half_life.  An ARRAY inv_half_life holds one decay per row
+        (a learned per-relation half-life: the host statement of renet_recurrence_mix_rows_decay); row i then equals the
+        scalar call with inv_half_life[i], list for list."""
         ent, rel, t = (np.asarray(x, dtype=np.int64).reshape(-1) for x in (ent, rel, t))
         as_of = np.broadcast_to(np.asarray(as_of, dtype=np.int64).reshape(-1), ent.shape)
-        ihl = float(inv_half_life) if inv_half_life is not None else (0.0 if half_life is None else 1.0 / float(half_life))
+        if inv_half_life is not None and np.ndim(inv_half_life) > 0:
+            rates = np.asarray(inv_half_life, dtype=np.float64).reshape(-1)
+            if rates.shape != ent.shape:
+                raise ValueError('prior_rows: an array inv_half_life holds one value per row')
+        else:
+            rates = None
+            ihl = float(inv_half_life) if inv_half_life is not None else (0.0 if half_life is None else 1.0 / float(half_life))
         ptr, col, w = [0], [], []
         for i in range(len(ent)):
             a, b = self.sub_run(int(ent[i]), int(rel[i]))
             seen = self.p_t[a:b] < as_of[i]
             o, tp = self.p_other[a:b][seen], self.p_t[a:b][seen]
+            if rates is not None:
+                ihl = float(rates[i])
             if len(o):
                 cols, inv = np.unique(o, return_inverse=True)
                 col.append(cols)

@@ -28,6 +28,16 @@ RENet.learn_observed(..., prior=, gate_optimizer=) train the model (and the gate
 alone.  A step with copy= is not in the C launch list (csrc/step.cpp): it pays the autograd path's host enqueue.  Numbers
 with a LEARNED gate are a protocol of their own: comparable only with numbers of the same protocol and the same fitting data.
 
+A LEARNED HALF-LIFE.  CopyGate(learn_half_life=True) also learns HOW RECENT a fact must be to count: one decay per (side,
+relation), rate = exp(log_rate) = 1 / half_life in the stream's timestamp units, initialised from half_life.  Every row takes
+its own rate (renet_recurrence_mix_rows_decay / renet_recurrence_gold_rows_decay in the gated / gold entries' places).  With
+the lag D = t - t' and w = 2^(-D rate):  G = sum over gold's facts of w, W = sum over all, GD / WD the same sums of D w,
+    q = G / W,   dq/drate = -ln2 (GD W - G WD) / W^2 = -ln2 q (E_gold[D] - E_all[D]),   dL/dq = -a / m = -a exp(L)
+-- the gold kernel returns dq beside q, the head Functions return dL/dq from their row losses (the CE writers are untouched),
+and the product reaches log_rate through the gates' deterministic segmented add: d log_rate[k] = rate_k * sum over the rows of
+k.  log_rate is a gate parameter: gate_optimizer steps it, it stays out of the model's clip norm.  Numbers with learned
+parameters are a protocol of their own: report the INITIAL alpha and half_life, the fitting split, steps and learning rate.
+
 EVENTS.  The event entries (RENet.evaluate_events_observed, predict_events_observed, observed_event_scores, forecast_events)
 rank a (relation, entity) PAIR among R * N_ent candidates; their `prior=` keyword mixes the JOINT statistic into the joint
 log-probabilities J of a history (a "group": the given entity e, t, as_of) with one renet_joint_mix_rows call per sub-block,
@@ -47,7 +57,7 @@ alpha and half_life.  `topk_events` is the baseline's top-k in predict_events_ob
 Not covered: rollout (generated facts in a prior are a protocol question of their own; generate_events_observed and
 evaluate_rollout take no prior: generation stays the model's own), training through the joint mix, a learned per-relation
 gate for events, fusing the mix into renet_joint_row_offsets or the rank kernel (measured first: profiles/event_prior.md), a
-relation-free term, a learned half-life, bf16-storage mode, data-parallel gate gradients."""
+relation-free term, a per-relation decay for events, bf16-storage mode, data-parallel gate gradients."""
 import math
 
 import numpy as np
@@ -114,22 +124,42 @@ class _PermuteFn(torch.autograd.Function):
         return out, None
 
 
+class _DecayQFn(torch.autograd.Function):
+    """q as a function of the per-row decay: forward returns the gold kernel's q (its bits), backward g * dq with the
+    kernel's dq = d q / d rate -- an elementwise product, one writer per row."""
+
+    @staticmethod
+    def forward(ctx, rate, q, dq):
+        ctx.save_for_backward(dq)
+        return q.clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        return g * ctx.saved_tensors[0], None, None
+
+
 A_MAX = 1.0 - 2.0 ** -24                  # the largest fp32 below 1: a gate never reaches 1, whatever its logit
 
 
 class CopyGate(torch.nn.Module):
     """The LEARNED recurrence prior: one gate per side and relation, a = sigmoid(logit).  logit: fp32 [2, num_rels] (row 0 the
     'ob' side -- objects of (s, r, ?) --, row 1 the 'sub' side), or [2, 1] with per_relation=False; initialised to
-    logit(alpha).  half_life as RecurrencePrior's, fixed.  Accepted wherever `prior=` takes a RecurrencePrior; trained by
-    RENet.learn_observed(prior=gate, gate_optimizer=) and fit_gate.  state_dict() holds `logit`."""
+    logit(alpha).  half_life as RecurrencePrior's, fixed -- or, with learn_half_life=True, LEARNED: a second parameter
+    log_rate, fp32 in logit's layout, rate = exp(log_rate) = 1 / half_life per (side, relation), initialised to
+    log(1 / half_life) (half_life is then required); every row is mixed with its own rate and the loss reaches log_rate
+    through q (see the module's text).  Accepted wherever `prior=` takes a RecurrencePrior; trained by
+    RENet.learn_observed(prior=gate, gate_optimizer=) and fit_gate.  state_dict() holds `logit`, and `log_rate` with
+    learn_half_life=True only."""
 
-    def __init__(self, num_rels, alpha=0.3, half_life=None, per_relation=True):
+    def __init__(self, num_rels, alpha=0.3, half_life=None, per_relation=True, learn_half_life=False):
         super(CopyGate, self).__init__()
         alpha = float(alpha)
         if not 0.0 < alpha < 1.0:
             raise ValueError('alpha must lie in (0, 1): it initialises logit = log(alpha / (1 - alpha))')
         if half_life is not None and not float(half_life) > 0.0:
             raise ValueError('half_life must be positive (None: frequency only)')
+        if learn_half_life and half_life is None:
+            raise ValueError('learn_half_life=True needs half_life: it initialises log_rate = log(1 / half_life)')
         self.num_rels, self.per_relation = int(num_rels), bool(per_relation)
         if self.num_rels < 1:
             raise ValueError('num_rels must be positive')
@@ -137,10 +167,14 @@ class CopyGate(torch.nn.Module):
         self.inv_half_life = 0.0 if half_life is None else float(np.float32(1.0 / float(half_life)))
         width = self.num_rels if self.per_relation else 1
         self.logit = torch.nn.Parameter(torch.full((2, width), math.log(alpha / (1.0 - alpha)), dtype=torch.float32))
-        self._checked_version = None
+        self.learn_half_life = bool(learn_half_life)
+        if self.learn_half_life:
+            self.log_rate = torch.nn.Parameter(torch.full((2, width), math.log(1.0 / float(half_life)), dtype=torch.float32))
+        self._checked_version = self._checked_rate = None
 
     def __repr__(self):
-        return 'CopyGate(num_rels=%d, half_life=%r, per_relation=%r)' % (self.num_rels, self.half_life, self.per_relation)
+        return 'CopyGate(num_rels=%d, half_life=%r, per_relation=%r%s)' % (
+            self.num_rels, self.half_life, self.per_relation, ', learn_half_life=True' if self.learn_half_life else '')
 
     def table(self):
         """The gates [2, width] = sigmoid(logit), kept below 1."""
@@ -155,7 +189,24 @@ class CopyGate(torch.nn.Module):
             if not bool(((tab >= 0) & (tab < 1)).all()):
                 raise ValueError('CopyGate: a gate outside [0, 1) (non-finite logit?)')
             self._checked_version = key
+        if self.learn_half_life:
+            key = (self.log_rate._version, self.log_rate.data_ptr())
+            if self._checked_rate != key:
+                rate = self.rate_table().detach()
+                if not bool(((rate >= 0) & (rate < float('inf'))).all()):
+                    raise ValueError('CopyGate: a decay that is negative or not finite (non-finite log_rate?)')
+                self._checked_rate = key
         return self
+
+    def rate_table(self):
+        """The learned decays [2, width] = exp(log_rate), 1 / half_life per (side, relation); learn_half_life=True only."""
+        if not self.learn_half_life:
+            raise ValueError('CopyGate: rate_table() needs learn_half_life=True (the fixed decay is inv_half_life)')
+        return torch.exp(self.log_rate)
+
+    def half_lives(self):
+        """The learned half-lives, a host float64 array [2, width] = 1 / rate_table(): for reports."""
+        return 1.0 / self.rate_table().detach().double().cpu().numpy()
 
     def index(self, side, rel):
         """The flat index into table() of the rows of `side` with relations rel (host array or device tensor)."""
@@ -175,11 +226,26 @@ class CopyGate(torch.nn.Module):
     def rows_at(self, index):
         """The gates at the flat table indices `index` (host int array), a device tensor with autograd: its gradient reaches
         `logit` through a deterministic segmented add."""
-        dev = self.logit.device
+        return self._rows_of(self.table().reshape(-1), self.logit, index)
+
+    def rate_rows_at(self, index):
+        """rows_at for the learned decays: rate_table() at the flat indices `index`, its gradient reaching `log_rate` through
+        the same plan and the same deterministic segmented add."""
+        return self._rows_of(self.rate_table().reshape(-1), self.log_rate, index)
+
+    def rate_rows(self, side, rel):
+        """rows for the learned decays: the per-row rate of the rows of `side` with relations rel."""
+        if isinstance(rel, torch.Tensor):
+            if not (torch.is_grad_enabled() and self.log_rate.requires_grad):
+                return self.rate_table().detach().reshape(-1)[self.index(side, rel)]
+            rel = rel.cpu().numpy()
+        return self.rate_rows_at(self.index(side, rel))
+
+    def _rows_of(self, flat, param, index):
+        dev = param.device
         index = np.ascontiguousarray(index, dtype=np.int64)
-        flat = self.table().reshape(-1)
         idx_dev = torch.from_numpy(index).to(dev)
-        if not (torch.is_grad_enabled() and self.logit.requires_grad) or len(index) == 0:
+        if not (torch.is_grad_enabled() and param.requires_grad) or len(index) == 0:
             return flat.detach()[idx_dev]
         hp, plan = G.SegPlan.host(index), G.SegPlan()
         plan.order, plan.seg_ptr, plan.target = (G.h2d(np.ascontiguousarray(a, dtype=np.int32), dev)
@@ -232,6 +298,13 @@ class QueryRows(object):
                 else:
                     rel = torch.zeros_like(rel)
                 a_row = tab[rel + role * width].contiguous()
+                if prior.learn_half_life:                               # one decay per row as well: gathered as a_row is
+                    ihl_row = prior.rate_table().reshape(-1)[rel + role * width].contiguous()
+            if prior.learn_half_life:
+                return K.recurrence_mix_rows_decay(self.ent[role][c:d], self.rel[c:d], self.t[c:d], self.as_of[c:d],
+                                                   self.tables[role], t['ent_ptr%d' % role], t['snap_ptr%d' % role],
+                                                   self.base.num_ent, logits, a_row, ihl_row, num_cols=self.base.num_ent,
+                                                   want_stats=want_stats, check=False)
             return K.recurrence_mix_rows_gated(self.ent[role][c:d], self.rel[c:d], self.t[c:d], self.as_of[c:d],
                                                self.tables[role], t['ent_ptr%d' % role], t['snap_ptr%d' % role],
                                                self.base.num_ent, logits, a_row, prior.inv_half_life,
@@ -247,18 +320,29 @@ def _checked(prior):
     return prior
 
 
-def event_alphas(prior):
-    """{'ob': a, 'sub': a}: the scalar weight of the JOINT mix per direction.  A RecurrencePrior gives its alpha for both; a
-    CopyGate(per_relation=False) its side's single gate (checked, then read to the host: one small copy per call).  A
-    per-relation CopyGate is refused: the joint mix takes ONE gate per history."""
+def event_scalars(prior):
+    """({'ob': a, 'sub': a}, {'ob': inv_half_life, 'sub': inv_half_life}): the scalar weight and decay of the JOINT mix per
+    direction.  A RecurrencePrior gives its alpha and inv_half_life for both; a CopyGate(per_relation=False) its side's single
+    gate and -- with learn_half_life=True -- its side's single learned rate (checked, then read to the host: ONE small copy per
+    call for both).  A per-relation CopyGate is refused: the joint mix takes ONE gate and ONE decay per history."""
     _checked(prior)
     if not isinstance(prior, CopyGate):
-        return {name: prior.alpha for name in SIDES}
+        return {name: prior.alpha for name in SIDES}, {name: prior.inv_half_life for name in SIDES}
     if prior.per_relation:
         raise ValueError('the event entries take a RecurrencePrior or a CopyGate(per_relation=False), not a per-relation gate: '
                          'with the relation open, a gate per relation does not give a normalised joint')
-    tab = prior.check().table().detach().reshape(-1).cpu().numpy()                  # [2]: the 'ob' gate, the 'sub' gate
-    return {name: float(np.float32(tab[row])) for name, row in SIDES.items()}
+    tab = prior.check().table().detach().reshape(-1)                                # [2]: the 'ob' gate, the 'sub' gate
+    if not prior.learn_half_life:
+        tab = tab.cpu().numpy()
+        return ({name: float(np.float32(tab[row])) for name, row in SIDES.items()},
+                {name: prior.inv_half_life for name in SIDES})
+    tab = torch.stack((tab, prior.rate_table().detach().reshape(-1))).cpu().numpy()  # [2, 2]: the gates, the rates
+    return tuple({name: float(np.float32(row[k])) for name, k in SIDES.items()} for row in tab)
+
+
+def event_alphas(prior):
+    """event_scalars(prior)[0]: {'ob': a, 'sub': a}."""
+    return event_scalars(prior)[0]
 
 
 def event_alpha(prior, name):
@@ -270,11 +354,11 @@ def event_alpha(prior, name):
 
 class EventMix(object):
     """What the `prior=` keyword of the event entries carries through one call: the two directions' alpha (event_alphas, read
-    once), inv_half_life, and -- from the first groups() on -- the base store whose pair tables are read."""
+    once) and inv_half_life (one per direction: a gate that learns its decay has one rate per side), and -- from the first
+    groups() on -- the base store whose pair tables are read."""
 
     def __init__(self, prior):
-        self.alpha = event_alphas(prior)
-        self.inv_half_life = prior.inv_half_life
+        self.alpha, self.inv_half_life = event_scalars(prior)
         self.base = None
 
     def groups(self, store, ent, t, first):
@@ -297,14 +381,15 @@ class EventMix(object):
         role, t = SIDES[name], self.base.t
         return K.joint_mix_rows(block, block.shape[0] // max(g1 - g0, 1), off, q[0][g0:g1], q[1][g0:g1], q[2][g0:g1],
                                 self.tables[role], t['ent_ptr%d' % role], t['snap_ptr%d' % role], self.base.num_ent,
-                                self.alpha[name], self.inv_half_life, mass=mass)
+                                self.alpha[name], self.inv_half_life[name], mass=mass)
 
 
 class CopyRows(object):
     """(a_row, q_row, W) of ONE merged training batch, for RENet.loss_prepared_both(prep, copy=): the positions idx of the
     resident store `store` (a gpu_builder.ObservedStore; as_of = t: no fact of the query's own timestamp is read) under
-    `prior` (RecurrencePrior: a = alpha; CopyGate: a = its gate of (side, relation), with autograd).  Two
-    renet_recurrence_gold_rows launches, one per role -- sequence i < n of the merged batch is position i's 'ob' direction
+    `prior` (RecurrencePrior: a = alpha; CopyGate: a = its gate of (side, relation), with autograd; a gate that learns its
+    decay: renet_recurrence_gold_rows_decay with the rows' own rates, and q with autograd -- its backward hands g * dq to the
+    per-row rates).  Two renet_recurrence_gold_rows launches, one per role -- sequence i < n of the merged batch is position i's 'ob' direction
     (given s, gold o), sequence n + i its 'sub' direction (given o, gold s) --, a zeroed where the prior abstains (W = 0), and
     in batch() one gather through the builder's perm (sorted position -> sequence) into the batch's row order."""
 
@@ -313,18 +398,31 @@ class CopyRows(object):
         idx = np.asarray(idx, dtype=np.int64).reshape(-1)
         rows = QueryRows(store, idx)
         base, n = rows.base, len(idx)
-        q, w = [], []
+        learned = isinstance(prior, CopyGate) and prior.learn_half_life
+        if isinstance(prior, CopyGate):
+            rel = store.quads[idx, 1]
+            index = np.concatenate((prior.index('ob', rel), prior.index('sub', rel)))
+            prior.check()
+        if learned:
+            rate = prior.rate_rows_at(index)                            # [2n], with autograd when log_rate learns
+            ihl = rate.detach().contiguous()
+        q, w, dq = [], [], []
         for role in (0, 1):
-            qq, ww = K.recurrence_gold_rows(rows.ent[role], rows.rel, rows.t, rows.as_of, rows.ent[1 - role], rows.tables[role],
-                                            base.t['ent_ptr%d' % role], base.t['snap_ptr%d' % role], base.num_ent, base.num_ent,
-                                            prior.inv_half_life)
+            args = (rows.ent[role], rows.rel, rows.t, rows.as_of, rows.ent[1 - role], rows.tables[role],
+                    base.t['ent_ptr%d' % role], base.t['snap_ptr%d' % role], base.num_ent, base.num_ent)
+            if learned:
+                qq, ww, dd = K.recurrence_gold_rows_decay(*args, ihl[role * n:(role + 1) * n])
+                dq.append(dd)
+            else:
+                qq, ww = K.recurrence_gold_rows(*args, prior.inv_half_life)
             q.append(qq)
             w.append(ww)
         self.n = n
         self.q_seq, self.W_seq = torch.cat(q), torch.cat(w)
+        if learned and rate.requires_grad:
+            self.q_seq = _DecayQFn.apply(rate, self.q_seq, torch.cat(dq))
         if isinstance(prior, CopyGate):
-            rel = store.quads[idx, 1]
-            a = prior.check().rows_at(np.concatenate((prior.index('ob', rel), prior.index('sub', rel))))
+            a = prior.rows_at(index)
         else:
             a = torch.full((2 * n,), prior.alpha, device=self.q_seq.device, dtype=torch.float32)
         self.a_seq = torch.where(self.W_seq > 0, a, torch.zeros_like(a))
@@ -335,19 +433,22 @@ class CopyRows(object):
             raise ValueError('CopyRows: the batch does not hold the two directions of these positions')
         perm = prep.g._v['perm'][:prep.b].long()
         a = _PermuteFn.apply(self.a_seq, perm) if self.a_seq.requires_grad else self.a_seq[perm]
-        return a, self.q_seq[perm], self.W_seq[perm]
+        q = _PermuteFn.apply(self.q_seq, perm) if self.q_seq.requires_grad else self.q_seq[perm]
+        return a, q, self.W_seq[perm]
 
 
 def fit_gate(model, obs, idx, gate, optimizer, steps=1, max_batch=4096):
     """"Fitting alpha" with the model FROZEN: `steps` optimizer steps of the CopyGate `gate` on the stream positions idx of
     the resident stream obs.  Per step and per batch of max_batch positions the scores are computed under no_grad as
     RENet.observed_scores computes them (eval mode), renet_mix_ce takes them with dlogits = NULL -- only d_a flows --, and the
-    gate's gradient of the MEAN mixed loss over all rows of both directions is accumulated before ONE optimizer.step().
+    gate's gradient of the MEAN mixed loss over all rows of both directions is accumulated before ONE optimizer.step().  A gate
+    that learns its decay also receives d_q = -a exp(row_loss) / (2n) through q.
     optimizer: any torch.optim over gate.parameters().  -> the mean mixed loss per step (Python floats, before that step's
     update).  The model's parameters and mode are left as found."""
     import model as M
     if not isinstance(gate, CopyGate):
         raise ValueError('fit_gate fits a recurrence.CopyGate')
+    gate.check()                                                        # (a non-finite parameter is refused before any launch)
     store = M._observed_store(obs)
     idx = M._observed_positions(store, idx)
     max_batch = max(1, int(max_batch))
@@ -366,10 +467,12 @@ def fit_gate(model, obs, idx, gate, optimizer, steps=1, max_batch=4096):
                 rows = CopyRows(store, part, gate)
                 m = len(part)
                 for k, (pred, gold) in enumerate(((ob_pred, rows_gold(store, part, 'ob')), (sub_pred, rows_gold(store, part, 'sub')))):
-                    a = rows.a_seq[k * m:(k + 1) * m]
-                    row_loss, d_a = K.mix_ce(pred, gold, a.detach().contiguous(), rows.q_seq[k * m:(k + 1) * m].contiguous(),
-                                             1.0 / (2 * n), False)
+                    a, q = rows.a_seq[k * m:(k + 1) * m], rows.q_seq[k * m:(k + 1) * m]
+                    row_loss, d_a = K.mix_ce(pred, gold, a.detach().contiguous(), q.detach().contiguous(), 1.0 / (2 * n), False)
                     a.backward(d_a, retain_graph=True)
+                    if q.requires_grad:                                  # (a learned decay: dL/dq = -a / m = -a exp(L))
+                        import ops
+                        q.backward(ops.copy_q_grad(a.detach(), row_loss, 1.0 / (2 * n)), retain_graph=True)
                     total = total + row_loss.sum() / (2 * n)
             optimizer.step()
             out.append(total)

@@ -185,6 +185,10 @@ _SIGNATURES = {
                                                 c_int, c_void_p, c_int, c_int, c_void_p, c_float] + [c_void_p] * 4),
     'renet_recurrence_gold_rows': (c_int, [c_void_p] * 5 + [c_int] + [c_void_p] * 3 + [c_int, c_void_p, c_void_p, c_int, c_int,
                                            c_int, c_float] + [c_void_p] * 3),
+    'renet_recurrence_mix_rows_decay': (c_int, [c_void_p] * 4 + [c_int] + [c_void_p] * 3 + [c_int, c_void_p, c_void_p, c_int,
+                                                c_int, c_void_p, c_int, c_int, c_void_p, c_void_p] + [c_void_p] * 4),
+    'renet_recurrence_gold_rows_decay': (c_int, [c_void_p] * 5 + [c_int] + [c_void_p] * 3 + [c_int, c_void_p, c_void_p, c_int,
+                                                 c_int, c_int, c_void_p] + [c_void_p] * 4),
     'renet_joint_mix_rows': (c_int, [c_void_p] * 3 + [c_int] + [c_void_p] * 3 + [c_int, c_void_p, c_void_p, c_int, c_int,
                                      c_void_p, c_int, c_int, c_int, c_void_p, c_float, c_float, c_void_p, c_void_p]),
     'renet_mix_ce': (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_float] + [c_void_p] * 4),
@@ -1787,8 +1791,34 @@ def recurrence_mix_rows_gated(ent, rel, t, as_of, tables, ent_ptr, snap_ptr, num
                            inv_half_life, num_cols, want_stats)
 
 
+def _row_floats(x, n, what):
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.numel() == n):
+        raise RenetHipError('%s must be a contiguous float32 device tensor, one per row' % what)
+    return x.detach()
+
+
+def recurrence_mix_rows_decay(ent, rel, t, as_of, tables, ent_ptr, snap_ptr, num_ent, logits, alpha_row, ihl_row,
+                              num_cols=None, want_stats=False, check=True):
+    """renet_recurrence_mix_rows_decay: recurrence_mix_rows_gated with one DECAY per row as well, ihl_row (fp32 device [n],
+    each finite and >= 0) in inv_half_life's place -- w_i[o] sums 2^(-(t - t') ihl_row[i]).  A constant ihl_row gives the gated
+    entry's bits.  check: read both ranges back (one synchronisation each) and refuse a gate outside [0, 1) or a decay that
+    is negative or not finite before the launch; a caller that built both from checked tables passes False."""
+    n = int(ent.numel())
+    alpha_row = _row_floats(alpha_row, n, 'recurrence_mix_rows_decay: alpha_row')
+    ihl_row = _row_floats(ihl_row, n, 'recurrence_mix_rows_decay: ihl_row')
+    if check and n:
+        lo, hi = (float(v) for v in torch.aminmax(alpha_row))
+        if not (lo >= 0.0 and hi < 1.0):
+            raise RenetHipError('recurrence_mix_rows_decay: every gate must lie in [0, 1)')
+        lo, hi = (float(v) for v in torch.aminmax(ihl_row))
+        if not (lo >= 0.0 and hi < float('inf')):
+            raise RenetHipError('recurrence_mix_rows_decay: every decay must be finite and >= 0')
+    return _recurrence_mix(ent, rel, t, as_of, tables, ent_ptr, snap_ptr, num_ent, logits, None, alpha_row, 0.0, num_cols,
+                           want_stats, ihl_row=ihl_row)
+
+
 def _recurrence_mix(ent, rel, t, as_of, tables, ent_ptr, snap_ptr, num_ent, logits, alpha, alpha_row, inv_half_life, num_cols,
-                    want_stats):
+                    want_stats, ihl_row=None):
     n = int(ent.numel())
     if any(int(a.numel()) != n for a in (rel, t, as_of)):
         raise RenetHipError('recurrence_mix_rows: ent, rel, t and as_of must have one entry per row')
@@ -1816,7 +1846,10 @@ def _recurrence_mix(ent, rel, t, as_of, tables, ent_ptr, snap_ptr, num_ent, logi
              _i32(snap_ptr, 'snap_ptr'), int(snap_ptr.numel()) - 1, int(num_ent),
              None if logits is None else logits.data_ptr(), ld, c)
     back = (float(inv_half_life), out.data_ptr(), _i32(stats), _f32(wsum), _stream())
-    if alpha_row is None:
+    if ihl_row is not None:
+        _check(lib().renet_recurrence_mix_rows_decay(*front, _f32(alpha_row, 'alpha_row'), _f32(ihl_row, 'ihl_row'), *back[1:]),
+               'recurrence_mix_rows_decay')
+    elif alpha_row is None:
         _check(lib().renet_recurrence_mix_rows(*front, float(alpha), *back), 'recurrence_mix_rows')
     else:
         _check(lib().renet_recurrence_mix_rows_gated(*front, _f32(alpha_row, 'alpha_row'), *back), 'recurrence_mix_rows_gated')
@@ -1845,6 +1878,31 @@ def recurrence_gold_rows(ent, rel, t, as_of, gold, tables, ent_ptr, snap_ptr, nu
                                             q.data_ptr(), w.data_ptr(), _stream()), 'recurrence_gold_rows')
     _timed_end(t0, 'recurrence_gold_rows', nbytes=float(n * 28))
     return q, w
+
+
+def recurrence_gold_rows_decay(ent, rel, t, as_of, gold, tables, ent_ptr, snap_ptr, num_ent, num_cols, ihl_row):
+    """renet_recurrence_gold_rows_decay, one direction: -> (q, W, dq), fp32 device [n]: recurrence_gold_rows with the decay of
+    row i taken from ihl_row (fp32 device [n], each finite and >= 0: the caller's to keep) and dq_i = d q_i / d ihl_row[i] =
+    -ln2 (GD W - G WD) / W^2, exactly 0 where W_i = 0 or the gold column has no counted fact.  A constant ihl_row gives the
+    (q, W) of recurrence_gold_rows bit for bit."""
+    n = int(ent.numel())
+    if any(int(a.numel()) != n for a in (rel, t, as_of, gold)):
+        raise RenetHipError('recurrence_gold_rows_decay: ent, rel, t, as_of and gold must have one entry per row')
+    ihl_row = _row_floats(ihl_row, n, 'recurrence_gold_rows_decay: ihl_row')
+    p_rel, p_other, p_t = tables
+    nf = int(p_rel.numel())
+    if p_other.numel() != nf or p_t.numel() != nf or ent_ptr.numel() != int(num_ent) + 1:
+        raise RenetHipError('recurrence_gold_rows_decay: the pair tables do not fit num_ent / their own lengths')
+    q, w, dq = (torch.empty(n, device=ent.device, dtype=torch.float32) for _ in range(3))
+    t0 = _timed()
+    _check(lib().renet_recurrence_gold_rows_decay(_i32(ent, 'ent'), _i32(rel, 'rel'), _i32(t, 't'), _i32(as_of, 'as_of'),
+                                                  _i32(gold, 'gold'), n, *[_i32(a, 'pair table') if nf else None for a in tables],
+                                                  nf, _i32(ent_ptr, 'ent_ptr'), _i32(snap_ptr, 'snap_ptr'),
+                                                  int(snap_ptr.numel()) - 1, int(num_ent), int(num_cols),
+                                                  _f32(ihl_row, 'ihl_row'), q.data_ptr(), w.data_ptr(), dq.data_ptr(),
+                                                  _stream()), 'recurrence_gold_rows_decay')
+    _timed_end(t0, 'recurrence_gold_rows', nbytes=float(n * 36))
+    return q, w, dq
 
 
 def joint_row_offsets(scores, num_rels, logits_r):

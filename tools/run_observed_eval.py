@@ -54,6 +54,12 @@ protocol of their own -- the gate has seen the fitting data: every line printed 
 with numbers of the same protocol and the same fitting data.  A learn step through the mix is not in the C launch list
 (csrc/step.cpp): it runs the autograd path and pays its host enqueue.
 
+--learn-half-life (with --recurrence ALPHA --half-life H and one of --fit-gate / --online --learn-copy) LEARNS the decay too:
+the gate carries one half-life per side and relation (recurrence.CopyGate(learn_half_life=True)), initialised to H and trained
+by the same optimizer through q's derivative by the decay (renet_recurrence_gold_rows_decay).  The lines printed give the min,
+median and max of the learned half-lives per side beside the gate range, and the JSON record holds them.  Numbers with learned
+parameters are a protocol of their own: report the INITIAL alpha and half-life, the fitting split, steps and learning rate.
+
 --events adds the EVENT forecasts (RENet.evaluate_events_observed): MRR / Hits of the gold (relation, entity) pair among all
 pairs of the given entity, and of the gold relation given both endpoints, in the three settings; with K also the K most
 probable (relation, object) pairs of the first few queries (RENet.predict_events_observed, time-aware filtered).
@@ -185,7 +191,8 @@ def online_loop(args, model, global_model, splits, num_ent, num_rels, data_dir):
     if args.recurrence is not None:
         import recurrence
         if args.learn_copy:
-            prior = recurrence.CopyGate(num_rels, alpha=args.recurrence, half_life=args.half_life).to(next(model.parameters()).device)
+            prior = recurrence.CopyGate(num_rels, alpha=args.recurrence, half_life=args.half_life,
+                                        learn_half_life=args.learn_half_life).to(next(model.parameters()).device)
             gate_opt = torch.optim.Adam(prior.parameters(), lr=args.gate_lr)
         else:
             prior = recurrence.RecurrencePrior(args.recurrence, args.half_life)
@@ -211,6 +218,8 @@ def online_loop(args, model, global_model, splits, num_ent, num_rels, data_dir):
                   'half-life %s, gate lr %g): the gate that ranks timestamp t was fitted on the evaluated timestamps before t; '
                   'gates now: ob side %.3f .. %.3f, sub side %.3f .. %.3f.  Comparable only with numbers of this protocol.'
                   % (args.recurrence, half, args.gate_lr, tab[0].min(), tab[0].max(), tab[1].min(), tab[1].max()))
+            if args.learn_half_life:
+                print(half_life_line(prior))
         else:
             print('MODEL MIXED WITH THE RECURRENCE PRIOR in the forecast half, fixed alpha %g, half-life %s; learning is not '
                   'touched by it' % (prior.alpha, half))
@@ -226,8 +235,24 @@ def online_loop(args, model, global_model, splits, num_ent, num_rels, data_dir):
     print(json.dumps({'protocol': 'observed', 'loop': 'online', 'steps': args.online, 'replay': args.replay,
                       'global_model_learns': gopt is not None, 'lr': args.lr, 'split': args.split, 'n': int(len(evaluated)),
                       'recurrence': None if prior is None else {'alpha': args.recurrence, 'half_life': args.half_life,
-                                                                'gate_learned': bool(args.learn_copy)},
+                                                                'gate_learned': bool(args.learn_copy),
+                                                                **(half_life_record(prior) if args.learn_half_life else {})},
                       'metrics': {name: U.rank_metrics(ranks[name]) for name in SETTINGS}}))
+
+
+def half_life_record(gate):
+    """{'half_life_learned': True, 'learned_half_lives': {side: {'min', 'median', 'max'}}} of a gate that learns its decay."""
+    import numpy as np
+    hl = gate.half_lives()
+    return {'half_life_learned': True,
+            'learned_half_lives': {side: {'min': float(hl[k].min()), 'median': float(np.median(hl[k])), 'max': float(hl[k].max())}
+                                   for k, side in enumerate(('ob', 'sub'))}}
+
+
+def half_life_line(gate):
+    rec = half_life_record(gate)['learned_half_lives']
+    return ('LEARNED HALF-LIVES per side and relation (initial %g), min / median / max: ob side %.4g / %.4g / %.4g, sub side '
+            '%.4g / %.4g / %.4g' % ((gate.half_life,) + tuple(rec[s][k] for s in ('ob', 'sub') for k in ('min', 'median', 'max'))))
 
 
 def main():
@@ -266,6 +291,9 @@ def main():
                     help='fit a per-relation gate on the valid split (model frozen), then evaluate mixed with it (--recurrence)')
     ap.add_argument('--learn-copy', action='store_true',
                     help='online steps train through the mix and the gates learn along the stream (--online --recurrence)')
+    ap.add_argument('--learn-half-life', action='store_true',
+                    help='the gate also learns one half-life per side and relation, from H (--recurrence --half-life with '
+                         '--fit-gate or --online --learn-copy)')
     ap.add_argument('--gate-lr', type=float, default=1e-2, help='learning rate of the gate (--fit-gate, --learn-copy)')
     args = ap.parse_args()
     if args.recurrence is not None:
@@ -279,8 +307,10 @@ def main():
             raise SystemExit('--fit-gate takes STEPS >= 1 and goes with the plain pass and --horizon')
         if args.learn_copy and args.online is None:
             raise SystemExit('--learn-copy belongs to --online --recurrence')
-    elif args.half_life is not None or args.fit_gate is not None or args.learn_copy:
-        raise SystemExit('--half-life, --fit-gate and --learn-copy belong to --recurrence')
+        if args.learn_half_life and (args.half_life is None or not (args.fit_gate is not None or args.learn_copy)):
+            raise SystemExit('--learn-half-life needs --half-life H (its initial value) and --fit-gate or --online --learn-copy')
+    elif args.half_life is not None or args.fit_gate is not None or args.learn_copy or args.learn_half_life:
+        raise SystemExit('--half-life, --fit-gate, --learn-copy and --learn-half-life belong to --recurrence')
     if args.online is not None:
         if args.online < 0 or args.replay < 0:
             raise SystemExit('--online and --replay must be >= 0')
@@ -402,7 +432,8 @@ def main():
         if args.fit_gate is not None:
             if splits[1] is None:
                 raise SystemExit('--fit-gate fits on the valid split: %s has no valid.txt' % data_dir)
-            gate = recurrence.CopyGate(num_rels, alpha=args.recurrence, half_life=args.half_life).to(dev)
+            gate = recurrence.CopyGate(num_rels, alpha=args.recurrence, half_life=args.half_life,
+                                       learn_half_life=args.learn_half_life).to(dev)
             t6 = time.perf_counter()
             fit = recurrence.fit_gate(model, obs, obs.positions('valid'), gate, torch.optim.Adam(gate.parameters(), lr=args.gate_lr),
                                       steps=args.fit_gate, max_batch=args.max_batch)
@@ -420,6 +451,8 @@ def main():
                      'none (frequency only)' if gate.half_life is None else '%g' % gate.half_life, t7 - t6, fit[0], fit[-1],
                      tab[0].min(), tab[0].max(), tab[1].min(), tab[1].max(), t8 - t7, len(idx) / max(t8 - t7, 1e-9),
                      float(np.mean(gate_loss))))
+            if args.learn_half_life:
+                print(half_life_line(gate))
             for name in SETTINGS:
                 m = U.rank_metrics(gate_ranks[name])
                 print('%-14s MRR %.6f  MR %.3f  Hits@1 %.6f  Hits@3 %.6f  Hits@10 %.6f'
@@ -427,7 +460,8 @@ def main():
             print('(a LEARNED gate: the same protocol, filters and tie rule as the blocks above, but the gate has seen the valid '
                   'split -- comparable only with numbers obtained the same way)')
             print(json.dumps(dict(record, recurrence={'alpha': args.recurrence, 'half_life': gate.half_life, 'gate_learned': True,
-                                                      'fitted_on': 'valid', 'fit_steps': args.fit_gate, 'gate_lr': args.gate_lr},
+                                                      'fitted_on': 'valid', 'fit_steps': args.fit_gate, 'gate_lr': args.gate_lr,
+                                                      **(half_life_record(gate) if args.learn_half_life else {})},
                                   mixed_learned_gate={name: U.rank_metrics(gate_ranks[name]) for name in SETTINGS})))
     if args.events is not None:
         def event_pass(label, run):
