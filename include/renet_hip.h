@@ -365,6 +365,12 @@ int renet_softmax_ce_planes(const float* logits, const int32_t* target, int B, i
 int renet_mix_ce_planes(const float* logits, const int32_t* target, const float* a_row, const float* q_row, int B, int C,
                         int ld, float grad_scale, float* row_loss, void* dl_planes, size_t plane, int ld16, int rows16,
                         float* d_a, void* stream);
+/* renet_mix_ce_planes for the loss through the JOINT mix (renet_joint_mix_ce below states it): lp_row[b] is added to the gold
+ * logit, s_row (optional) receives s_b; planes, padding, row map and refusals as renet_mix_ce_planes, and a missing lp_row.
+ * lp_row = 0 gives renet_mix_ce_planes bit for bit. */
+int renet_joint_mix_ce_planes(const float* logits, const int32_t* target, const float* a_row, const float* q_row,
+                              const float* lp_row, int B, int C, int ld, float grad_scale, float* row_loss, void* dl_planes,
+                              size_t plane, int ld16, int rows16, float* d_a, float* s_row, void* stream);
 
 /* column sums: out[n] = beta * out[n] + sum_m X[m,n]  (bias gradients; beta = 1 accumulates straight into
  * an existing .grad); two deterministic passes over row groups, `workspace` = renet_colsum_workspace(M, N)
@@ -538,6 +544,21 @@ int renet_softmax_ce(const float* logits, const int32_t* target, int B, int C, i
  * per-row scalars cost no pass over the row.  A missing array or ld < C: RENET_ERR_BADARG before any launch. */
 int renet_mix_ce(const float* logits, const int32_t* target, const float* a_row, const float* q_row, int B, int C, int ld,
                  float grad_scale, float* row_loss, float* dlogits, float* d_a, void* stream);
+/* renet_mix_ce for the loss THROUGH THE JOINT MIX of renet_joint_mix_rows: the entity head's writer of an EVENT loss.  Beside
+ * a_row and q_row (renet_joint_gold_rows: q = G / W, entity-wide W), lp_row[b] <= 0 (device fp32 [B]) is the log-probability
+ * the relation head gives ITS gold class, pr = exp(lp).  With p = softmax(logits[b, :]), g = target[b]:
+ *     m = (1 - a) p_g pr + a q,   row_loss[b] = -log m   (= -M[r*, g] of renet_joint_mix_rows),   s_b = (1 - a) p_g pr / m
+ *     dlogits[b, c] = (p_c - [c == g]) * (grad_scale * s_b)          (NULL: not written; may alias logits)
+ *     d_a[b]        = grad_scale * (p_g pr - q) / m                  (NULL: not written)
+ *     s_row[b]      = s_b                                            (NULL: not written)
+ * The relation head's gradient row is ITS plain CE gradient times the same s_b (the caller scales it), and dL/dq = -a exp(L).
+ * p_g pr = exp(x_g + lp - max) / sum: the kernels of renet_mix_ce with the gold logit x_g + lp_row[b] (one fp32 addition), so
+ * lp_row = 0 gives renet_mix_ce bit for bit, and its branches hold with p_g pr in p_g's place: where a == 0 or q == 0, s_b = 1
+ * exactly, row_loss = (logsumexp - x_g - lp) - log1p(-a), and a product that underflowed to 0 is not divided by (d_a = 0).
+ * Refusals as renet_mix_ce, and a missing lp_row. */
+int renet_joint_mix_ce(const float* logits, const int32_t* target, const float* a_row, const float* q_row, const float* lp_row,
+                       int B, int C, int ld, float grad_scale, float* row_loss, float* dlogits, float* d_a, float* s_row,
+                       void* stream);
 /* Softmax cross-entropy against SPARSE SOFT targets (the global model's loss, global_model.py:52-55, with the target
  * distribution of row b given as the entries k in [tgt_ptr[b], tgt_ptr[b + 1]): columns tgt_col[k] -- distinct, ascending,
  * in [0, C) -- with weights tgt_w[k] >= 0 that need NOT sum to 1).  With W = sum_k tgt_w[k] and p = softmax(logits[b, :]):
@@ -995,11 +1016,35 @@ int renet_recurrence_gold_rows_decay(const int32_t* ent, const int32_t* rel, con
  * any ld, any row alignment); no workspace.
  * 1 <= R <= 1024, C in [1, RENET_RECURRENCE_MAX_C]; alpha outside [0, 1), a negative or non-finite inv_half_life, ld < C, R or C
  * out of range, G < 0 or a missing array: RENET_ERR_BADARG before any launch; G == 0 is a no-op.
- * Not covered: a gate per relation (with the relation open it gives no normalised joint), training through the joint mix. */
+ * Not covered: a gate per relation (with the relation open it gives no normalised joint). */
 int renet_joint_mix_rows(const int32_t* ent, const int32_t* t, const int32_t* as_of, int G, const int32_t* p_rel,
                          const int32_t* p_other, const int32_t* p_t, int n_facts, const int32_t* ent_ptr,
                          const int32_t* snap_ptr, int n_snaps, int num_ent, float* scores, int ld, int R, int C, float* off,
                          float alpha, float inv_half_life, double* mass, void* stream);
+/* renet_joint_gold_rows: what the LOSS through the joint mix needs of the prior (renet_joint_mix_ce): for row i -- the given
+ * entity ent[i], the GOLD relation rel[i], the gold partner gold[i], the query time t[i] and the window as_of[i] (device int32
+ * [n] each; tables, ent_ptr and snap_ptr of the given entity's role) -- with w = 2^(-(t - t') * inv_half_life):
+ *     G = sum of w over the facts (e, rel, gold, t' < as_of)       W = sum of w over ALL facts (e, *, *, t' < as_of)
+ *     q[i] = fp32(G / W),  W[i] = fp32(W)
+ * W is the entity-wide W of renet_joint_mix_rows: fp32(mass[g]) of a call on the group (ent, t, as_of), bit for bit (the same
+ * strided pass, shuffle tree and wave fold), and exp(-row_loss) of renet_joint_mix_ce is exp(M[rel, gold]) there.
+ * q = W = 0 where the entity has no fact before as_of or lies outside [0, num_ent); q = 0 (W kept) where gold lies outside
+ * [0, C), rel outside [0, R), or the pair has no counted fact.  One workgroup per row, every sum in fp64 in an order fixed by
+ * the tables' content and the block size, one rounding per output: no atomics, no workspace, the same bits from run to run.
+ * renet_joint_gold_rows_decay: the decay of row i is ihl_row[i] (device fp32 [n], finite and >= 0: the caller's to keep), and
+ * with GD, WD the same two sums of (t - t') w:
+ *     dq[i] = fp32(-ln2 (GD W - G WD) / W^2) = d q[i] / d ihl_row[i],  exactly 0 where W = 0 or G = 0
+ * (both products rounded separately: q = 1 gives 0).  A constant ihl_row gives the (q, W) of renet_joint_gold_rows bit for bit.
+ * 1 <= R <= 1024, C in [1, RENET_RECURRENCE_MAX_C]; R or C out of range, a negative or non-finite inv_half_life, n < 0 or a
+ * missing array (ihl_row and dq for the decay entry): RENET_ERR_BADARG before any launch; n == 0 is a no-op. */
+int renet_joint_gold_rows(const int32_t* ent, const int32_t* rel, const int32_t* t, const int32_t* as_of, const int32_t* gold,
+                          int n, const int32_t* p_rel, const int32_t* p_other, const int32_t* p_t, int n_facts,
+                          const int32_t* ent_ptr, const int32_t* snap_ptr, int n_snaps, int num_ent, int R, int C,
+                          float inv_half_life, float* q, float* W, void* stream);
+int renet_joint_gold_rows_decay(const int32_t* ent, const int32_t* rel, const int32_t* t, const int32_t* as_of,
+                                const int32_t* gold, int n, const int32_t* p_rel, const int32_t* p_other, const int32_t* p_t,
+                                int n_facts, const int32_t* ent_ptr, const int32_t* snap_ptr, int n_snaps, int num_ent, int R,
+                                int C, const float* ihl_row, float* q, float* W, float* dq, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * DEVICE builder for the FULL-GRAPH batches of the global model (graph.build_full_graphs; reference Aggregator.py:44-55 /

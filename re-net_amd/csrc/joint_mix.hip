@@ -2,6 +2,9 @@
 //   renet_joint_mix_rows mixes "what did this entity do before, and with whom" into the joint blocks of csrc/joint_rank.hip, in
 //                        place, between renet_joint_row_offsets and the rank / top-k kernels
 //                        (host statement: preprocess.PairIndex.event_rows + tests/event_prior_statement.py mix_block).
+//   renet_joint_gold_rows(_decay) the prior's mass on ONE (relation, partner) pair per row, q = G / W with the same entity-wide
+//                        W (and dq / d(decay)): what the loss THROUGH this mix needs of the prior (renet_joint_mix_ce in
+//                        csrc/seq.hip; host statement: tests/event_gate_statement.py gold_rows).  At the end of this file.
 //
 // A GROUP g is one history: the entity ent[g], the query time t[g] and the as_of[g] <= t[g] its window was built with.  Over
 // the facts (e, r, c, t' < as_of) of the entity's run of the role's pair tables (csrc/recurrence.hip):
@@ -190,7 +193,126 @@ __global__ __launch_bounds__(RC_THREADS) void joint_mix_rows_kernel(
     if (tid == 0) off[row] = 0.f;
 }
 
+// ---- the gold pair's prior mass: what the loss THROUGH the joint mix needs of the prior ---------------------------------
+// One workgroup per row (e, r*, t, as_of, gold).  W: the strided pass, shuffle tree and wave fold of joint_mix_mass_kernel over
+// the entity's whole run -- the same operations in the same order, so W here is fp32(mass[g]) there, bit for bit.  G: the gold
+// group [k0, cut) of the (e, r*) sub-run -- contiguous, ascending in time, found as recurrence_gold_rows_kernel finds it --
+// summed in the same strided shares through the same tree.  DECAY: the row's decay is ihl_row[row], and WD = sum of D w over the
+// run and GD over the gold group (D = t - t' the lag) ride beside them: dq = -ln2 (GD W - G WD) / W^2.  The DECAY = false
+// instance holds none of it.  Two (three) floats out per row, no atomics, no workspace.
+template <bool DECAY>
+__global__ __launch_bounds__(RC_THREADS) void joint_gold_rows_kernel(
+    const int32_t* __restrict__ q_ent, const int32_t* __restrict__ q_rel, const int32_t* __restrict__ q_t,
+    const int32_t* __restrict__ q_as_of, const int32_t* __restrict__ q_gold, const int32_t* __restrict__ p_rel,
+    const int32_t* __restrict__ p_other, const int32_t* __restrict__ p_t, int n_facts, const int32_t* __restrict__ ent_ptr,
+    const int32_t* __restrict__ snap_ptr, int n_snaps, int num_ent, int R, int C, float inv_half_life,
+    const float* __restrict__ ihl_row, float* __restrict__ q_out, float* __restrict__ w_out, float* __restrict__ dq_out) {
+    __shared__ double s_w[RC_WAVES], s_g[RC_WAVES];
+    __shared__ double s_wd[DECAY ? RC_WAVES : 1], s_gd[DECAY ? RC_WAVES : 1];
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int e = q_ent[row], r = q_rel[row], t = q_t[row], as_of = q_as_of[row], g = q_gold[row];
+    const double ihl = DECAY ? (double)ihl_row[row] : (double)inv_half_life;
+    int a, b;
+    rc_ent_run(n_facts, ent_ptr, snap_ptr, n_snaps, num_ent, e, a, b);
+    double w = 0.0, wd_sum = 0.0;                                         // (w: joint_mix_mass_kernel's accumulator, operation for operation)
+    for (int k = a + tid; k < b; k += RC_THREADS) {
+        const int tp = p_t[k];
+        if (tp < as_of) {
+            const double wk = rc_weight(t, tp, ihl);
+            w += wk;
+            if (DECAY) wd_sum += ((double)t - (double)tp) * wk;
+        }
+    }
+    double g_sum = 0.0, gd_sum = 0.0;
+    if (g >= 0 && g < C && r >= 0 && r < R && a < b) {                    // (uniform over the workgroup)
+        // the (e, r*) sub-run: rc_pair_run()'s two searches inside the entity run [a, b) this kernel already holds (rc_pair_run
+        // would look the run up again; keep the two alike).  r < R <= 1024: r + 1 cannot overflow
+        const int ra = rc_lower(p_rel, a, b, r), rb = rc_lower(p_rel, ra, b, r + 1);
+        const int k0 = rc_lower(p_other, ra, rb, g);
+        const int cut = rc_lower(p_t, k0, rc_lower(p_other, k0, rb, g + 1), as_of);
+        for (int j = k0 + tid; j < cut; j += RC_THREADS) {
+            const int tp = p_t[j];
+            const double wj = rc_weight(t, tp, ihl);
+            g_sum += wj;
+            if (DECAY) gd_sum += ((double)t - (double)tp) * wj;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        w += __shfl_xor(w, o);
+        g_sum += __shfl_xor(g_sum, o);
+        if (DECAY) {
+            wd_sum += __shfl_xor(wd_sum, o);
+            gd_sum += __shfl_xor(gd_sum, o);
+        }
+    }
+    if (lane == 0) {
+        s_w[wave] = w;
+        s_g[wave] = g_sum;
+        if (DECAY) {
+            s_wd[wave] = wd_sum;
+            s_gd[wave] = gd_sum;
+        }
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    double W = 0.0, G = 0.0, WD = 0.0, GD = 0.0;
+#pragma unroll
+    for (int k = 0; k < RC_WAVES; ++k) {
+        W += s_w[k];
+        G += s_g[k];
+        if (DECAY) {
+            WD += s_wd[k];
+            GD += s_gd[k];
+        }
+    }
+    w_out[row] = (float)W;
+    q_out[row] = W > 0.0 ? (float)(G / W) : 0.f;
+    if (DECAY) dq_out[row] = (W > 0.0 && G > 0.0) ? (float)(-M_LN2 * rc_cross(GD, W, G, WD) / (W * W)) : 0.f;
+}
+
+static int joint_gold_front(const int32_t* ent, const int32_t* rel, const int32_t* t, const int32_t* as_of, const int32_t* gold,
+                            int n, const int32_t* p_rel, const int32_t* p_other, const int32_t* p_t, int n_facts,
+                            const int32_t* ent_ptr, const int32_t* snap_ptr, int n_snaps, int num_ent, int R, int C,
+                            float inv_half_life, const float* ihl_row, bool decay, float* q, float* W, float* dq, void* stream) {
+    if (n < 0 || R < 1 || R > JM_MAX_R || C < 1 || C > RENET_RECURRENCE_MAX_C || n_facts < 0 || n_snaps < 0 || num_ent < 0)
+        return RENET_ERR_BADARG;
+    if (!decay && (!(inv_half_life >= 0.f) || !(inv_half_life <= FLT_MAX))) return RENET_ERR_BADARG;
+    if (n == 0) return RENET_OK;
+    if (!ent || !rel || !t || !as_of || !gold || !q || !W || !ent_ptr || !snap_ptr || (decay && (!ihl_row || !dq)))
+        return RENET_ERR_BADARG;
+    if (n_facts > 0 && (!p_rel || !p_other || !p_t)) return RENET_ERR_BADARG;
+    if (decay)
+        RENET_LAUNCH(joint_gold_rows_kernel<true>, dim3(n), dim3(RC_THREADS), 0, (hipStream_t)stream, ent, rel, t, as_of, gold,
+                     p_rel, p_other, p_t, n_facts, ent_ptr, snap_ptr, n_snaps, num_ent, R, C, 0.f, ihl_row, q, W, dq);
+    else
+        RENET_LAUNCH(joint_gold_rows_kernel<false>, dim3(n), dim3(RC_THREADS), 0, (hipStream_t)stream, ent, rel, t, as_of, gold,
+                     p_rel, p_other, p_t, n_facts, ent_ptr, snap_ptr, n_snaps, num_ent, R, C, inv_half_life, nullptr, q, W,
+                     nullptr);
+    RENET_LAUNCH_CHECK();
+    return RENET_OK;
+}
+
 }  // namespace
+
+int renet_joint_gold_rows(const int32_t* ent, const int32_t* rel, const int32_t* t, const int32_t* as_of, const int32_t* gold,
+                          int n, const int32_t* p_rel, const int32_t* p_other, const int32_t* p_t, int n_facts,
+                          const int32_t* ent_ptr, const int32_t* snap_ptr, int n_snaps, int num_ent, int R, int C,
+                          float inv_half_life, float* q, float* W, void* stream) {
+    return joint_gold_front(ent, rel, t, as_of, gold, n, p_rel, p_other, p_t, n_facts, ent_ptr, snap_ptr, n_snaps, num_ent, R, C,
+                            inv_half_life, nullptr, false, q, W, nullptr, stream);
+}
+
+// ihl_row is DEVICE memory: its range (finite, >= 0) is the caller's to keep; a bad decay gives a non-finite output, never an
+// address: it only feeds exp2
+int renet_joint_gold_rows_decay(const int32_t* ent, const int32_t* rel, const int32_t* t, const int32_t* as_of,
+                                const int32_t* gold, int n, const int32_t* p_rel, const int32_t* p_other, const int32_t* p_t,
+                                int n_facts, const int32_t* ent_ptr, const int32_t* snap_ptr, int n_snaps, int num_ent, int R,
+                                int C, const float* ihl_row, float* q, float* W, float* dq, void* stream) {
+    return joint_gold_front(ent, rel, t, as_of, gold, n, p_rel, p_other, p_t, n_facts, ent_ptr, snap_ptr, n_snaps, num_ent, R, C,
+                            0.f, ihl_row, true, q, W, dq, stream);
+}
 
 int renet_joint_mix_rows(const int32_t* ent, const int32_t* t, const int32_t* as_of, int G, const int32_t* p_rel,
                          const int32_t* p_other, const int32_t* p_t, int n_facts, const int32_t* ent_ptr,

@@ -36,7 +36,7 @@
 // from run to run.  Traffic: the row is read twice (the second time from L2) and written once.  Rows of any width up to
 // 2^20 columns are swept from memory; nothing is staged in LDS.
 #include "common.h"
-#include "recurrence_common.h"                            // the walk's geometry, rc_lower, rc_run, rc_weight, rc_pair_run
+#include "recurrence_common.h"                            // the walk's geometry, rc_lower, rc_run, rc_weight, rc_pair_run, rc_cross
 #include <float.h>
 #include <math.h>
 
@@ -301,14 +301,6 @@ __global__ __launch_bounds__(RC_THREADS) void recurrence_mix_rows_kernel(
 }
 
 // ---- the gold column's prior mass ---------------------------------------------------------------------------------------
-// a b - c d with BOTH products rounded (no fused multiply-add): equal products cancel to exactly 0, so a pair whose only
-// counted partner is the gold one (q = 1 whatever the decay) has dq = 0, not the rounding residue of one product
-__device__ __forceinline__ double rc_cross(double a, double b, double c, double d) {
-#pragma clang fp contract(off)
-    const double ab = a * b, cd = c * d;
-    return ab - cd;
-}
-
 // One workgroup per row, the mix kernel's steps 1 and 2 and its reduction tree for W (the same operations in the same order:
 // W here is stats_w there, bit for bit), and beside them the gold partner's group [k, cut) -- contiguous, ascending in time,
 // three binary searches -- summed in the same strided shares through the same tree.  Two floats out per row, nothing else.

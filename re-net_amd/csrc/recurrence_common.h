@@ -53,4 +53,12 @@ __device__ __forceinline__ void rc_pair_run(const int32_t* __restrict__ p_rel, i
     b = r == 0x7fffffff ? rb : rc_lower(p_rel, a, rb, r + 1);
 }
 
+// a b - c d with BOTH products rounded (no fused multiply-add): equal products cancel to exactly 0, so a pair whose only
+// counted partner is the gold one (q = 1 whatever the decay) has dq = 0, not the rounding residue of one product
+__device__ __forceinline__ double rc_cross(double a, double b, double c, double d) {
+#pragma clang fp contract(off)
+    const double ab = a * b, cd = c * d;
+    return ab - cd;
+}
+
 }  // namespace

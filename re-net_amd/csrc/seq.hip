@@ -222,6 +222,13 @@ __device__ __forceinline__ MixRow mix_row(float a, float q, float xt, float m, f
     }
     return o;
 }
+// THE JOINT MIX (renet_joint_mix_ce, renet_joint_mix_ce_planes): the row's loss is -log((1 - a) p_g pr + a q) with pr =
+// exp(lp) the other head's probability of ITS gold class; p_g pr = exp(x_g + lp - m) / sum, so it is mix_row() with the gold
+// logit x_g + lp_row[b] -- one more float per row, nothing per column; every branch holds with p_g pr in p_g's place.  A NULL
+// lp_row is the code as it stands.
+__device__ __forceinline__ float mix_gold(float xt, const float* __restrict__ lp_row, int b) {
+    return lp_row ? xt + lp_row[b] : xt;
+}
 
 // `dlogits` may ALIAS `logits` (the training path turns the logits into their gradient in place): neither pointer
 // may be __restrict__ -- with it hipcc is free to sink thread 0's read of x[target] below the barrier, past other
@@ -233,7 +240,7 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const float* logits,
                                                          const int32_t* __restrict__ target, int C, int ld,
                                                          float grad_scale, float* __restrict__ row_loss,
                                                          float* dlogits, __bf16* __restrict__ dl16, int ld16, const float* __restrict__ a_row,
-    const float* __restrict__ q_row, float* __restrict__ d_a) {
+    const float* __restrict__ q_row, float* __restrict__ d_a, const float* __restrict__ lp_row, float* __restrict__ s_row) {
     __shared__ float red[4];
     const int b = blockIdx.x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -259,10 +266,11 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const float* logits,
     asm volatile("" : "+v"(xt) :: "memory");
     __syncthreads();
     if constexpr (MIX) {
-        const MixRow mx = mix_row(a_row[b], q_row[b], xt, m, s, grad_scale);
+        const MixRow mx = mix_row(a_row[b], q_row[b], mix_gold(xt, lp_row, b), m, s, grad_scale);
         if (threadIdx.x == 0) {
             row_loss[b] = mx.loss;
             if (d_a) d_a[b] = mx.d_a;
+            if (s_row) s_row[b] = mx.s;
         }
         grad_scale *= mx.s;
     } else {
@@ -295,7 +303,7 @@ template <int NQ, bool MIX>
 __global__ __launch_bounds__(512, 4) void softmax_ce_reg_kernel(const float* logits, const int32_t* __restrict__ target,
                                                                 int C, int ld, float grad_scale,
                                                                 float* __restrict__ row_loss, float* dlogits, const float* __restrict__ a_row,
-    const float* __restrict__ q_row, float* __restrict__ d_a) {
+    const float* __restrict__ q_row, float* __restrict__ d_a, const float* __restrict__ lp_row, float* __restrict__ s_row) {
     __shared__ float red_m[8], red_s[8];
     __shared__ float red_xt;                            // MIX: the gold logit, from its owner to the whole workgroup
     const int b = blockIdx.x;
@@ -345,10 +353,11 @@ __global__ __launch_bounds__(512, 4) void softmax_ce_reg_kernel(const float* log
 #pragma unroll
     for (int w = 0; w < 8; ++w) s += red_s[w];
     if constexpr (MIX) {
-        const MixRow mx = mix_row(a_row[b], q_row[b], red_xt, m, s, grad_scale);
+        const MixRow mx = mix_row(a_row[b], q_row[b], mix_gold(red_xt, lp_row, b), m, s, grad_scale);
         if (mine) {
             row_loss[b] = mx.loss;
             if (d_a) d_a[b] = mx.d_a;
+            if (s_row) s_row[b] = mx.s;
         }
         grad_scale *= mx.s;
     } else {
@@ -375,7 +384,7 @@ __global__ __launch_bounds__(1024) void softmax_ce_lds_kernel(const float* logit
                                                               const int32_t* __restrict__ target, int C, int ld,
                                                               float grad_scale, float* __restrict__ row_loss,
                                                               float* dlogits, __bf16* __restrict__ dl16, int ld16, const float* __restrict__ a_row,
-    const float* __restrict__ q_row, float* __restrict__ d_a) {
+    const float* __restrict__ q_row, float* __restrict__ d_a, const float* __restrict__ lp_row, float* __restrict__ s_row) {
     extern __shared__ float row[];
     __shared__ float red[16];
     const int b = blockIdx.x;
@@ -423,10 +432,11 @@ __global__ __launch_bounds__(1024) void softmax_ce_lds_kernel(const float* logit
 #pragma unroll
     for (int w = 0; w < 16; ++w) s += red[w];
     if constexpr (MIX) {
-        const MixRow mx = mix_row(a_row[b], q_row[b], xt, m, s, grad_scale);
+        const MixRow mx = mix_row(a_row[b], q_row[b], mix_gold(xt, lp_row, b), m, s, grad_scale);
         if (threadIdx.x == 0) {
             row_loss[b] = mx.loss;
             if (d_a) d_a[b] = mx.d_a;
+            if (s_row) s_row[b] = mx.s;
         }
         grad_scale *= mx.s;
     } else {
@@ -490,7 +500,7 @@ __global__ __launch_bounds__(512) void softmax_ce_planes4_kernel(const float* __
                                                                  const int32_t* __restrict__ target, int B, int C, int ld,
                                                                  float grad_scale, float* __restrict__ row_loss,
                                                                  __bf16* __restrict__ P, size_t plane, int ld16, const float* __restrict__ a_row,
-    const float* __restrict__ q_row, float* __restrict__ d_a) {
+    const float* __restrict__ q_row, float* __restrict__ d_a, const float* __restrict__ lp_row, float* __restrict__ s_row) {
     __shared__ float red_m[8][4], red_s[8][4];
     __shared__ float red_xt[4];                         // MIX: the gold logits, from their owners to the whole workgroup
     __shared__ __attribute__((aligned(16))) char stage[3 * SP4_PLANE];
@@ -570,10 +580,11 @@ __global__ __launch_bounds__(512) void softmax_ce_planes4_kernel(const float* __
         one[r] = grad_scale;
         if constexpr (MIX) {
             const int b = min(b0 + r, B - 1);
-            const MixRow mx = mix_row(a_row[b], q_row[b], red_xt[r], m[r], acc, grad_scale);
+            const MixRow mx = mix_row(a_row[b], q_row[b], mix_gold(red_xt[r], lp_row, b), m[r], acc, grad_scale);
             if (live && tid == ((tgt[r] >> 2) & 511)) {
                 row_loss[b0 + r] = mx.loss;
                 if (d_a) d_a[b0 + r] = mx.d_a;
+                if (s_row) s_row[b0 + r] = mx.s;
             }
             one[r] = grad_scale * mx.s;
         } else {
@@ -722,7 +733,7 @@ __global__ __launch_bounds__(256) void softmax_ce_planes_generic_kernel(const fl
                                                                         const int32_t* __restrict__ target, int C, int ld,
                                                                         float grad_scale, float* __restrict__ row_loss,
                                                                         __bf16* __restrict__ P, size_t plane, int ld16, const float* __restrict__ a_row,
-    const float* __restrict__ q_row, float* __restrict__ d_a) {
+    const float* __restrict__ q_row, float* __restrict__ d_a, const float* __restrict__ lp_row, float* __restrict__ s_row) {
     __shared__ float red[4];
     const int b = blockIdx.x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -742,10 +753,11 @@ __global__ __launch_bounds__(256) void softmax_ce_planes_generic_kernel(const fl
     s = (red[0] + red[1]) + (red[2] + red[3]);
     const int t = target[b];
     if constexpr (MIX) {
-        const MixRow mx = mix_row(a_row[b], q_row[b], x[t], m, s, grad_scale);
+        const MixRow mx = mix_row(a_row[b], q_row[b], mix_gold(x[t], lp_row, b), m, s, grad_scale);
         if (threadIdx.x == 0) {
             row_loss[b] = mx.loss;
             if (d_a) d_a[b] = mx.d_a;
+            if (s_row) s_row[b] = mx.s;
         }
         grad_scale *= mx.s;
     } else {
@@ -991,7 +1003,7 @@ extern "C++" {
 template <bool MIX>
 static int softmax_ce_front(const float* logits, const int32_t* target, int B, int C, int ld, float grad_scale,
                             float* row_loss, float* dlogits, __bf16* dl16, int ld16, const float* a_row, const float* q_row,
-                            float* d_a, void* stream);
+                            float* d_a, const float* lp_row, float* s_row, void* stream);
 }
 
 int renet_softmax_ce(const float* logits, const int32_t* target, int B, int C, int ld,
@@ -1002,7 +1014,16 @@ int renet_softmax_ce(const float* logits, const int32_t* target, int B, int C, i
 int renet_mix_ce(const float* logits, const int32_t* target, const float* a_row, const float* q_row, int B, int C, int ld,
                  float grad_scale, float* row_loss, float* dlogits, float* d_a, void* stream) {
     if (!logits || !target || !a_row || !q_row || !row_loss) return RENET_ERR_BADARG;
-    return softmax_ce_front<true>(logits, target, B, C, ld, grad_scale, row_loss, dlogits, nullptr, 0, a_row, q_row, d_a, stream);
+    return softmax_ce_front<true>(logits, target, B, C, ld, grad_scale, row_loss, dlogits, nullptr, 0, a_row, q_row, d_a, nullptr, nullptr,
+                                  stream);
+}
+
+int renet_joint_mix_ce(const float* logits, const int32_t* target, const float* a_row, const float* q_row, const float* lp_row,
+                       int B, int C, int ld, float grad_scale, float* row_loss, float* dlogits, float* d_a, float* s_row,
+                       void* stream) {
+    if (!logits || !target || !a_row || !q_row || !lp_row || !row_loss) return RENET_ERR_BADARG;
+    return softmax_ce_front<true>(logits, target, B, C, ld, grad_scale, row_loss, dlogits, nullptr, 0, a_row, q_row, d_a, lp_row,
+                                  s_row, stream);
 }
 
 int renet_softmax_ce_bf16(const float* logits, const int32_t* target, int B, int C, int ld, float grad_scale,
@@ -1020,7 +1041,7 @@ int renet_softmax_ce_bf16(const float* logits, const int32_t* target, int B, int
 static int softmax_ce_impl(const float* logits, const int32_t* target, int B, int C, int ld, float grad_scale,
                            float* row_loss, float* dlogits, __bf16* dl16, int ld16, void* stream) {
     return softmax_ce_front<false>(logits, target, B, C, ld, grad_scale, row_loss, dlogits, dl16, ld16, nullptr, nullptr,
-                                   nullptr, stream);
+                                   nullptr, nullptr, nullptr, stream);
 }
 
 extern "C++" {
@@ -1028,16 +1049,16 @@ extern "C++" {
 template <bool MIX>
 static int softmax_ce_front(const float* logits, const int32_t* target, int B, int C, int ld, float grad_scale,
                             float* row_loss, float* dlogits, __bf16* dl16, int ld16, const float* a_row, const float* q_row,
-                            float* d_a, void* stream) {
+                            float* d_a, const float* lp_row, float* s_row, void* stream) {
     if (B < 0 || C <= 0 || ld < C) return RENET_ERR_BADARG;
     if (B == 0) return RENET_OK;
     const size_t lds = (size_t)C * sizeof(float);
     if (!dl16 && C >= 4096 && C <= 48 * 512) {
         const dim3 grid(B), blk(512);
         hipStream_t st = (hipStream_t)stream;
-        if (C <= 16 * 512) RENET_LAUNCH((softmax_ce_reg_kernel<16, MIX>), grid, blk, 0, st, logits, target, C, ld, grad_scale, row_loss, dlogits, a_row, q_row, d_a);
-        else if (C <= 32 * 512) RENET_LAUNCH((softmax_ce_reg_kernel<32, MIX>), grid, blk, 0, st, logits, target, C, ld, grad_scale, row_loss, dlogits, a_row, q_row, d_a);
-        else RENET_LAUNCH((softmax_ce_reg_kernel<48, MIX>), grid, blk, 0, st, logits, target, C, ld, grad_scale, row_loss, dlogits, a_row, q_row, d_a);
+        if (C <= 16 * 512) RENET_LAUNCH((softmax_ce_reg_kernel<16, MIX>), grid, blk, 0, st, logits, target, C, ld, grad_scale, row_loss, dlogits, a_row, q_row, d_a, lp_row, s_row);
+        else if (C <= 32 * 512) RENET_LAUNCH((softmax_ce_reg_kernel<32, MIX>), grid, blk, 0, st, logits, target, C, ld, grad_scale, row_loss, dlogits, a_row, q_row, d_a, lp_row, s_row);
+        else RENET_LAUNCH((softmax_ce_reg_kernel<48, MIX>), grid, blk, 0, st, logits, target, C, ld, grad_scale, row_loss, dlogits, a_row, q_row, d_a, lp_row, s_row);
     } else if (lds <= 128 * 1024 && C >= 4096) {
         static bool attr_set = false;      // benign race: the attribute is idempotent
         if (!attr_set) {
@@ -1047,10 +1068,10 @@ static int softmax_ce_front(const float* logits, const int32_t* target, int B, i
             attr_set = true;
         }
         RENET_LAUNCH(softmax_ce_lds_kernel<MIX>, dim3(B), dim3(1024), lds, (hipStream_t)stream, logits, target, C, ld,
-                     grad_scale, row_loss, dlogits, dl16, ld16, a_row, q_row, d_a);
+                     grad_scale, row_loss, dlogits, dl16, ld16, a_row, q_row, d_a, lp_row, s_row);
     } else {
         RENET_LAUNCH(softmax_ce_kernel<MIX>, dim3(B), dim3(256), 0, (hipStream_t)stream, logits, target, C, ld,
-                     grad_scale, row_loss, dlogits, dl16, ld16, a_row, q_row, d_a);
+                     grad_scale, row_loss, dlogits, dl16, ld16, a_row, q_row, d_a, lp_row, s_row);
     }
     RENET_LAUNCH_CHECK();
     return RENET_OK;
@@ -1059,7 +1080,7 @@ static int softmax_ce_front(const float* logits, const int32_t* target, int B, i
 template <bool MIX>
 static int softmax_ce_planes_front(const float* logits, const int32_t* target, int B, int C, int ld, float grad_scale,
                                    float* row_loss, void* dl_planes, size_t plane, int ld16, int rows16, const float* a_row,
-                                   const float* q_row, float* d_a, void* stream) {
+                                   const float* q_row, float* d_a, const float* lp_row, float* s_row, void* stream) {
     if (B < 0 || C <= 0 || ld < C || !dl_planes || ld16 < C || (ld16 & 15) || rows16 < ((B + 15) & ~15)) return RENET_ERR_BADARG;
     if (plane < (size_t)rows16 * ld16) return RENET_ERR_BADARG;
     if (B == 0) return RENET_OK;
@@ -1083,9 +1104,9 @@ static int softmax_ce_planes_front(const float* logits, const int32_t* target, i
         (plane & 7) == 0) {
         const int quads = (B + 3) / 4;
         const dim3 grid((unsigned)((quads + 31) & ~31)), blk(512);   // whole groups of 8 XCDs x 4 quads
-        if (ld16 <= 4 * 2048) RENET_LAUNCH((softmax_ce_planes4_kernel<4, MIX>), grid, blk, 0, st, logits, target, B, C, ld, grad_scale, row_loss, P, plane, ld16, a_row, q_row, d_a);
-        else if (ld16 <= 8 * 2048) RENET_LAUNCH((softmax_ce_planes4_kernel<8, MIX>), grid, blk, 0, st, logits, target, B, C, ld, grad_scale, row_loss, P, plane, ld16, a_row, q_row, d_a);
-        else RENET_LAUNCH((softmax_ce_planes4_kernel<12, MIX>), grid, blk, 0, st, logits, target, B, C, ld, grad_scale, row_loss, P, plane, ld16, a_row, q_row, d_a);
+        if (ld16 <= 4 * 2048) RENET_LAUNCH((softmax_ce_planes4_kernel<4, MIX>), grid, blk, 0, st, logits, target, B, C, ld, grad_scale, row_loss, P, plane, ld16, a_row, q_row, d_a, lp_row, s_row);
+        else if (ld16 <= 8 * 2048) RENET_LAUNCH((softmax_ce_planes4_kernel<8, MIX>), grid, blk, 0, st, logits, target, B, C, ld, grad_scale, row_loss, P, plane, ld16, a_row, q_row, d_a, lp_row, s_row);
+        else RENET_LAUNCH((softmax_ce_planes4_kernel<12, MIX>), grid, blk, 0, st, logits, target, B, C, ld, grad_scale, row_loss, P, plane, ld16, a_row, q_row, d_a, lp_row, s_row);
     } else if (!MIX && aligned && C >= 2048 && ld16 <= 12 * 2048) {
         const dim3 grid((unsigned)((B + 127) & ~127)), blk(512);     // whole groups of 8 XCDs x 16 rows (see the kernel)
         if (ld16 <= 4 * 2048) RENET_LAUNCH((softmax_ce_planes_kernel<4>), grid, blk, 0, st, logits, target, B, C, ld, grad_scale, row_loss, P, plane, ld16);
@@ -1093,7 +1114,7 @@ static int softmax_ce_planes_front(const float* logits, const int32_t* target, i
         else RENET_LAUNCH((softmax_ce_planes_kernel<12>), grid, blk, 0, st, logits, target, B, C, ld, grad_scale, row_loss, P, plane, ld16);
     } else {
         RENET_LAUNCH(softmax_ce_planes_generic_kernel<MIX>, dim3(B), dim3(256), 0, st, logits, target, C, ld, grad_scale,
-                     row_loss, P, plane, ld16, a_row, q_row, d_a);
+                     row_loss, P, plane, ld16, a_row, q_row, d_a, lp_row, s_row);
     }
     RENET_LAUNCH_CHECK();
     return RENET_OK;
@@ -1104,7 +1125,7 @@ static int softmax_ce_planes_front(const float* logits, const int32_t* target, i
 int renet_softmax_ce_planes(const float* logits, const int32_t* target, int B, int C, int ld, float grad_scale,
                             float* row_loss, void* dl_planes, size_t plane, int ld16, int rows16, void* stream) {
     return softmax_ce_planes_front<false>(logits, target, B, C, ld, grad_scale, row_loss, dl_planes, plane, ld16, rows16,
-                                          nullptr, nullptr, nullptr, stream);
+                                          nullptr, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 int renet_mix_ce_planes(const float* logits, const int32_t* target, const float* a_row, const float* q_row, int B, int C,
@@ -1112,7 +1133,15 @@ int renet_mix_ce_planes(const float* logits, const int32_t* target, const float*
                         float* d_a, void* stream) {
     if (!logits || !target || !a_row || !q_row || !row_loss) return RENET_ERR_BADARG;
     return softmax_ce_planes_front<true>(logits, target, B, C, ld, grad_scale, row_loss, dl_planes, plane, ld16, rows16, a_row,
-                                         q_row, d_a, stream);
+                                         q_row, d_a, nullptr, nullptr, stream);
+}
+
+int renet_joint_mix_ce_planes(const float* logits, const int32_t* target, const float* a_row, const float* q_row,
+                              const float* lp_row, int B, int C, int ld, float grad_scale, float* row_loss, void* dl_planes,
+                              size_t plane, int ld16, int rows16, float* d_a, float* s_row, void* stream) {
+    if (!logits || !target || !a_row || !q_row || !lp_row || !row_loss) return RENET_ERR_BADARG;
+    return softmax_ce_planes_front<true>(logits, target, B, C, ld, grad_scale, row_loss, dl_planes, plane, ld16, rows16, a_row,
+                                         q_row, d_a, lp_row, s_row, stream);
 }
 
 int renet_zero(float* x, size_t n, void* stream) {

@@ -276,7 +276,7 @@ class RENet(nn.Module):
         return None if hbatch is None else self.prepare_both_from_host(hbatch)
 
     @_moded
-    def loss_prepared_both(self, prep, row_tap=None, copy=None):
+    def loss_prepared_both(self, prep, row_tap=None, copy=None, event_copy=None):
         """loss_prepared(prep_s) + loss_prepared(prep_o) evaluated as ONE pass over the 2B sequences of the merged
         batch (extension of the reference API; train.py:136-138 adds the two losses of the same quadruples).  The
         aggregator, both encoders and both heads are shared between the directions (model.py:26-40), the directions
@@ -286,10 +286,23 @@ class RENet(nn.Module):
         copy: a recurrence.CopyRows of the batch, or its (a_row, q_row) in the batch's row order -- the ENTITY head's loss
         goes through the copy mix of the recurrence prior, -log((1 - a) softmax[gold] + a q) (ops._head_forward); a_row may
         require grad (a learned recurrence.CopyGate).  The relation head is unchanged.  Such a step is not in the C launch
-        list: it runs the autograd path and pays its host enqueue.  None: today's path, launch for launch."""
+        list: it runs the autograd path and pays its host enqueue.  None: today's path, launch for launch.
+        event_copy: a recurrence.EventCopyRows of the batch, or its (a_row, q_row) -- the EVENT loss through the joint mix,
+        -log((1 - a) softmax[gold] softmax_r[gold relation] + a q) per row with q the prior's mass on the gold (relation,
+        partner) pair (ops.DualHeadCEFn, event_a / event_q): both heads train through it, the relation term has weight 1 (not
+        0.1).  Never with copy=; refused for sharded batches and in bf16-storage mode as copy= is; not in the C launch list."""
         g = prep.g
         self.aggregator.last_batch = g
-        copy_a = copy_q = None
+        copy_a = copy_q = event_a = event_q = None
+        if event_copy is not None:
+            if copy is not None:
+                raise ValueError('loss_prepared_both: copy= and event_copy= are two different losses: give one of them')
+            if getattr(prep, 'sharded', False):
+                raise ValueError('loss_prepared_both: event_copy= with a sharded batch is not supported (the gate gradients of '
+                                 'the ranks are not exchanged)')
+            if K.current_mode() == 'bf16s':
+                raise ValueError('loss_prepared_both: event_copy= has no bf16-storage writer: use another GEMM mode')
+            event_a, event_q = event_copy.batch(prep)[:2] if hasattr(event_copy, 'batch') else event_copy
         if copy is not None:
             if getattr(prep, 'sharded', False):
                 raise ValueError('loss_prepared_both: copy= with a sharded batch is not supported (the gate gradients of the '
@@ -299,7 +312,7 @@ class RENet(nn.Module):
             copy_a, copy_q = copy.batch(prep)[:2] if hasattr(copy, 'batch') else copy
         # the same launch sequence issued from C (csrc/step.cpp): two C-ABI calls per step instead of ~55; bit-identical
         import step_plan
-        if copy is None and step_plan.eligible(self, prep):
+        if copy is None and event_copy is None and step_plan.eligible(self, prep):
             return step_plan.StepFn.apply(self, prep, row_tap, *step_plan.model_params(self))
         # a shard of a batch whose graph every rank replicates (prepare_both(shard=...)): rank-independent dropout
         # masks at the graph-side sites, so that the N-rank step equals the 1-rank step
@@ -318,7 +331,7 @@ class RENet(nn.Module):
         return ops.DualHeadCEFn.apply(self.ent_embeds, prep.s_idx, s_h, self.rel_embeds, prep.r_idx,
                                       self.linear.weight, self.linear.bias, prep.o_idx, s_q,
                                       self.linear_r.weight, self.linear_r.bias, prep.r_label, prep.plan_s,
-                                      prep.plan_r, p, seed1, seed2, scale, 0.1, row_tap, copy_a, copy_q)
+                                      prep.plan_r, p, seed1, seed2, scale, 0.1, row_tap, copy_a, copy_q, event_a, event_q)
 
     def prepare(self, triplets, hist, graph_dict, subject=True):
         """Host + upload half of one direction of a training step: batch graph, packed layout and plans,

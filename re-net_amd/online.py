@@ -83,7 +83,8 @@ def _train_step(module, optimizer, loss_fn, grad_norm, head_passes=1):
 
 
 # ---- RENet.learn_observed ----------------------------------------------------------------------------------------------
-def _learn_observed(self, obs, idx, optimizer, steps=1, batch_size=1024, grad_norm=1.0, prior=None, gate_optimizer=None):
+def _learn_observed(self, obs, idx, optimizer, steps=1, batch_size=1024, grad_norm=1.0, prior=None, gate_optimizer=None,
+                    event_prior=None):
     """Training steps on the stream positions idx of a resident stream (preprocess.ObservedStream after resident() /
     observe(), or its gpu_builder.ObservedStore): the positions are cut into batches of batch_size <= gpu_builder.MAX_BOTH in
     the given order, and each batch is ONE merged two-direction step in train mode -- prepare_both_device ->
@@ -96,9 +97,21 @@ def _learn_observed(self, obs, idx, optimizer, steps=1, batch_size=1024, grad_no
     (recurrence.CopyRows of each batch, loss_prepared_both(prep, copy=)), the weights learn what the copy term does not
     explain, and the losses returned are the mixed ones.  A recurrence.RecurrencePrior is a fixed mix; a recurrence.CopyGate
     with a gate_optimizer (any torch.optim over gate.parameters()) learns its gates in the same step -- their gradients stay
-    out of the model's clip norm.  A step with a prior is not in the C launch list: it pays the autograd path's host enqueue."""
+    out of the model's clip norm.  A step with a prior is not in the C launch list: it pays the autograd path's host enqueue.
+    event_prior (never with prior=): a RecurrencePrior or a CopyGate(per_relation=False) -- every batch gets a
+    recurrence.EventCopyRows and the step trains BOTH heads, and with a gate_optimizer the gate, through the JOINT mix
+    (loss_prepared_both(prep, event_copy=)): the losses returned are the mean joint losses (relation term at weight 1)."""
     import gpu_builder
-    if prior is not None:
+    if event_prior is not None:
+        import recurrence
+        if prior is not None:
+            raise ValueError('learn_observed: prior= and event_prior= are two different losses: give one of them')
+        recurrence._event_gate(event_prior)
+        if gate_optimizer is not None and not isinstance(event_prior, recurrence.CopyGate):
+            raise ValueError('learn_observed: gate_optimizer needs event_prior= to be a recurrence.CopyGate')
+        if getattr(self, 'gemm_mode', None) == 'bf16s' or K.current_mode() == 'bf16s':
+            raise ValueError('learn_observed: event_prior= has no bf16-storage writer: use another GEMM mode')
+    elif prior is not None:
         import recurrence
         recurrence._checked(prior)
         if gate_optimizer is not None and not isinstance(prior, recurrence.CopyGate):
@@ -127,13 +140,18 @@ def _learn_observed(self, obs, idx, optimizer, steps=1, batch_size=1024, grad_no
                 if prep.g.S == 0:
                     raise ValueError('learn_observed: no position of the batch has a history (the first timestamp of a '
                                      'stream): nothing to encode')
-                if prior is None:
+                if prior is None and event_prior is None:
                     losses.append(_train_step(self, optimizer, lambda: self.loss_prepared_both(prep), grad_norm))
                     continue
                 if gate_optimizer is not None:
                     gate_optimizer.zero_grad()
-                rows = recurrence.CopyRows(store, part, prior)
-                losses.append(_train_step(self, optimizer, lambda: self.loss_prepared_both(prep, copy=rows), grad_norm))
+                if event_prior is not None:
+                    rows = recurrence.EventCopyRows(store, part, event_prior)
+                    losses.append(_train_step(self, optimizer, lambda: self.loss_prepared_both(prep, event_copy=rows),
+                                              grad_norm))
+                else:
+                    rows = recurrence.CopyRows(store, part, prior)
+                    losses.append(_train_step(self, optimizer, lambda: self.loss_prepared_both(prep, copy=rows), grad_norm))
                 if gate_optimizer is not None:
                     gate_optimizer.step()
                     gate_optimizer.zero_grad()

@@ -644,13 +644,20 @@ def dual_gru(x, xr, enc, enc_r, step_off, total_rows):
                             xr, enc_r.weight_ih_l0, enc_r.weight_hh_l0, enc_r.bias_ih_l0, enc_r.bias_hh_l0)
 
 
-def _head_forward(a, ia, hmid, c, ic, weight, bias, target, drop_p, seed, grad_scale, need_grad, row_loss=None, copy=None):
+def _head_forward(a, ia, hmid, c, ic, weight, bias, target, drop_p, seed, grad_scale, need_grad, row_loss=None, copy=None,
+                  event=None):
     """One score head up to the per-row losses: [a[ia] | hmid | c[ic]] -> dropout -> Linear -> CE.
     -> (row_loss[B], feat, logits-or-gradient buffer, bf16 / planes gradient matrix or None, operand handle of feat or None,
     d_a or None).  copy = (a_row, q_row), fp32 device [B]: the loss goes THROUGH THE COPY MIX of the recurrence prior,
     row_loss = -log((1 - a) softmax[gold] + a q) (K.mix_ce_planes / K.mix_ce in the CE's place: the same gradient buffers,
-    every row scaled by its s <= 1, so the f16x3 bound grad_scale stays valid) and d_a[B] = grad_scale * d row_loss / d a."""
-    if copy is not None and K.current_mode() == 'bf16s':
+    every row scaled by its s <= 1, so the f16x3 bound grad_scale stays valid) and d_a[B] = grad_scale * d row_loss / d a.
+    event = (a_row, q_row, lp): the loss goes through the JOINT mix instead (K.joint_mix_ce_planes / K.joint_mix_ce),
+    row_loss = -log((1 - a) softmax[gold] exp(lp) + a q); lp is a callable, called once the logits exist and right before the
+    CE writer, that returns the other head's log-probability of its gold class (fp32 [B]) -- the caller joins that head's
+    stream in it.  The tuple then ends with s_row[B], the scalar of every row."""
+    if copy is not None and event is not None:
+        raise ValueError('copy= and event= are two different losses: give one of them')
+    if (copy is not None or event is not None) and K.current_mode() == 'bf16s':
         raise ValueError('the loss through the copy mix has no bf16-storage writer: use another GEMM mode with copy=')
     feat = K.concat3_fwd(a, ia, hmid, c, ic, drop_p, seed)
     if need_grad and debug_tap is None and K.use_planes(weight, weight.shape[0]):
@@ -667,6 +674,10 @@ def _head_forward(a, ia, hmid, c, ic, weight, bias, target, drop_p, seed, grad_s
         feat_pl1 = K.pack_planes(feat, ones_col=True)
         K.gemm_planes(K.PlanesMat(feat_pl1.p, feat_pl1.R, feat_pl1.C - 1), w_pl, tb=True, bias=bias, out=logits)
         d_a = None
+        if event is not None:
+            row_loss, dl_pl, d_a, s_row = K.joint_mix_ce_planes(logits, target, event[0], event[1], event[2](), grad_scale,
+                                                                row_loss=row_loss)
+            return row_loss, feat, feat.new_empty(0), dl_pl, feat_pl1, d_a, s_row
         if copy is None:
             row_loss, dl_pl = K.softmax_ce_planes(logits, target, grad_scale, row_loss=row_loss)
         else:
@@ -677,6 +688,10 @@ def _head_forward(a, ia, hmid, c, ic, weight, bias, target, drop_p, seed, grad_s
     if debug_tap is not None:
         debug_tap('logits', logits)
     dl_bf16 = d_a = None
+    if event is not None:
+        row_loss, d_a, s_row = K.joint_mix_ce(logits, target, event[0], event[1], event[2](), grad_scale, need_grad,
+                                              row_loss=row_loss)
+        return row_loss, feat, logits, None, (feat_op if K.is_handle(feat_op) else None), d_a, s_row
     if copy is not None:
         row_loss, d_a = K.mix_ce(logits, target, copy[0], copy[1], grad_scale, need_grad, row_loss=row_loss)
     elif need_grad and K.current_mode() == 'bf16s':
@@ -847,13 +862,31 @@ class DualHeadCEFn(Function):
     @staticmethod
     @_fwd_mode
     def forward(ctx, a, ia, h1, c, ic, w1, b1, target1, h2, w2, b2, target2, plan_a, plan_c, drop_p, seed1, seed2,
-                loss_scale=1.0, rel_weight=0.1, row_tap=None, copy_a=None, copy_q=None):
+                loss_scale=1.0, rel_weight=0.1, row_tap=None, copy_a=None, copy_q=None, event_a=None, event_q=None):
         """row_tap: a list that receives (row losses [2b]: entity head rows then relation head rows, s1, s2) -- the weights
         with which the returned scalar sums them (RENet.forward's fused directions split the merged loss by direction).
         copy_a / copy_q: as for HeadCEFn (d_a and d_q included), for the ENTITY head only; the relation head is the plain
-        CE."""
+        CE.
+        event_a / event_q (both or neither; never with copy_a / copy_q): the EVENT loss through the joint mix, per row
+            L = -log((1 - a) p_gold pr_gold + a q),   returned: loss_scale / b * sum(L)
+        with q the prior's mass on the gold (relation, partner) pair (K.joint_gold_rows).  Both terms of the joint have weight
+        1: rel_weight is NOT applied.  The relation head runs first, on the side stream, with the ENTITY head's grad_scale;
+        its row losses give lp = -row_loss; the side stream is joined before the entity head's CE writer (the joint entry),
+        which returns s per row; the relation head's gradient rows are multiplied by it (a dense [B, R] matrix: a relation
+        head wide enough for the planes path, renet_hip.PLANES_MIN_CLASSES classes, is refused before any launch).
+        event_a / event_q receive g * d_a
+        and g * d_q as copy_a / copy_q do.  row_tap receives L in the entity rows and zeros, with weight 0, in the relation
+        rows."""
         ctx.srcs = (a, c, w1, b1, w2, b2)
         copy = _copy_pair(copy_a, copy_q, h1.shape[0])
+        event = _copy_pair(event_a, event_q, h1.shape[0])
+        if event is not None:
+            if copy is not None:
+                raise ValueError('copy_a / copy_q and event_a / event_q are two different losses: give one pair')
+            if K.current_mode() == 'bf16s':
+                raise ValueError('the loss through the joint mix has no bf16-storage writer: use another GEMM mode')
+            return DualHeadCEFn._forward_event(ctx, a, ia, h1, c, ic, w1, b1, target1, h2, w2, b2, target2, plan_a, plan_c,
+                                               drop_p, seed1, seed2, loss_scale, row_tap, event)
         a, h1, h2, c, w1, b1, w2, b2 = (_c(t) for t in (a, h1, h2, c, w1, b1, w2, b2))
         b, d = h1.shape
         need_grad = any(ctx.needs_input_grad)
@@ -880,6 +913,45 @@ class DualHeadCEFn(Function):
         if row_tap is not None:
             row_tap.append((rl.detach(), s1, s2))
         return torch.dot(rl, _loss_weight_vector(b, s1, s2, h1.device))
+
+    @staticmethod
+    def _forward_event(ctx, a, ia, h1, c, ic, w1, b1, target1, h2, w2, b2, target2, plan_a, plan_c, drop_p, seed1, seed2,
+                       loss_scale, row_tap, event):
+        a, h1, h2, c, w1, b1, w2, b2 = (_c(t) for t in (a, h1, h2, c, w1, b1, w2, b2))
+        b, d = h1.shape
+        need_grad = any(ctx.needs_input_grad)
+        s1 = float(loss_scale) / b
+        if need_grad and debug_tap is None and K.use_planes(w2, w2.shape[0]):
+            # (before any launch.  The relation head's gradient rows are scaled by s as a dense [B, R] matrix; a relation head
+            # wide enough for the planes GEMMs -- renet_hip.PLANES_MIN_CLASSES classes -- keeps no dense gradient)
+            raise ValueError('the loss through the joint mix scales the relation head\'s dense gradient rows: a relation head '
+                             'with %d or more classes (the planes path) is not supported' % K.PLANES_MIN_CLASSES)
+        rl = torch.empty(2 * b, device=h1.device, dtype=torch.float32)
+        sd = _Side(h1.device)
+        # (the relation head FIRST, also under debug_tap, where the ordinary path lets the entity head report first: the entity
+        # head's writer needs the relation head's row losses)
+        with sd():
+            _, feat2, lg2, dl2, fop2, _ = _head_forward(a, ia, h2, None, None, w2, b2, target2, drop_p, seed2, s1, need_grad,
+                                                        row_loss=rl[b:])
+
+        def lp():
+            sd.join()                                        # an event wait: the relation head ended long before
+            return torch.neg(rl[b:])
+        _, feat1, lg1, dl1, fop1, ctx.d_gate, s_row = _head_forward(a, ia, h1, c, ic, w1, b1, target1, drop_p, seed1, s1,
+                                                                    need_grad, row_loss=rl[:b], event=event + (lp,))
+        if need_grad:
+            lg2.mul_(s_row.unsqueeze(1))                     # the relation head's CE gradient times the row's s
+        ctx.d_q = copy_q_grad(event[0], rl[:b], s1) if ctx.needs_input_grad[23] else None
+        ctx.event = True
+        ctx.meta = (d, drop_p, seed1, seed2, plan_a, plan_c, a.shape, c.shape)
+        ctx.grad_scales = (s1, s1)                           # (s <= 1: the f16x3 bound of the relation head stays valid)
+        if need_grad:
+            ctx.save_for_backward(feat1, lg1, w1, feat2, lg2, w2)
+            ctx.consumed = False
+            ctx.bf16 = (dl1, fop1, dl2, fop2)
+        if row_tap is not None:
+            row_tap.append((torch.cat((rl[:b].detach(), torch.zeros_like(rl[b:]))), s1, 0.0))
+        return rl[:b].sum() * s1
 
     @staticmethod
     @_bwd_mode
@@ -911,9 +983,12 @@ class DualHeadCEFn(Function):
             grad_done(ctx.srcs[5])
         da1.add_(da2)                                        # same rows ent[s] in both heads: one scatter-add
         d_a, d_c = _scatter_head_rows(da1, dc1, plan_a, plan_c, t_a, t_c, a_shape, c_shape)
-        d_gate = ctx.d_gate * g if ctx.d_gate is not None and ctx.needs_input_grad[20] else None
+        gate_slot = 22 if getattr(ctx, 'event', False) else 20
+        d_gate = ctx.d_gate * g if ctx.d_gate is not None and ctx.needs_input_grad[gate_slot] else None
         d_q = ctx.d_q * g if ctx.d_q is not None else None
-        return (d_a, None, dh1, d_c, None, d_w1, d_b1, None, dh2, d_w2, d_b2, None) + (None,) * 8 + (d_gate, d_q)
+        if gate_slot == 22:
+            return (d_a, None, dh1, d_c, None, d_w1, d_b1, None, dh2, d_w2, d_b2, None) + (None,) * 10 + (d_gate, d_q)
+        return (d_a, None, dh1, d_c, None, d_w1, d_b1, None, dh2, d_w2, d_b2, None) + (None,) * 8 + (d_gate, d_q, None, None)
 
 
 class SegmentPoolFn(Function):

@@ -54,9 +54,22 @@ MODEL-FREE baseline in evaluate_events_observed's layout (the uniform joint thro
 and tie rule).  The baseline's and the mixed event numbers go beside event numbers of the SAME protocol only, and with their
 alpha and half_life.  `topk_events` is the baseline's top-k in predict_events_observed's layout, through that entry's own tail.
 
+TRAINING THROUGH THE JOINT MIX.  The training loss of a row is the unmixed event loss already, CE_e + CE_r = -J[r*, g]; with
+EventCopyRows (RENet.loss_prepared_both(prep, event_copy=), RENet.learn_observed(event_prior=, gate_optimizer=)) it is
+
+    L = -log((1 - a) p_g pr + a q) = -M[r*, g],     q = G / W from renet_joint_gold_rows(_decay), W entity-wide as above
+
+and both heads receive their plain CE gradient times ONE scalar per row, s = (1 - a) p_g pr / m (ops.DualHeadCEFn, event_a /
+event_q; renet_joint_mix_ce(_planes) is renet_mix_ce(_planes) with lp = log pr added to the gold logit).  a is a
+RecurrencePrior's alpha or the side's single gate of a CopyGate(per_relation=False), with autograd; a gate that learns its
+decay gets dq from the decay entry.  fit_event_gate fits such a gate with the model frozen: it PRODUCES the two numbers
+event_scalars() reads.  Numbers with a fitted event gate are a protocol of their own: report them with the INITIAL alpha and
+half_life, the fitting split, steps and learning rate.
+
 Not covered: rollout (generated facts in a prior are a protocol question of their own; generate_events_observed and
-evaluate_rollout take no prior: generation stays the model's own), training through the joint mix, a learned per-relation
-gate for events, fusing the mix into renet_joint_row_offsets or the rank kernel (measured first: profiles/event_prior.md), a
+evaluate_rollout take no prior: generation stays the model's own), a learned per-relation
+gate for events, evaluate_online with an event prior, the C launch list for steps with a prior, fusing the mix into
+renet_joint_row_offsets or the rank kernel (measured first: profiles/event_prior.md), a
 relation-free term, a per-relation decay for events, bf16-storage mode, data-parallel gate gradients."""
 import math
 
@@ -435,6 +448,126 @@ class CopyRows(object):
         a = _PermuteFn.apply(self.a_seq, perm) if self.a_seq.requires_grad else self.a_seq[perm]
         q = _PermuteFn.apply(self.q_seq, perm) if self.q_seq.requires_grad else self.q_seq[perm]
         return a, q, self.W_seq[perm]
+
+
+def _event_gate(prior):
+    """prior checked for the EVENT loss: a RecurrencePrior, or a CopyGate(per_relation=False) (event_scalars' refusal)."""
+    _checked(prior)
+    if isinstance(prior, CopyGate):
+        if prior.per_relation:
+            raise ValueError('the event entries take a RecurrencePrior or a CopyGate(per_relation=False), not a per-relation '
+                             'gate: with the relation open, a gate per relation does not give a normalised joint')
+        prior.check()
+    return prior
+
+
+class EventCopyRows(object):
+    """The event twin of CopyRows: (a_row, q_row, W) of ONE merged training batch for RENet.loss_prepared_both(prep,
+    event_copy=), the loss through the JOINT mix of renet_joint_mix_rows.  Sequence i < n is position i's 'ob' direction (given
+    s, gold pair (r, o)), sequence n + i its 'sub' direction (given o, gold pair (r, s)); as_of = t.  Two renet_joint_gold_rows
+    launches, one per role: q = G / W with the ENTITY-WIDE W (every relation), not CopyRows' per-(s, r) one.  a is a
+    RecurrencePrior's alpha, or the side's single gate of a CopyGate(per_relation=False), WITH autograd (rows_at with the
+    side's one index: its gradient reaches `logit` through the deterministic segmented add); zeroed where W = 0.  A gate that
+    learns its decay: renet_joint_gold_rows_decay with the side's rate on every row, and q with autograd (_DecayQFn).  A
+    per-relation gate is refused (event_scalars' message)."""
+
+    def __init__(self, store, idx, prior):
+        _event_gate(prior)
+        idx = np.asarray(idx, dtype=np.int64).reshape(-1)
+        rows = QueryRows(store, idx)
+        base, n = rows.base, len(idx)
+        gate = isinstance(prior, CopyGate)
+        learned = gate and prior.learn_half_life
+        if gate:
+            index = np.concatenate((np.full(n, SIDES['ob'], dtype=np.int64), np.full(n, SIDES['sub'], dtype=np.int64)))
+        if learned:
+            rate = prior.rate_rows_at(index)                            # [2n], with autograd when log_rate learns
+            ihl = rate.detach().contiguous()
+        q, w, dq = [], [], []
+        for role in (0, 1):
+            args = (rows.ent[role], rows.rel, rows.t, rows.as_of, rows.ent[1 - role], rows.tables[role],
+                    base.t['ent_ptr%d' % role], base.t['snap_ptr%d' % role], base.num_ent, base.num_rels, base.num_ent)
+            if learned:
+                qq, ww, dd = K.joint_gold_rows_decay(*args, ihl[role * n:(role + 1) * n])
+                dq.append(dd)
+            else:
+                qq, ww = K.joint_gold_rows(*args, prior.inv_half_life)
+            q.append(qq)
+            w.append(ww)
+        self.n = n
+        self.q_seq, self.W_seq = torch.cat(q), torch.cat(w)
+        if learned and rate.requires_grad:
+            self.q_seq = _DecayQFn.apply(rate, self.q_seq, torch.cat(dq))
+        if gate:
+            a = prior.rows_at(index)
+        else:
+            a = torch.full((2 * n,), prior.alpha, device=self.q_seq.device, dtype=torch.float32)
+        self.a_seq = torch.where(self.W_seq > 0, a, torch.zeros_like(a))
+
+    batch = CopyRows.batch
+
+
+def fit_event_gate(model, obs, idx, gate, optimizer, steps=1, max_batch=4096):
+    """fit_gate for EVENTS, the model FROZEN: `steps` optimizer steps of the CopyGate(per_relation=False) `gate` on the joint
+    loss -log((1 - a) p(o | s, r) p(r | s) + a q) of the stream positions idx, both directions.  Per step and per batch of
+    max_batch positions the entity scores and the relation logits of the gold rows are computed under no_grad as
+    evaluate_observed(relation=True) computes them (eval mode); the relation head's row loss gives lp, renet_joint_mix_ce
+    takes the entity scores with dlogits = NULL -- only d_a and d_q flow --, and the gradient of the MEAN joint loss over all
+    rows of both directions is accumulated before ONE optimizer.step().  -> the mean joint loss per step (Python floats,
+    before that step's update).  The model's parameters and mode are left as found."""
+    import model as M
+    import ops
+    if not isinstance(gate, CopyGate):
+        raise ValueError('fit_event_gate fits a recurrence.CopyGate(per_relation=False)')
+    _event_gate(gate)
+    store = M._observed_store(obs)
+    idx = M._observed_positions(store, idx)
+    max_batch = max(1, int(max_batch))
+    n = len(idx)
+    dev = gate.logit.device
+    was_training = model.training
+    model.eval()
+    out = []
+    try:
+        for _ in range(int(steps)):
+            optimizer.zero_grad()
+            total = torch.zeros((), device=dev)
+            with torch.no_grad():
+                cuts = M._observed_cuts(M._observed_chunks(model, store, idx, True), max_batch)
+            while True:
+                with torch.no_grad():
+                    cut = next(cuts, None)
+                if cut is None:
+                    break
+                c, d, (feat_ob, feat_sub, featr_ob, featr_sub) = cut
+                part = idx[c:d]
+                rows = EventCopyRows(store, part, gate)
+                m = len(part)
+                rel = rows_rel(store, part)
+                for k, (feat, featr, gold) in enumerate(((feat_ob, featr_ob, rows_gold(store, part, 'ob')),
+                                                         (feat_sub, featr_sub, rows_gold(store, part, 'sub')))):
+                    with torch.no_grad():
+                        pred = M._linear_eval(model.linear, feat)
+                        lp = -K.softmax_ce(M._linear_eval(model.linear_r, featr), rel, 1.0, False)
+                    a, q = rows.a_seq[k * m:(k + 1) * m], rows.q_seq[k * m:(k + 1) * m]
+                    row_loss, d_a, _ = K.joint_mix_ce(pred, gold, a.detach().contiguous(), q.detach().contiguous(), lp,
+                                                      1.0 / (2 * n), False)
+                    if a.requires_grad:
+                        a.backward(d_a, retain_graph=True)
+                    if q.requires_grad:                                  # (a learned decay: dL/dq = -a / m = -a exp(L))
+                        q.backward(ops.copy_q_grad(a.detach(), row_loss, 1.0 / (2 * n)), retain_graph=True)
+                    total = total + row_loss.sum() / (2 * n)
+            optimizer.step()
+            out.append(total)
+    finally:
+        model.train(was_training)
+    return [float(x) for x in torch.stack(out).cpu()] if out else []
+
+
+def rows_rel(store, idx):
+    """The relation (int32 device [n]) of the stream positions idx: the gold class of the relation head, both directions."""
+    pos = torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int64)).to(store.device)
+    return store.t['q_r'][pos].contiguous()
 
 
 def fit_gate(model, obs, idx, gate, optimizer, steps=1, max_batch=4096):

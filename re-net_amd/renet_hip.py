@@ -191,6 +191,13 @@ _SIGNATURES = {
                                                  c_int, c_int, c_void_p] + [c_void_p] * 4),
     'renet_joint_mix_rows': (c_int, [c_void_p] * 3 + [c_int] + [c_void_p] * 3 + [c_int, c_void_p, c_void_p, c_int, c_int,
                                      c_void_p, c_int, c_int, c_int, c_void_p, c_float, c_float, c_void_p, c_void_p]),
+    'renet_joint_gold_rows': (c_int, [c_void_p] * 5 + [c_int] + [c_void_p] * 3 + [c_int, c_void_p, c_void_p, c_int, c_int, c_int,
+                                      c_int, c_float] + [c_void_p] * 3),
+    'renet_joint_gold_rows_decay': (c_int, [c_void_p] * 5 + [c_int] + [c_void_p] * 3 + [c_int, c_void_p, c_void_p, c_int, c_int,
+                                            c_int, c_int, c_void_p] + [c_void_p] * 4),
+    'renet_joint_mix_ce': (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, c_float] + [c_void_p] * 5),
+    'renet_joint_mix_ce_planes': (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_size_t, c_int,
+                                          c_int, c_void_p, c_void_p, c_void_p]),
     'renet_mix_ce': (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_float] + [c_void_p] * 4),
     'renet_mix_ce_planes': (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_size_t, c_int, c_int,
                                     c_void_p, c_void_p]),
@@ -360,7 +367,7 @@ def _timed_end(t0, name, flops=0.0, nbytes=0.0, tag=None):
 GLUE = ('softmax_ce_planes', 'gather_rows', 'segment_add', 'segment_add2', 'compose_table_items', 'rgcn_bwd_prep', 'colsum',
         'scale_by_device_scalar', 'seq_assemble_fwd', 'seq_assemble_fwd_bf16', 'softmax_ce_bf16', 'seq_assemble_bwd',
         'concat3_fwd', 'concat3_bwd', 'dropout', 'softmax_ce', 'adam_step', 'segment_pool_fwd', 'segment_pool_bwd',
-        'pack_bf16_glue', 'soft_ce_sparse', 'mix_ce', 'mix_ce_planes')
+        'pack_bf16_glue', 'soft_ce_sparse', 'mix_ce', 'mix_ce_planes', 'joint_mix_ce', 'joint_mix_ce_planes')
 _glue_saved = {}
 
 
@@ -995,6 +1002,33 @@ def mix_ce_planes(logits, target, a_row, q_row, grad_scale, row_loss=None, want_
     return row_loss, dl, d_a
 
 
+def joint_mix_ce_planes(logits, target, a_row, q_row, lp_row, grad_scale, row_loss=None, want_da=True):
+    """mix_ce_planes for the loss through the JOINT mix (renet_joint_mix_ce_planes): lp_row (fp32 device [B], <= 0) is the log-
+    probability the relation head gives its gold class and q_row the prior's mass on the gold PAIR (joint_gold_rows).  ->
+    (row_loss[B] = -log((1 - a) p_gold exp(lp) + a q), PlanesMat (softmax - onehot) * grad_scale * s, d_a[B] or None, s_row[B])."""
+    b, c = logits.shape
+    pa, pq = _copy_rows(a_row, q_row, b, 'joint_mix_ce_planes')
+    plp = _lp_row(lp_row, b, 'joint_mix_ce_planes')
+    if row_loss is None:
+        row_loss = torch.empty(b, device=logits.device, dtype=torch.float32)
+    d_a = torch.empty(b, device=logits.device, dtype=torch.float32) if want_da else None
+    s_row = torch.empty(b, device=logits.device, dtype=torch.float32)
+    dl = planes_empty(b, c, logits.device)
+    _check(lib().renet_joint_mix_ce_planes(logits.data_ptr(), _i32(target), pa, pq, plp, b, c, _ld(logits), float(grad_scale),
+                                           _f32(row_loss), dl.p.data_ptr(), dl.plane, dl.p.shape[2], dl.p.shape[1], _f32(d_a),
+                                           s_row.data_ptr(), _stream()), 'joint_mix_ce_planes')
+    return row_loss, dl, d_a, s_row
+
+
+def _lp_row(lp_row, b, what):
+    if lp_row is None:
+        raise RenetHipError('%s: lp_row is missing' % what)
+    if not (torch.is_tensor(lp_row) and lp_row.is_cuda and lp_row.dtype == torch.float32 and lp_row.is_contiguous()
+            and lp_row.numel() == b):
+        raise RenetHipError('%s: lp_row must be a contiguous float32 device tensor with one entry per row' % what)
+    return lp_row.data_ptr()
+
+
 class F32Op(object):
     """An fp32 GEMM operand together with the bound on its largest magnitude that the f16x3 GEMM scales it by:
     `part` holds n <= 256 device floats whose maximum bounds max |t| (renet_maxabs_partials, or a known bound)."""
@@ -1529,6 +1563,22 @@ def mix_ce(logits, target, a_row, q_row, grad_scale, want_grad, row_loss=None, w
     return row_loss, d_a
 
 
+def joint_mix_ce(logits, target, a_row, q_row, lp_row, grad_scale, want_grad, row_loss=None, want_da=True):
+    """mix_ce for the loss through the JOINT mix (renet_joint_mix_ce; lp_row as for joint_mix_ce_planes): -> (row_loss[B],
+    d_a[B] or None, s_row[B]); if want_grad, logits is OVERWRITTEN with (softmax - onehot) * grad_scale * s."""
+    b, c = logits.shape
+    pa, pq = _copy_rows(a_row, q_row, b, 'joint_mix_ce')
+    plp = _lp_row(lp_row, b, 'joint_mix_ce')
+    if row_loss is None:
+        row_loss = torch.empty(b, device=logits.device, dtype=torch.float32)
+    d_a = torch.empty(b, device=logits.device, dtype=torch.float32) if want_da else None
+    s_row = torch.empty(b, device=logits.device, dtype=torch.float32)
+    _check(lib().renet_joint_mix_ce(logits.data_ptr(), _i32(target), pa, pq, plp, b, c, _ld(logits), float(grad_scale),
+                                    _f32(row_loss), logits.data_ptr() if want_grad else None, _f32(d_a), s_row.data_ptr(),
+                                    _stream()), 'joint_mix_ce')
+    return row_loss, d_a, s_row
+
+
 def soft_ce_sparse(logits, tgt_ptr, tgt_col, tgt_w, grad_scale, want_grad, row_loss=None):
     """renet_soft_ce_sparse on logits [B, C] (fp32, unit inner stride) with the CSR soft targets tgt_ptr [B + 1] (int32),
     tgt_col [nnz] (int32; per row distinct, ascending) and tgt_w [nnz] (fp32, >= 0; a row need not sum to 1): returns
@@ -1902,6 +1952,55 @@ def recurrence_gold_rows_decay(ent, rel, t, as_of, gold, tables, ent_ptr, snap_p
                                                   _f32(ihl_row, 'ihl_row'), q.data_ptr(), w.data_ptr(), dq.data_ptr(),
                                                   _stream()), 'recurrence_gold_rows_decay')
     _timed_end(t0, 'recurrence_gold_rows', nbytes=float(n * 36))
+    return q, w, dq
+
+
+JOINT_MAX_RELS = 1024                  # renet_joint_mix_rows, renet_joint_gold_rows: R at most this
+
+
+def _joint_gold_front(what, ent, rel, t, as_of, gold, tables, ent_ptr, snap_ptr, num_ent, num_rels, num_cols):
+    n = int(ent.numel())
+    if any(int(a.numel()) != n for a in (rel, t, as_of, gold)):
+        raise RenetHipError('%s: ent, rel, t, as_of and gold must have one entry per row' % what)
+    if not 1 <= int(num_rels) <= JOINT_MAX_RELS:
+        raise RenetHipError('%s: num_rels must lie in [1, %d]' % (what, JOINT_MAX_RELS))
+    p_rel, p_other, p_t = tables
+    nf = int(p_rel.numel())
+    if p_other.numel() != nf or p_t.numel() != nf or ent_ptr.numel() != int(num_ent) + 1:
+        raise RenetHipError('%s: the pair tables do not fit num_ent / their own lengths' % what)
+    return n, (_i32(ent, 'ent'), _i32(rel, 'rel'), _i32(t, 't'), _i32(as_of, 'as_of'), _i32(gold, 'gold'), n,
+               *[_i32(a, 'pair table') if nf else None for a in tables], nf, _i32(ent_ptr, 'ent_ptr'),
+               _i32(snap_ptr, 'snap_ptr'), int(snap_ptr.numel()) - 1, int(num_ent), int(num_rels), int(num_cols))
+
+
+def joint_gold_rows(ent, rel, t, as_of, gold, tables, ent_ptr, snap_ptr, num_ent, num_rels, num_cols, inv_half_life=0.0):
+    """renet_joint_gold_rows, one direction: -> (q, W), fp32 device [n].  Row i is the given entity ent_i with the GOLD relation
+    rel_i and the gold partner gold_i (int32 device [n]); W_i is the entity-wide W of joint_mix_rows (fp32 of its mass, bit for
+    bit) and q_i = w_i[rel_i, gold_i] / W_i the prior's mass on the gold PAIR.  Both 0 where the entity has no history before
+    as_of_i or lies outside [0, num_ent); q_i = 0 where gold_i lies outside [0, num_cols) or rel_i outside [0, num_rels).
+    num_rels in [1, 1024]."""
+    n, front = _joint_gold_front('joint_gold_rows', ent, rel, t, as_of, gold, tables, ent_ptr, snap_ptr, num_ent, num_rels,
+                                 num_cols)
+    q = torch.empty(n, device=ent.device, dtype=torch.float32)
+    w = torch.empty(n, device=ent.device, dtype=torch.float32)
+    t0 = _timed()
+    _check(lib().renet_joint_gold_rows(*front, float(inv_half_life), q.data_ptr(), w.data_ptr(), _stream()), 'joint_gold_rows')
+    _timed_end(t0, 'joint_gold_rows', nbytes=float(n * 28))
+    return q, w
+
+
+def joint_gold_rows_decay(ent, rel, t, as_of, gold, tables, ent_ptr, snap_ptr, num_ent, num_rels, num_cols, ihl_row):
+    """renet_joint_gold_rows_decay, one direction: -> (q, W, dq), fp32 device [n]: joint_gold_rows with the decay of row i taken
+    from ihl_row (fp32 device [n], each finite and >= 0: the caller's to keep) and dq_i = d q_i / d ihl_row[i], exactly 0 where
+    W_i = 0 or the gold pair has no counted fact.  A constant ihl_row gives the (q, W) of joint_gold_rows bit for bit."""
+    n, front = _joint_gold_front('joint_gold_rows_decay', ent, rel, t, as_of, gold, tables, ent_ptr, snap_ptr, num_ent,
+                                 num_rels, num_cols)
+    ihl_row = _row_floats(ihl_row, n, 'joint_gold_rows_decay: ihl_row')
+    q, w, dq = (torch.empty(n, device=ent.device, dtype=torch.float32) for _ in range(3))
+    t0 = _timed()
+    _check(lib().renet_joint_gold_rows_decay(*front, _f32(ihl_row, 'ihl_row'), q.data_ptr(), w.data_ptr(), dq.data_ptr(),
+                                             _stream()), 'joint_gold_rows_decay')
+    _timed_end(t0, 'joint_gold_rows', nbytes=float(n * 36))
     return q, w, dq
 
 

@@ -45,6 +45,12 @@ connected to each object before the query's as-of time, ranked under the same hi
 model MIXED with the prior at weight ALPHA, each labelled as such.  The baseline is a protocol-matched yardstick: report it
 with its ALPHA and half-life (in the dataset's raw timestamp units), beside model numbers of the same protocol only.
 
+--events [K] --recurrence ALPHA [--half-life H] --fit-gate STEPS [--learn-half-life] fits the EVENT gate INSTEAD of the
+per-relation entity gate (one invocation fits one gate; the entity blocks above it are those of the initial prior): a
+recurrence.CopyGate(per_relation=False) -- one gate, and with --learn-half-life one decay, per side -- through the joint mix
+(recurrence.fit_event_gate) on the VALID split, the model frozen; it prints the fitted alpha and half-life per side, then the
+event numbers with the fitted gate, with the initial prior and without a prior.  WARNING: numbers with a fitted event gate are a
+protocol of their own: report them with the initial ALPHA and H, the fitting split, STEPS and --gate-lr.
 --fit-gate STEPS (with --recurrence) LEARNS the weight of the prior: a recurrence.CopyGate -- one gate per side and relation,
 initialised to ALPHA -- is fitted with the model frozen (recurrence.fit_gate, STEPS Adam steps at --gate-lr) on the VALID
 split under observed histories, and the chosen split is then evaluated mixed with the learned gates.  --online --recurrence
@@ -59,6 +65,7 @@ the gate carries one half-life per side and relation (recurrence.CopyGate(learn_
 by the same optimizer through q's derivative by the decay (renet_recurrence_gold_rows_decay).  The lines printed give the min,
 median and max of the learned half-lives per side beside the gate range, and the JSON record holds them.  Numbers with learned
 parameters are a protocol of their own: report the INITIAL alpha and half-life, the fitting split, steps and learning rate.
+With --events --fit-gate the EVENT gate carries ONE half-life per side (renet_joint_gold_rows_decay); both are printed.
 
 --events adds the EVENT forecasts (RENet.evaluate_events_observed): MRR / Hits of the gold (relation, entity) pair among all
 pairs of the given entity, and of the gold relation given both endpoints, in the three settings; with K also the K most
@@ -288,12 +295,14 @@ def main():
     ap.add_argument('--half-life', type=float, default=None, metavar='H',
                     help='half-life of the recurrence prior in raw timestamp units (default: frequency only)')
     ap.add_argument('--fit-gate', type=int, default=None, metavar='STEPS',
-                    help='fit a per-relation gate on the valid split (model frozen), then evaluate mixed with it (--recurrence)')
+                    help='fit a per-relation gate on the valid split (model frozen), then evaluate mixed with it (--recurrence); with '
+                         '--events: fit the EVENT gate instead, one gate per side through the joint mix, and print the event '
+                         'numbers with it')
     ap.add_argument('--learn-copy', action='store_true',
                     help='online steps train through the mix and the gates learn along the stream (--online --recurrence)')
     ap.add_argument('--learn-half-life', action='store_true',
                     help='the gate also learns one half-life per side and relation, from H (--recurrence --half-life with '
-                         '--fit-gate or --online --learn-copy)')
+                         '--fit-gate or --online --learn-copy); with --events --fit-gate: one half-life per side')
     ap.add_argument('--gate-lr', type=float, default=1e-2, help='learning rate of the gate (--fit-gate, --learn-copy)')
     args = ap.parse_args()
     if args.recurrence is not None:
@@ -429,7 +438,7 @@ def main():
                      baseline={name: U.rank_metrics(base_ranks[name]) for name in SETTINGS},
                      mixed={name: U.rank_metrics(mix_ranks[name]) for name in SETTINGS})
         print(json.dumps(extra))
-        if args.fit_gate is not None:
+        if args.fit_gate is not None and args.events is None:            # (with --events the EVENT gate is fitted instead, below)
             if splits[1] is None:
                 raise SystemExit('--fit-gate fits on the valid split: %s has no valid.txt' % data_dir)
             gate = recurrence.CopyGate(num_rels, alpha=args.recurrence, half_life=args.half_life,
@@ -488,6 +497,34 @@ def main():
             prior = recurrence.RecurrencePrior(args.recurrence, args.half_life)
             tag = 'alpha %g, half-life %s' % (prior.alpha, 'none (frequency only)' if prior.half_life is None else '%g' % prior.half_life)
             event_record['recurrence'] = {'alpha': prior.alpha, 'half_life': prior.half_life}
+            if args.fit_gate is not None:
+                # the EVENT gate: one gate (and, with --learn-half-life, one decay) per side, fitted through the joint mix on
+                # the valid split with the model frozen -- a protocol of its own, reported with what it started from
+                if splits[1] is None:
+                    raise SystemExit('--fit-gate fits on the valid split: %s has no valid.txt' % data_dir)
+                egate = recurrence.CopyGate(num_rels, alpha=args.recurrence, half_life=args.half_life, per_relation=False,
+                                            learn_half_life=args.learn_half_life).to(dev)
+                t3 = time.perf_counter()
+                efit = recurrence.fit_event_gate(model, obs, obs.positions('valid'), egate,
+                                                 torch.optim.Adam(egate.parameters(), lr=args.gate_lr), steps=args.fit_gate,
+                                                 max_batch=args.max_batch)
+                torch.cuda.synchronize()
+                alphas, rates = recurrence.event_scalars(egate)
+                lives = {k: (None if v == 0.0 else 1.0 / v) for k, v in rates.items()}
+                print('EVENT GATE fitted on the valid split%s (model frozen, %d Adam steps at lr %g from alpha %g, half-life %s): '
+                      'fit %.2f s, mean joint loss of the valid split %.6f -> %.6f; alpha ob side %.4f, sub side %.4f; half-life '
+                      'ob side %s, sub side %s'
+                      % (' -- THE EVALUATED SPLIT ITSELF' if args.split == 'valid' else '', args.fit_gate, args.gate_lr,
+                         args.recurrence, 'none (frequency only)' if args.half_life is None else '%g' % args.half_life,
+                         time.perf_counter() - t3, efit[0], efit[-1], alphas['ob'], alphas['sub'],
+                         *('none' if lives[k] is None else '%.4g' % lives[k] for k in ('ob', 'sub'))))
+                event_record['fitted_gate'] = {'alpha': alphas, 'half_life': lives, 'fitted_on': 'valid', 'fit_steps': args.fit_gate,
+                                               'gate_lr': args.gate_lr, 'initial_alpha': args.recurrence,
+                                               'initial_half_life': args.half_life, 'learn_half_life': bool(args.learn_half_life)}
+                event_record['mixed_fitted_gate'] = event_pass(
+                    'event forecasts, MODEL MIXED WITH THE FITTED EVENT GATE (a protocol of its own: report it with the initial %s, '
+                    'the fitting split, %d steps and lr %g)' % (tag, args.fit_gate, args.gate_lr),
+                    lambda: model.evaluate_events_observed(obs, idx, prior=egate))
             event_record['baseline'] = event_pass('event forecasts, RECURRENCE BASELINE ALONE (no model), %s' % tag,
                                                   lambda: recurrence.evaluate_events(obs, idx, prior))
             event_record['mixed'] = event_pass('event forecasts, MODEL MIXED WITH THE RECURRENCE PRIOR, %s' % tag,
